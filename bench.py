@@ -20,7 +20,14 @@ A GPU's share of the job is a list of record-level batches (<= 1024 windows
 each, and at least --min-batches (2)) dealt over --split (4) contexts of the
 GPU -- what the driver does with its PF_DEV_CONTEXTS contexts per GPU -- and
 every step launches all of them.
-The first batch alone gives the per-kernel figures and the roofline.
+A plain run does only that: it sets the job up, warms up, times --steps steps,
+writes the last step's results when --dump-outputs DIR is given and prints the
+result line; the base windows are mapped from build/bench_inputs/ when
+--prepare-inputs (run by build()) wrote them there, else generated (the same
+batch, a quarter of a minute later).  Everything else is behind --full: the first batch alone (the
+per-kernel figures and the roofline), the calls-level, fixed-gap, projection,
+PCIe-inclusive and end-to-end legs and the CPU baseline with its comparison
+against the oracle.
 `--calls-level` times the previous boundary instead (reads and 5mC calls
 resident, no K0).  --coverage 30 --windows 256 is configs[1]'s shape.
 
@@ -30,7 +37,7 @@ job's windows are dealt over the ranks by the product's LPT
 line is the same job as the N=8 line; no collective in the data path; after
 each step the int8 decisions are all-gathered over RCCL (the drop-in's only
 exchange: the host that writes VCF/GTF needs all decisions).  --weak gives
-every rank a whole job of its own.  At N=1 the `strong_projection` leg times
+every rank a whole job of its own.  At N=1 with --full the `strong_projection` leg times
 rank 0's share of the same job at N=2/4/8 on this GPU, and `critical_window`
 the heaviest window alone (the floor of any GPU's step).
 
@@ -44,7 +51,9 @@ import os
 import sys
 import time
 
-import numpy as np
+T_START = time.perf_counter()
+
+import numpy as np  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
@@ -517,6 +526,90 @@ def compare_with_oracle(out, wro, ref, sub, tags: bool = True):
     return bad
 
 
+INPUT_CACHE = os.path.join(HERE, "build", "bench_inputs")
+
+
+def input_cache_dir(spec) -> str:
+    """Where the record-level batch of `spec` is kept once prepared: under
+    build/ (ignored by git), named by a digest of the spec and of the
+    generator's source, so that a batch of another generator is never read."""
+    import hashlib
+    h = hashlib.sha1(repr(spec).encode())
+    for mod in ("synth_aln.py", "synth.py"):
+        with open(os.path.join(HERE, "pomfret_amd", mod), "rb") as f:
+            h.update(f.read())
+    return os.path.join(INPUT_CACHE, h.hexdigest()[:16])
+
+
+def headline_spec(wl: dict, seed: int = 1000):
+    from pomfret_amd.synth_aln import AlnSpec
+    return AlnSpec(n_windows=wl["n_windows"], coverage=wl["coverage"], gap=wl["gap"], seed=seed,
+                   gap_mix=wl["gap_mix"], skip_frac=wl["skip_frac"], nosite_frac=wl["nosite_frac"])
+
+
+def prepare_inputs() -> None:
+    """Generate the default job's base windows once (13 GB, a quarter of a
+    minute on 16 cores) and keep them as plain .npy files, one per field, so
+    that a benchmark run maps them instead of generating them again.  Best
+    effort: without the files (no room, read-only tree) every run generates
+    its batch as before; the batch is the same either way."""
+    import shutil
+    from pomfret_amd.synth_aln import _SAVE_FIELDS, make_aln_batch
+    spec = headline_spec(WORKLOAD)
+    path = input_cache_dir(spec)
+    if os.path.isdir(path):
+        return
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        aln = make_aln_batch(spec, workers=0)
+        os.makedirs(tmp)
+        for k in _SAVE_FIELDS:
+            np.save(os.path.join(tmp, k + ".npy"), getattr(aln, k))
+        np.save(os.path.join(tmp, "orient.npy"), aln.meta["orient"])
+        os.rename(tmp, path)
+    except OSError as e:
+        log(f"[bench] inputs not prepared ({e}); runs will generate them")
+        shutil.rmtree(tmp, ignore_errors=True)
+
+
+def load_inputs(path: str):
+    """The batch prepare_inputs() wrote, memory-mapped read-only."""
+    from pomfret_amd import AlnBatch
+    from pomfret_amd.synth_aln import _SAVE_FIELDS
+    b = AlnBatch(**{k: np.load(os.path.join(path, k + ".npy"), mmap_mode="r") for k in _SAVE_FIELDS})
+    b.meta["orient"] = np.load(os.path.join(path, "orient.npy"))
+    return b
+
+
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(path: str, outs, max_bytes: int = DUMP_MAX_BYTES):
+    """The headline's results of its last timed step as `path`/<field>.npy:
+    every field of the batches' WindowResult, concatenated in batch order,
+    as float64 (Fisher p) or float32 (every other field; the integer fields
+    are far below 2^24, so the conversion is exact).  The files take at most
+    `max_bytes` in all: the fields are written smallest first, and one that
+    would take more than an equal share of what is left is written as a
+    fixed seeded sample of its rows (sorted indices, the same from run to
+    run)."""
+    from dataclasses import fields
+    os.makedirs(path, exist_ok=True)
+    arrs = []
+    for f in fields(outs[0]):
+        a = np.concatenate([np.asarray(getattr(o, f.name)) for o in outs])
+        arrs.append((f.name, a.astype(np.float64 if a.dtype == np.float64 else np.float32)))
+    arrs.sort(key=lambda na: na[1].nbytes)
+    left = max_bytes - 128 * len(arrs)               # the .npy headers
+    for i, (name, a) in enumerate(arrs):
+        row = a.itemsize * max(1, int(np.prod(a.shape[1:])))
+        n_max = left // (len(arrs) - i) // row
+        if a.shape[0] > n_max:
+            a = a[np.sort(np.random.default_rng(20240229).choice(a.shape[0], n_max, replace=False))]
+        left -= a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -533,6 +626,16 @@ def main():
     ap.add_argument("--weak", action="store_true",
                     help="every rank runs a whole job of its own (seeds differ per rank) instead of its LPT "
                          "share of one job")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the first batch alone (per-kernel figures, "
+                         "roofline), the calls-level, fixed-gap, projection, PCIe-inclusive and end-to-end legs "
+                         "and the CPU baseline (each still subject to --no-cpu / --no-legs / --e2e-*)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step of the headline (every batch's WindowResult "
+                         "fields, concatenated in batch order) as DIR/<name>.npy")
+    ap.add_argument("--prepare-inputs", action="store_true",
+                    help="generate the default job's base windows, keep them under build/bench_inputs/ for "
+                         "later runs (what build() does) and exit")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
     ap.add_argument("--no-legs", action="store_true",
                     help="skip the calls-level, fixed-gap, projection, PCIe-inclusive and end-to-end legs")
@@ -554,6 +657,12 @@ def main():
     ap.add_argument("--calls-level", action="store_true",
                     help="time the calls-level boundary (reads + 5mC calls resident, no K0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.prepare_inputs:
+        prepare_inputs()
+        return
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -573,21 +682,27 @@ def main():
     n_job = n_base * tiles
     split = max(1, args.split)
     seed = 1000 + (rank if args.weak else 0)
-    spec = AlnSpec(n_windows=n_base, coverage=wl["coverage"], gap=wl["gap"], seed=seed, gap_mix=wl["gap_mix"],
-                   skip_frac=wl["skip_frac"], nosite_frac=wl["nosite_frac"])
+    spec = headline_spec(wl, seed)
     t = time.perf_counter()
     if record_level:
-        # generated (in worker processes) before anything touches the GPU;
-        # PF_BENCH_ALN_CACHE: a batch saved beforehand (tools/run_aln_once.py,
-        # same spec), so that a traced run forks no generator workers
+        # generated (in worker processes) before anything touches the GPU,
+        # unless the batch is at hand: PF_BENCH_ALN_CACHE names one saved
+        # beforehand (tools/run_aln_once.py, same spec), so that a traced run
+        # forks no generator workers; else the one prepare_inputs() wrote
         cache = os.environ.get("PF_BENCH_ALN_CACHE")
+        prepared = input_cache_dir(spec)
+        how = "generated"
         if cache and os.path.exists(cache) and not args.weak:
             from pomfret_amd.synth_aln import load_aln
             aln = load_aln(cache)
             assert aln.n_windows == n_base, "PF_BENCH_ALN_CACHE holds another batch"
+            how = "loaded"
+        elif os.path.isdir(prepared):
+            aln = load_inputs(prepared)
+            how = "mapped (prepared by build())"
         else:
             aln = make_aln_batch(spec, workers=0 if world == 1 else max(1, CPU_SHARE // 2))
-        log(f"[bench] rank {rank}: generated {aln.n_windows} base windows, {aln.n_recs} BAM records "
+        log(f"[bench] rank {rank}: {how} {aln.n_windows} base windows, {aln.n_recs} BAM records "
             f"({aln.nbytes() / 1e9:.2f} GB) in {time.perf_counter() - t:.1f}s")
         base_costs = aln_window_costs(aln)
     else:
@@ -644,7 +759,8 @@ def main():
         f"(upload: validation, SEQ repack, H2D; no device work): {time.perf_counter() - t:.1f}s")
     db = dbs[0]
     aln0 = subs[0]
-    if record_level:
+    batch = None                                     # the loaded reads: --full's byte model and legs
+    if full and record_level:
         off, cpos, ccat, _, _ = db.debug_calls()
         rr = db.read_recs()
         # the loaded reads as a window batch (the byte model and the calls-level
@@ -656,7 +772,7 @@ def main():
                             read_hp=aln0.hp[rr], read_call_off=off, call_pos=cpos, call_cat=ccat,
                             win_cov_sel=aln0.win_cov_sel, win_cov_rt=aln0.win_cov_rt, win_n_cand=aln0.win_n_cand)
         del off, cpos, ccat
-    else:
+    elif full:
         batch = cbatch.select(groups[0][1])
 
     def timed(dbs_, steps=None):
@@ -727,37 +843,43 @@ def main():
             total = float(rt.item()) * steps
         return elapsed, total, kern_acc, [o[(steps - 1) % 2] if steps else o[0] for o in outs]
 
-    # 1. the first batch alone on one context: the per-kernel figures and the roofline
-    el1, tot1, kern_acc, outs1 = timed([db])
-    out = outs1[0]
-    single = {"value": round(tot1 / el1, 1), "ms_per_step": round(el1 / args.steps * 1e3, 4),
-              "windows": int(db.n_windows), "reads": int(out.win_n_reads.sum()),
-              "what": "the rank's first batch alone on one context (kernels and roofline measured here)"}
-    log(f"[bench] single batch: {json.dumps(single)}")
-    stats = db.stats()
-    kmean = {k: v / args.steps for k, v in kern_acc.items()}
-    ab = algo_bytes(batch, stats, out.win_n_sites, db.heavy_problems())
-    if record_level:
-        ab["pf_k0_load"] = k0_bytes(aln0, rr, batch.n_calls)
-        ab["pf_k0_pack"] = pack_bytes(aln0.n_recs, batch.n_reads, batch.n_calls)
-    else:
-        kmean.pop("pf_k0_load", None)
-        kmean.pop("pf_k0_pack", None)
-    kernels = {}
-    for k, ms in kmean.items():
-        b = ab.get(k, 0)
-        kernels[k] = {"ms": round(ms, 4), "algo_bytes": int(b),
-                      "GBps": round(b / (ms * 1e-3) / 1e9, 2) if ms > 0 else None}
-    dom = max(kmean, key=kmean.get)
-    achieved = kernels[dom]["GBps"]
     boundary = "records" if record_level else "calls"
-    traffic = pmc_traffic(dom, dict(wl, windows_per_gpu=batch.n_windows), boundary)
+    out = single = kernels = dom = achieved = traffic = None
+    if full:
+        # 1. the first batch alone on one context: the per-kernel figures and the roofline
+        el1, tot1, kern_acc, outs1 = timed([db])
+        out = outs1[0]
+        single = {"value": round(tot1 / el1, 1), "ms_per_step": round(el1 / args.steps * 1e3, 4),
+                  "windows": int(db.n_windows), "reads": int(out.win_n_reads.sum()),
+                  "what": "the rank's first batch alone on one context (kernels and roofline measured here)"}
+        log(f"[bench] single batch: {json.dumps(single)}")
+        stats = db.stats()
+        kmean = {k: v / args.steps for k, v in kern_acc.items()}
+        ab = algo_bytes(batch, stats, out.win_n_sites, db.heavy_problems())
+        if record_level:
+            ab["pf_k0_load"] = k0_bytes(aln0, rr, batch.n_calls)
+            ab["pf_k0_pack"] = pack_bytes(aln0.n_recs, batch.n_reads, batch.n_calls)
+        else:
+            kmean.pop("pf_k0_load", None)
+            kmean.pop("pf_k0_pack", None)
+        kernels = {}
+        for k, ms in kmean.items():
+            b = ab.get(k, 0)
+            kernels[k] = {"ms": round(ms, 4), "algo_bytes": int(b),
+                          "GBps": round(b / (ms * 1e-3) / 1e9, 2) if ms > 0 else None}
+        dom = max(kmean, key=kmean.get)
+        achieved = kernels[dom]["GBps"]
+        traffic = pmc_traffic(dom, dict(wl, windows_per_gpu=batch.n_windows), boundary)
 
     # 2. the headline: the rank's whole share, every batch launched every step
     elapsed, total_reads, _, job_outs = timed(dbs)
     value = total_reads / elapsed
     ms_per_step = elapsed / args.steps * 1e3
     job_reads = int(sum(int(o.win_n_reads.sum()) for o in job_outs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, job_outs)
+    if out is None:
+        out = job_outs[0]                            # the first batch, as the headline ran it
     # every copy of a base window must get the same decision and tags
     dec_by_base = {}
     consistent = True
@@ -780,7 +902,7 @@ def main():
     log(f"[bench] job: {json.dumps(job)}")
 
     calls_leg = None
-    if record_level and not args.no_legs and world == 1:
+    if full and record_level and not args.no_legs and world == 1:
         # the same reads with K0's calls already resident (the calls-level
         # boundary, pf_batch_upload): K12 + K3 + epilogue only
         dbc = ctx.upload(cfg, batch)
@@ -794,7 +916,7 @@ def main():
 
     proj = None
     crit = None
-    if record_level and not args.no_legs and world == 1 and not args.weak:
+    if full and record_level and not args.no_legs and world == 1 and not args.weak:
         # Strong scaling projected on this GPU: rank 0's LPT share of the same
         # job at N GPUs, timed here (the ranks' shares are equal by the deal:
         # max/mean load below), aggregate = job reads / that step time.
@@ -874,7 +996,7 @@ def main():
         log(f"[bench] critical window: {json.dumps(crit)}")
 
     fixed_leg = None
-    if record_level and not args.no_legs and args.workload == "mix" and world == 1:
+    if full and record_level and not args.no_legs and args.workload == "mix" and world == 1:
         # round 2's headline workload (50 kb gaps, every window decided), one
         # 1024-window batch per context: the rate the gap mix is compared with
         wl50 = dict(WORKLOADS["fixed50"], n_windows=n_base, coverage=wl["coverage"])
@@ -895,7 +1017,7 @@ def main():
     # PCIe-inclusive rate (never `value`): the one-shot boundary call hands
     # over host buffers -- upload (validation, pinned staging, H2D), run, D2H
     pcie = None
-    if not args.no_legs and record_level:
+    if full and not args.no_legs and record_level:
         t1 = time.perf_counter()
         n_once = 2
         for _ in range(n_once):
@@ -908,7 +1030,7 @@ def main():
                         "the first batch, rank 0"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and record_level:
+    if full and rank == 0 and world == 1 and not args.no_cpu and record_level:
         # BASELINE's target is phrased against the reference's -t 32.  The
         # port runs with min(32, effective cores) threads -- the effective
         # cores are the affinity set capped by the cgroup quota (the GPU box
@@ -961,7 +1083,7 @@ def main():
     records_per_gpu = (int(sum(int(np.diff(aln.win_rec_off.astype(np.int64))[bw].sum()) for _, bw in groups))
                        if record_level else None)
     n_batches = len(dbs)
-    e2e_any = rank == 0 and world == 1 and not args.no_legs and (
+    e2e_any = full and rank == 0 and world == 1 and not args.no_legs and (
         (args.e2e_windows > 0 and record_level) or args.e2e_u_scale > 0)
     if e2e_any:
         for d in dbs:
@@ -973,7 +1095,7 @@ def main():
         gc.collect()
 
     e2e = None
-    if rank == 0 and world == 1 and not args.no_legs and args.e2e_windows > 0 and record_level:
+    if e2e_any and args.e2e_windows > 0 and record_level:
         threads = args.cpu_threads or min(CPU_SHARE, len(os.sched_getaffinity(0)))
         # (round 2's 64-window BAM: the 50 kb workload, so the fetch rates compare across rounds)
         e2e = e2e_leg(ctx, cfg, lcfg, dict(WORKLOADS["fixed50"], coverage=wl["coverage"]),
@@ -983,7 +1105,7 @@ def main():
         log(f"[bench] e2e: {json.dumps(e2e)}")
 
     e2e_u = None
-    if rank == 0 and world == 1 and not args.no_legs and args.e2e_u_scale > 0:
+    if e2e_any and args.e2e_u_scale > 0:
         threads = args.cpu_threads or min(CPU_SHARE, len(os.sched_getaffinity(0)))
         e2e_u = e2e_u_leg(ctx, lcfg, threads, os.environ.get("TMPDIR", "/tmp"), scale=args.e2e_u_scale,
                           cpu=not args.no_cpu, cpu_threads=args.cpu_threads or min(32, effective_cores()[0]))
@@ -1026,9 +1148,10 @@ def main():
             "parallelism": par,
             "batches_per_gpu": n_batches, "contexts_per_gpu": split,
         },
+        "full": full,
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": PEAK_HBM_GBPS,
                      "unit": "GB/s", "frac": round(achieved / PEAK_HBM_GBPS, 5) if achieved else None,
-                     "traffic": traffic, "measured_on": "single_batch"},
+                     "traffic": traffic, "measured_on": "single_batch"} if full else None,
         "kernels": kernels,
         "cpu_baseline": cpu,
         "vs_cpu_baseline": round(value / cpu["value"], 2) if cpu else None,
@@ -1053,6 +1176,10 @@ def main():
         c.close()
     if dist is not None:
         dist.destroy_process_group()
+    if rank == 0:
+        wall = time.perf_counter() - T_START
+        log(f"[bench] {wall:.1f}s in all, {wall - (args.steps + args.warmup) * ms_per_step * 1e-3:.1f}s of them "
+            f"outside the headline's {args.warmup} + {args.steps} steps")
 
 
 if __name__ == "__main__":

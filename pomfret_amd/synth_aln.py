@@ -70,6 +70,29 @@ class AlnSpec:
     nosite_frac: float = 0.0   # windows without allele- or unmethylated sites (no site qualifies, 4266)
 
 
+_ARANGE = np.arange(1 << 18)
+
+
+def _arange(n: int) -> np.ndarray:
+    """np.arange(n) as a view of a shared array (read-only use)."""
+    global _ARANGE
+    if n > _ARANGE.shape[0]:
+        _ARANGE = np.arange(2 * n)
+    return _ARANGE[:n]
+
+
+_MASK = np.zeros(1 << 18, bool)
+
+
+def _scratch_mask(n: int) -> np.ndarray:
+    """An all-False bool array of n elements, a view of a shared scratch
+    array: the caller clears what it sets."""
+    global _MASK
+    if n > _MASK.shape[0]:
+        _MASK = np.zeros(2 * n, bool)
+    return _MASK[:n]
+
+
 def _qual_from_cat(rng, cat):
     q = np.empty(cat.shape[0], np.uint8)
     m = cat == 0
@@ -216,44 +239,57 @@ def _build_reads(spec: AlnSpec, rng, ref: np.ndarray, rs0: np.ndarray, lens: np.
         core_len[-1] = m_last[r]
         core_op[-1] = 0
         # SEQ: reference bases of M ops, random bases of I ops
-        ref_cur = rs0[r] + np.concatenate([[0], np.cumsum(np.where(core_op == 1, 0, core_len))[:-1]])
+        rlen = np.where(core_op == 1, 0, core_len)
+        ref_cur = rs0[r] + np.cumsum(rlen) - rlen             # reference / query offset of each op
         qlen = np.where(core_op == 2, 0, core_len)
-        tot = int(qlen.sum())
-        q0 = np.concatenate([[0], np.cumsum(qlen)[:-1]])
-        idx = np.repeat(ref_cur - q0, qlen) + np.arange(tot)
-        kind = np.repeat(core_op, qlen)
-        bases = ref[np.where(kind == 0, idx, 0)]
-        refpos = np.where(kind == 0, idx, -1)
+        q0 = np.cumsum(qlen)
+        tot = int(q0[-1])
+        q0 -= qlen
+        idx = np.repeat(ref_cur - q0, qlen)                   # reference index of every query base
+        idx += _arange(tot)                                   # (an I op's bases: the cursor it sits at)
+        bases = ref[idx]
+        i_ops = np.flatnonzero(core_op == 1)
+        i_len = core_len[i_ops]
+        i_tot = int(i_len.sum())
+        ipos = np.repeat(q0[i_ops] - (np.cumsum(i_len) - i_len), i_len) + _arange(i_tot)   # inserted bases
         if snv is not None:                                   # het SNV alleles of the read's haplotype
-            on = (kind == 0) & (snv["alt_of"][np.maximum(idx, 0)] >= 0)
-            on &= snv["halt_of"][np.maximum(idx, 0)] == truth[r]
+            on = (snv["alt_of"][idx] >= 0) & (snv["halt_of"][idx] == truth[r])
+            on[ipos] = False
             bases[on] = snv["alt_of"][idx[on]]
-        ins_m = kind == 1
-        bases[ins_m] = rng.integers(0, 4, int(ins_m.sum()))
-        sub = (rng.random(tot) < spec.sub_rate) & ~ins_m
-        bases[sub] = (bases[sub] + rng.integers(1, 4, int(sub.sum()))) % 4
+        ins_m = _scratch_mask(tot)                            # the inserted bases as a mask (cleared below)
+        ins_m[ipos] = True
+        bases[ipos] = rng.integers(0, 4, i_tot)
+        sub = np.flatnonzero(rng.random(tot) < spec.sub_rate)
+        sub = sub[~ins_m[sub]]
+        bases[sub] = (bases[sub] + rng.integers(1, 4, sub.shape[0])) % 4
         if c1[r] or c2[r]:
             bases = np.concatenate([rng.integers(0, 4, c1[r]).astype(np.uint8), bases,
                                     rng.integers(0, 4, c2[r]).astype(np.uint8)])
-            refpos = np.concatenate([np.full(c1[r], -1), refpos, np.full(c2[r], -1)])
-        ops = []
+        h, n_core = int(c1[r] > 0), core_len.shape[0]
+        cigar = np.empty(h + n_core + int(c2[r] > 0), np.uint32)
+        cigar[h:h + n_core] = (core_len << 4) | core_op
         if c1[r]:
-            ops.append((c1[r], 4))
-        ops += list(zip(core_len.tolist(), core_op.tolist()))
+            cigar[0] = (c1[r] << 4) | 4
         if c2[r]:
-            ops.append((c2[r], 4))
-        cigar = np.array([(l << 4) | op for l, op in ops], np.uint32)
+            cigar[-1] = (c2[r] << 4) | 4
         md = _md_string(bases[c1[r]:], ref, rs0[r], core_op, core_len) if snv is not None else None
-        recs.append((bases, refpos, cigar, md))
+        # the CpGs of the stored SEQ (the C of each) and their reference index
+        # (-1: in a clip or an insertion)
+        cgp = np.flatnonzero((bases[:-1] == C_) & (bases[1:] == G_))
+        j = cgp - c1[r]
+        jc = np.minimum(np.maximum(j, 0), tot - 1)
+        rp = idx[jc]
+        rp[(j != jc) | ins_m[jc]] = -1
+        ins_m[ipos] = False
+        recs.append((bases, cgp, rp, cigar, md))
 
     # calls per read
     out = []
     for r in range(n):
-        bases, refpos, cigar, md_s = recs[r]
+        bases, cgp, rp, cigar, md_s = recs[r]
         lq = bases.shape[0]
-        cgp = np.flatnonzero((bases[:-1] == C_) & (bases[1:] == G_))     # C of each CpG (stored)
-        sid = site_of[np.maximum(refpos[cgp], 0)]
-        sid[refpos[cgp] < 0] = -1
+        sid = site_of[np.maximum(rp, 0)]
+        sid[rp < 0] = -1
         p = np.full(cgp.shape[0], 0.5)
         on = sid >= 0
         p[on] = site_p[sid[on]]
@@ -300,7 +336,7 @@ def _build_reads(spec: AlnSpec, rng, ref: np.ndarray, rs0: np.ndarray, lens: np.
             mm, ml = f"C+m.,{ds};", qual
         else:
             mm, ml = f"C+m?,{ds};", np.zeros(0, np.uint8)
-        codes = _NT16[bases]
+        codes = np.left_shift(np.uint8(1), bases)                # _NT16[bases]
         if lq & 1:
             codes = np.concatenate([codes, np.zeros(1, np.uint8)])
         seq = (codes[0::2] << 4) | codes[1::2]
@@ -388,8 +424,23 @@ def _md_string(core: np.ndarray, ref: np.ndarray, rs0: int, ops: np.ndarray, len
     return "".join(parts)
 
 
+_REC_ARRAYS = (("cigar", np.uint32), ("seq", np.uint8), ("mm", np.uint8), ("ml", np.uint8))
+
+
 def _window_job(args):
-    return make_aln_window(*args)
+    """make_aln_window with the records' arrays joined per window (a few
+    large arrays instead of several small ones per record: what a worker
+    process hands back, and what make_aln_batch joins over the windows)."""
+    p = make_aln_window(*args)
+    recs = p.pop("recs")
+    p["n_recs"] = len(recs)
+    p["l_qseq"] = np.array([r["l_qseq"] for r in recs], np.uint32)
+    for key, dt in _REC_ARRAYS:
+        p[key + "_len"] = np.array([r[key].shape[0] for r in recs], np.int64)
+        p[key] = np.concatenate([r[key] for r in recs]).astype(dt, copy=False) if recs else np.zeros(0, dt)
+    if recs and "md" in recs[0]:
+        p["md"] = [r["md"] for r in recs]
+    return p
 
 
 def window_cost_estimate(spec: AlnSpec, w: int) -> float:
@@ -460,16 +511,30 @@ def make_aln_batch(spec: AlnSpec, windows=None, workers: int = 0, jobs=None) -> 
         with mp.get_context("fork").Pool(workers) as pool:
             parts = pool.map(_window_job, jobs, chunksize=1)
     else:
-        parts = [make_aln_window(*j) for j in jobs]
-    recs = [r for p in parts for r in p["recs"]]
+        parts = [_window_job(j) for j in jobs]
 
-    def off(key, f=lambda x: x.shape[0]):
-        return np.concatenate([[0], np.cumsum([f(r[key]) for r in recs])]).astype(np.uint64)
+    def off(key):
+        lens = [p[key + "_len"] for p in parts]
+        return np.concatenate([[0], np.cumsum(np.concatenate(lens) if lens else [])]).astype(np.uint64)
 
     def cat(key, dt):
-        return np.concatenate([r[key] for r in recs]).astype(dt) if recs else np.zeros(0, dt)
+        """The windows' arrays joined; a large one (the bench batch's SEQ is
+        10 GB) by a few threads, each copying whole windows into place."""
+        ends = np.cumsum([p[key].shape[0] for p in parts], dtype=np.int64)
+        total = int(ends[-1]) if parts else 0
+        if total * np.dtype(dt).itemsize < (64 << 20):
+            return np.concatenate([p[key] for p in parts]).astype(dt, copy=False) if parts else np.zeros(0, dt)
+        out = np.empty(total, dt)
 
-    rc = np.array([len(p["recs"]) for p in parts], np.int64)
+        def copy(i):
+            out[ends[i] - parts[i][key].shape[0]:ends[i]] = parts[i][key]
+
+        from multiprocessing.pool import ThreadPool
+        with ThreadPool(min(8, max(workers, 1))) as tp:
+            tp.map(copy, range(len(parts)), chunksize=max(1, len(parts) // 64))
+        return out
+
+    rc = np.array([p["n_recs"] for p in parts], np.int64)
     b = AlnBatch(
         win_start=np.array([p["s"] for p in parts], np.uint32),
         win_end=np.array([p["e"] for p in parts], np.uint32),
@@ -477,7 +542,7 @@ def make_aln_batch(spec: AlnSpec, windows=None, workers: int = 0, jobs=None) -> 
         flag=np.concatenate([p["flag"] for p in parts]) if parts else np.zeros(0, np.uint16),
         mapq=np.concatenate([p["mapq"] for p in parts]) if parts else np.zeros(0, np.uint8),
         pos=np.concatenate([p["pos"] for p in parts]) if parts else np.zeros(0, np.uint32),
-        l_qseq=np.array([r["l_qseq"] for r in recs], np.uint32),
+        l_qseq=cat("l_qseq", np.uint32),
         de=np.concatenate([p["de"] for p in parts]) if parts else np.zeros(0, np.float32),
         hp=np.concatenate([p["hp"] for p in parts]) if parts else np.zeros(0, np.uint8),
         cigar_off=off("cigar"), cigar=cat("cigar", np.uint32),
@@ -488,7 +553,7 @@ def make_aln_batch(spec: AlnSpec, windows=None, workers: int = 0, jobs=None) -> 
     b.meta["orient"] = np.array([p["orient"] for p in parts], np.int8)
     b.meta["spec"] = spec
     if spec.het_snv_rate > 0:
-        b.meta["md"] = [r["md"] for r in recs]
+        b.meta["md"] = [m for p in parts for m in p.get("md", ())]
         b.meta["snv"] = [p["snv"] for p in parts]
     return b
 

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/${MEAS_TAG:-m2}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 500 python3 $R/bench.py > $O/bench.json 2> $O/bench.err || exit 11
+timeout -k 10 500 python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err || exit 11
 echo bench done
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/trace -o bench --output-format csv -- python3 $R/bench.py --no-cpu --no-legs --steps 50 > $O/bench_prof.json 2> $O/bench_prof.err || exit 12
 echo trace done
