@@ -288,6 +288,28 @@ int  pf_batch_k3_paths(pf_dbatch_t *db, uint8_t *out, uint64_t n);
  * (no calls, or the left-coverage check of blockjoin.c:1161).  n >= n_windows.
  * Tests assert which path the wide headline windows took. */
 int  pf_batch_k12_paths(pf_dbatch_t *db, uint8_t *out, uint64_t n);
+
+/* Masked reference positions (the masked_poss set of get_methmer_sites_and_ranges,
+ * blockjoin.c:3202-3205, 3277-3283): a position that qualifies as a
+ * methylation site by its call counts and is in the mask is no site.  Nothing
+ * else changes: the calls stay in their reads, the window's position range,
+ * the reads' first and last calls, K12's path and the left-coverage check are
+ * those of the unmasked run, so a masked run equals the unmasked run of the
+ * batch whose calls at masked positions are no-calls (call_cat 2).
+ * pos[0..n): strictly ascending 0-based positions of the batch's coordinate
+ * space (a site's position is its call_pos value, the CpG's C), each below
+ * 2^29 (PF_ERR_LIMIT).  win_rng NULL: every window sees the whole array;
+ * else [2*n_windows] with window w seeing pos[win_rng[2w], win_rng[2w+1])
+ * (begin <= end <= n, else PF_ERR_ARG).  n == 0 clears the mask.  Serves
+ * window-level and record-level batches; copies to the device and
+ * synchronises the context's stream; the mask stays in force for every later
+ * run of the batch until replaced, and a refused call leaves the previous
+ * mask in force. */
+int  pf_batch_set_mask(pf_dbatch_t *db, const uint32_t *pos, uint64_t n, const uint32_t *win_rng);
+/* out[w]: the qualifying positions the mask removed from window w in the last
+ * finished run (the reference's n_filtered); zeros with no mask.  win_n_sites
+ * counts the sites after masking.  n >= n_windows. */
+int  pf_batch_masked_sites(pf_dbatch_t *db, uint32_t *out, uint64_t n);
 /* The greedy launch this batch was given: out[0] the main kernel's dynamic
  * LDS per problem, out[1] its persistent workgroups (problems at once on the
  * device), out[2] pf_k3_heavy's dynamic LDS, out[3] its problems.  n >= 4. */
@@ -652,6 +674,26 @@ int  pf_vcf_known_vars(const char *vcf_path, const char *contig, pf_known_table_
 int  pf_vcf_known_vars_multi(const char *vcf_path, uint32_t n, const char *const *names, pf_known_table_t **out);
 void pf_known_table_free(pf_known_table_t *t);
 
+/* A host mask: per contig of `names` the sorted unique masked positions
+ * (pf_batch_set_mask), the union of
+ *   bed_path: lines `chrom start end` (tab or space separated, 0-based
+ *     half-open, plain or gzipped, read like --tsv: a trailing line without
+ *     its newline is dropped); '#' and empty lines skipped, contigs not in
+ *     `names` ignored, start >= end empty; unsorted, overlapping and
+ *     duplicate intervals allowed; a line with fewer than three columns or a
+ *     non-numeric bound is PF_ERR_ARG;
+ *   vcf_path: [pos, pos+len) of every variant of each contig's known-variant
+ *     table (pf_vcf_known_vars_multi with the same names), the set
+ *     main_methreport builds (blockjoin.c:5006-5029).
+ * Either path may be NULL.  A position >= 2^29 is PF_ERR_LIMIT; a file that
+ * cannot be read -1. */
+typedef struct pf_mask pf_mask_t;
+int  pf_mask_load(const char *bed_path, const char *vcf_path, uint32_t n_contigs, const char *const *names,
+                  pf_mask_t **out);
+/* contig c's positions (valid until pf_mask_free); *pos is NULL when *n is 0 */
+int  pf_mask_contig(const pf_mask_t *mask, uint32_t c, const uint32_t **pos, uint64_t *n);
+void pf_mask_free(pf_mask_t *mask);
+
 /* ------------------------------------------------------------------ */
 /* qname -> haplotag tables (the reference's htstri_t: st->qname2haptag,  */
 /* st->qname2haptag_raw), first entry of a qname wins.                    */
@@ -720,6 +762,14 @@ typedef struct pf_methphase_opts {
     int32_t write_input_tagging;   /* -U (with -u): {prefix}.mp.input_haptag.tsv (4494-4517)  */
     int32_t bam_threads;           /* -T / --bam-threads: --write-bam's BGZF compression threads
                                       (<= 0: `threads`, as -t sets threads_bam, cli.c:261-264)  */
+    /* masked reference positions of the window jobs (methphase and report;
+     * varhaptag ignores them): pf_mask_load(mask_path, mask_variants ?
+     * vcf_path : NULL) over the windows' contigs, each job's batch given its
+     * contig's positions (pf_batch_set_mask) */
+    const char *mask_path;         /* --mask-bed: BED of positions no site may lie on (NULL: none) */
+    int32_t mask_variants;         /* --mask-variants: also every phased variant's [pos, pos+len)
+                                      of --vcf, the set main_methreport builds and leaves unused
+                                      (blockjoin.c:5006-5029, 4250-4251); needs vcf_path         */
 } pf_methphase_opts_t;
 
 typedef struct pf_mp_plan pf_mp_plan_t;
@@ -789,6 +839,9 @@ const pf_tags_t   *pf_mp_qname_hp(const pf_mp_plan_t *p);
 const pf_tags_t   *pf_mp_raw_hp(const pf_mp_plan_t *p);     /* NULL without -u */
 /* report: {correct, switch, fail} */
 int  pf_mp_report_counts(const pf_mp_plan_t *p, double *counts3);
+/* The qualifying positions the mask removed (pf_batch_masked_sites summed over
+ * the window jobs this process ran; 0 with no mask) */
+int  pf_mp_masked_sites(const pf_mp_plan_t *p, uint64_t *total);
 /* measurement hook: wall seconds per phase of the run and the device-fetch
  * sums (pf_bam_dev_fetch_t's ms_* and byte counts) of its jobs; index 0 =
  * window jobs, 1 = -u pre-pass jobs */

@@ -59,6 +59,8 @@ def lib():
         L.pf_batch_k3_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.pf_batch_k12_paths.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.pf_batch_k3_budget.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
+        L.pf_batch_set_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.pf_batch_masked_sites.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
         L.pf_batch_debug_sites.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_uint32]
         L.pf_batch_debug_methmers.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
@@ -484,6 +486,33 @@ class DeviceBatch:
         _check(lib().pf_batch_k12_paths(self.handle, out.ctypes.data, out.size), "pf_batch_k12_paths")
         return out[:self.n_windows]
 
+    def set_mask(self, pos, win_rng=None):
+        """Masked reference positions (pf_batch_set_mask): a position that
+        qualifies as a methylation site and is in `pos` (strictly ascending,
+        0-based, below 2^29) is no site.  win_rng: [n_windows, 2] index ranges
+        into `pos`, window w seeing pos[win_rng[w, 0]:win_rng[w, 1]]; None:
+        every window sees all of it.  An empty `pos` clears the mask.  The
+        mask stays in force for later runs until replaced."""
+        pos = np.ascontiguousarray(np.asarray(pos, np.int64).ravel())
+        if pos.size and (pos.min() < 0 or pos.max() > 0xFFFFFFFF):
+            raise PomfretError("pf_batch_set_mask: positions must fit 32 bits")
+        p32 = np.ascontiguousarray(pos.astype(np.uint32))
+        rng = None
+        if win_rng is not None:
+            rng = np.ascontiguousarray(np.asarray(win_rng, np.uint32).reshape(-1))
+            if rng.size != 2 * self.n_windows:
+                raise PomfretError(f"pf_batch_set_mask: win_rng needs {self.n_windows} (begin, end) pairs")
+        _check(lib().pf_batch_set_mask(self.handle, p32.ctypes.data if p32.size else None, p32.size,
+                                       rng.ctypes.data if rng is not None and rng.size else None),
+               "pf_batch_set_mask")
+
+    def masked_sites(self) -> np.ndarray:
+        """Per window, the qualifying positions the mask removed in the last
+        finished run (pf_batch_masked_sites); zeros with no mask."""
+        out = np.zeros(max(self.n_windows, 1), np.uint32)
+        _check(lib().pf_batch_masked_sites(self.handle, out.ctypes.data, out.size), "pf_batch_masked_sites")
+        return out[:self.n_windows]
+
     def k3_paths(self) -> np.ndarray:
         """Per-(window, dir) slot-list source of the last run's greedy loop:
         [W, 2] of 1 LDS lists, 2 candidate cache, 3 HBM lists, 4 general
@@ -546,8 +575,17 @@ class DeviceBatch:
         return out
 
 
-def methphase_windows(cfg: Config, batch: WindowBatch, device: int = 0) -> WindowResult:
-    """One-shot: upload + run + free (pf_methphase_windows)."""
+def methphase_windows(cfg: Config, batch: WindowBatch, device: int = 0, mask=None) -> WindowResult:
+    """One-shot: upload + run + free (pf_methphase_windows).  mask: masked
+    reference positions for every window (DeviceBatch.set_mask)."""
+    if mask is not None:
+        ctx = Context(device)
+        try:
+            db = ctx.upload(cfg, batch)
+            db.set_mask(mask)
+            return db.run()
+        finally:
+            ctx.close()
     out = WindowResult.alloc(batch.n_windows, batch.n_reads)
     c, b, o = cfg.to_c(), batch.to_c(), out.to_c()
     _check(lib().pf_methphase_windows(int(device), C.byref(c), C.byref(b), C.byref(o)),

@@ -674,6 +674,8 @@ static int batch_build(pf_dbatch *b, const pf_window_batch_t *in, const uint32_t
     ALLOC(d.k3_fb_list, std::max<uint32_t>(4 * W, 1));       // the main kernel's deferrals, then pf_k3_heavy's
     ALLOC(d.k3_ntot, std::max<uint32_t>(2 * W, 1));
     ALLOC(d.k12_path, std::max<uint32_t>(W, 1));
+    ALLOC(d.win_masked, std::max<uint32_t>(W, 1));           // K12 writes every window's count in every run
+    if (hipMemset(d.win_masked, 0, 4ull * std::max<uint32_t>(W, 1)) != hipSuccess) return fail(PF_ERR_HIP);
     // one I/O block: the counters zeroed before a run (status, arena
     // counters, fallback counter) followed by everything copied back after it,
     // so a step costs one memset and one D2H copy
@@ -1641,6 +1643,48 @@ extern "C" int pf_batch_set_hp(pf_dbatch_t *b, const uint8_t *hp, uint32_t n) {
     HIPCHK(hipSetDevice(b->ctx->device));
     HIPCHK(hipStreamSynchronize(b->ctx->stream));
     HIPCHK(hipMemcpy(const_cast<uint8_t *>(b->ld.hp), hp, n, hipMemcpyHostToDevice));
+    return PF_OK;
+}
+
+// The masked positions K12 drops from its sites.  Checked on the host first, so
+// a refused call leaves the previous mask in force; the new arrays replace
+// the old ones only after their copies are done.
+extern "C" int pf_batch_set_mask(pf_dbatch_t *b, const uint32_t *pos, uint64_t n, const uint32_t *win_rng) {
+    if (!b || (n && !pos)) return PF_ERR_ARG;
+    for (uint64_t i = 0; i < n; i++) {                       // ascending and below 2^29: n <= 2^29
+        if (i && pos[i] <= pos[i - 1]) return PF_ERR_ARG;
+        if (pos[i] >= (1u << 29)) return PF_ERR_LIMIT;       // the call positions' bound (pos<<3 packing)
+    }
+    if (n && win_rng)
+        for (uint32_t w = 0; w < b->W; w++)
+            if (win_rng[2 * w] > win_rng[2 * w + 1] || win_rng[2 * w + 1] > n) return PF_ERR_ARG;
+    HIPCHK(hipSetDevice(b->ctx->device));
+    HIPCHK(hipStreamSynchronize(b->ctx->stream));
+    uint32_t *np = nullptr, *nr = nullptr;
+    int rc = PF_OK;
+    if (n) {
+        rc = dev_put(b, &np, pos, (size_t)n);
+        if (!rc && win_rng && b->W) rc = dev_put(b, &nr, win_rng, 2ull * b->W);
+        if (rc) {
+            if (np) free_arena(b, np);
+            if (nr) free_arena(b, nr);
+            return rc;
+        }
+    }
+    pf_dev_batch &d = b->d;
+    if (d.mask_pos) free_arena(b, const_cast<uint32_t *>(d.mask_pos));
+    if (d.win_mask_rng) free_arena(b, const_cast<uint32_t *>(d.win_mask_rng));
+    d.mask_pos = np;
+    d.win_mask_rng = nr;
+    d.mask_n = (uint32_t)n;
+    return PF_OK;
+}
+
+extern "C" int pf_batch_masked_sites(pf_dbatch_t *b, uint32_t *out, uint64_t n) {
+    if (!b || !out || n < b->W) return PF_ERR_ARG;
+    HIPCHK(hipSetDevice(b->ctx->device));
+    HIPCHK(hipStreamSynchronize(b->ctx->stream));
+    if (b->W) HIPCHK(hipMemcpy(out, b->d.win_masked, 4ull * b->W, hipMemcpyDeviceToHost));
     return PF_OK;
 }
 

@@ -13,8 +13,10 @@
  * order-dependent -n override and varhaptag's --write-bam (which there turns
  * the BAM output OFF, cli.c:416) are kept.  Added: --gpus G (GPUs driven by
  * this process; default all visible), --host-fetch (records inflated and
- * decoded on the host instead of the device fetch) and --job-windows W (windows per device
- * job).  Phase blocks come from --tsv, else --gtf, else --vcf (main_blockjoin
+ * decoded on the host instead of the device fetch), --job-windows W (windows per device
+ * job), and --mask-bed FILE / --mask-variants (reference positions no
+ * methylation site may lie on: a BED's intervals, the phased variants of
+ * --vcf; methphase and report).  Phase blocks come from --tsv, else --gtf, else --vcf (main_blockjoin
  * 4661-4666); with -u the VCF still supplies the variants and the contigs to
  * pre-haplotag.  -U writes {prefix}.mp.input_haptag.tsv (4494-4517).  --dbg's
  * {prefix}.mp.dbg.read2tag (2223-2248) lists a khash in bucket order, which
@@ -68,10 +70,14 @@ static void help_methphase(const char *prefix) {
     fprintf(stderr, "  -T,--bam-threads [opt] Compression threads of the output BAM. [-t]\n");
     fprintf(stderr, "  --gpus [opt] GPUs to use. [all visible]\n");
     fprintf(stderr, "  --host-fetch [opt] Inflate and decode BAM records (and the coverage pass) on the host instead of the GPU.\n");
+    fprintf(stderr, "  --mask-bed FILE [opt] BED (chrom, start, end; 0-based half-open; plain or gz'd) of reference\n"
+                    "               positions that are never used as methylation sites (methphase, report).\n");
+    fprintf(stderr, "  --mask-variants [opt] Also mask every phased variant of --vcf (its position and length):\n"
+                    "               a CpG a heterozygous variant creates or destroys is no site.\n");
 }
 
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
-       O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH };
+       O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -84,12 +90,14 @@ static const struct option longopts[] = {
     {"help", no_argument, 0, O_HELP},            {"dbg", no_argument, 0, O_DBG},
     {"gpus", required_argument, 0, O_GPUS},      {"job-windows", required_argument, 0, O_JOBW},
     {"host-fetch", no_argument, 0, O_HFETCH},
+    {"mask-bed", required_argument, 0, O_MBED},  {"mask-variants", no_argument, 0, O_MVAR},
     {0, 0, 0, 0}};
 
 typedef struct {
     int help, threads, lo, hi, readlen, mapq, k, k_span, cov, cov_sel, n_cand, untagged, out_tsv, out_bam;
     int chunk_size, chunk_stride, gpus, job_windows, verbose, host_fetch, write_input_tagging, dbg, bam_threads;
-    char *prefix, *vcf, *gtf, *tsv, *bam;
+    int mask_variants;
+    char *prefix, *vcf, *gtf, *tsv, *bam, *mask_bed;
 } cli_t;
 
 static int parse(int argc, char **argv, cli_t *c) {
@@ -127,6 +135,8 @@ static int parse(int argc, char **argv, cli_t *c) {
         case O_GPUS: c->gpus = atoi(optarg); break;
         case O_JOBW: c->job_windows = atoi(optarg); break;
         case O_HFETCH: c->host_fetch = 1; break;
+        case O_MBED: c->mask_bed = optarg; break;
+        case O_MVAR: c->mask_variants = 1; break;
         default:
             fprintf(stderr, "[E::parse_cli] unknown or incomplete option \"%s\"\n", argv[optind - 1]);
             return 1;
@@ -155,6 +165,15 @@ static int sancheck(cli_t *c) {                       /* sancheck_cliopt, cli.c:
     if (c->untagged && !c->vcf) {
         fprintf(stderr, "[E::sancheck_cliopt] input bam was flagged unhaplotagged, but vcf is missing.\n");
         return 1;
+    }
+    if (c->mask_variants && !c->vcf) {
+        fprintf(stderr, "[E::sancheck_cliopt] --mask-variants needs the phased variants of --vcf.\n");
+        return 1;
+    }
+    if (c->mask_bed) {
+        FILE *fp = fopen(c->mask_bed, "rb");
+        if (!fp) { fprintf(stderr, "[E::sancheck_cliopt] cannot read --mask-bed %s\n", c->mask_bed); return 1; }
+        fclose(fp);
     }
     if (!c->bam) { fprintf(stderr, "[E::sancheck_cliopt] missing bam file\n"); return 1; }
     size_t l = c->prefix ? strlen(c->prefix) : 0;
@@ -275,6 +294,8 @@ int main(int argc, char **argv) {
         o.interval_format = c.tsv ? PF_INTERVALS_TSV : PF_INTERVALS_GTF;
     }
     o.write_input_tagging = c.write_input_tagging;
+    o.mask_path = c.mask_bed;
+    o.mask_variants = c.mask_variants;
     pf_mp_plan_t *p = NULL;
     const int rc = pf_methphase_main(&o, &p);
     if (rc) {

@@ -107,6 +107,13 @@ struct pf_dev_batch {
     uint8_t *k12_path;                 /* [W] K12's sites path of the last run: 1 / 2 the fast path over 1 / 2
                                           segments, 3 the dense path, 0 none (no calls, left coverage) */
     uint32_t *k3_ntot;                 /* [2W] slots of each problem (kdict) */
+    /* masked reference positions (pf_batch_set_mask): a position that qualifies
+     * as a site by its counts and is in the mask is no site (blockjoin.c:3202-3205,
+     * 3277-3283); K12 alone reads them */
+    const uint32_t *mask_pos;          /* [mask_n] ascending, unique */
+    const uint32_t *win_mask_rng;      /* [2W] window w sees mask_pos[rng[2w], rng[2w+1]); NULL: all of it */
+    uint32_t *win_masked;              /* [W] qualifying positions the mask removed (the reference's n_filtered) */
+    uint32_t mask_n;                   /* 0: no mask */
 };
 
 #endif

@@ -739,6 +739,16 @@ DEV void k12_methmers(const pf_dev_batch &d, uint32_t r0, uint32_t i0, uint32_t 
 // K12: sites + directional methmer ranges + end-order + arena reservation,
 // then every read's methmers (both directions) from LDS-resident site arrays
 // ========================================================================
+// first index in [lo, hi) of the ascending p whose value is >= x (hi: none)
+__device__ __forceinline__ uint32_t mask_lower(const uint32_t *p, uint32_t lo, uint32_t hi, uint32_t x) {
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo) >> 1);
+        if (p[mid] < x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
 __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_batch d) {
     __shared__ uint32_t tile[PF_K1_TILE];
     __shared__ uint32_t sh_scan[PF_K1_THREADS / 64 + 1];
@@ -778,7 +788,7 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
     const bool fail = R == 0 || (int)sh_misc[0] < d.hard_cov || (int)sh_misc[1] < d.hard_cov ||
                       sh_misc[2] > sh_misc[3];
     if (fail) {
-        if (tid == 0) { d.win_S[w] = 0; d.win_nreads[w] = 0; }
+        if (tid == 0) { d.win_S[w] = 0; d.win_nreads[w] = 0; d.win_masked[w] = 0; }
         for (uint32_t i = tid; i < R; i += NT) {
             const uint32_t r = r0 + i;
             d.mmr_n[2 * r] = 0; d.mmr_n[2 * r + 1] = 0;
@@ -791,6 +801,17 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
     }
     K12_STAMP(1);
     const uint32_t pmin = sh_misc[2], pmax = sh_misc[3];
+    // masked positions (pf_batch_set_mask): the window's slice of the mask cut
+    // to its position range, mask_pos[mk0, mk1); empty without a mask.  A
+    // position that qualifies by its counts and is masked is no site
+    // (blockjoin.c:3277-3283); the removed ones are counted in sh_misc[6].
+    uint32_t mk0 = 0, mk1 = 0;
+    if (d.mask_n != 0) {
+        const uint32_t a = d.win_mask_rng ? d.win_mask_rng[2 * w] : 0u;
+        const uint32_t b = d.win_mask_rng ? d.win_mask_rng[2 * w + 1] : d.mask_n;
+        mk0 = mask_lower(d.mask_pos, a, b, pmin);
+        mk1 = mask_lower(d.mask_pos, mk0, b, pmax + 1);      // positions are below 2^29
+    }
     if (tid == 0) { sh_misc[4] = 0; d.win_nreads[w] = R; }
     __syncthreads();
 
@@ -909,6 +930,26 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
                 mycount += (uint32_t)__popcll(q);
             }
         }
+        if (mk1 > mk0) {
+            // the segment's masked positions leave the qualifying bitmap; a
+            // bit that was set is a removed site (block-uniform branches)
+            const uint32_t m0 = mask_lower(d.mask_pos, mk0, mk1, base);
+            const uint32_t m1 = mask_lower(d.mask_pos, m0, mk1, base + SEGB);
+            if (m1 > m0) {
+                __syncthreads();
+                uint32_t gone = 0;
+                for (uint32_t j = m0 + tid; j < m1; j += NT) {
+                    const uint32_t o = d.mask_pos[j] - base;
+                    const unsigned long long bit = 1ull << (o & 63);
+                    if (atomicAnd((unsigned long long *)&bmap[o >> 6], ~bit) & bit) gone++;
+                }
+                if (gone) atomicAdd(&sh_misc[6], gone);
+                __syncthreads();
+                mycount = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < PW; j++) mycount += (uint32_t)__popcll(bmap[tid * PW + j]);
+            }
+        }
         // the segment's sites, ranked after the earlier segments'
         uint32_t total;
         const uint32_t excl = block_excl_scan<NT>(mycount, sh_scan, &total);
@@ -933,8 +974,8 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
     }
     if (range_ok && !fast) {
         // a segment had too many repeated positions: the dense path restarts
-        // the window's sites from rank 0
-        if (tid == 0) sh_misc[4] = 0;
+        // the window's sites from rank 0 (and its removed count)
+        if (tid == 0) { sh_misc[4] = 0; sh_misc[6] = 0; }
         __syncthreads();
     }
     // ---- general path (a position range beyond the bitmaps, or more repeated
@@ -1062,6 +1103,25 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
                             if (v4[u] != 0xFFFFFFFFu) atomicAdd(&ccnt[v4[u] & (CH - 1)], (v4[u] >> 15) ? 0x10000u : 1u);
                     }
                     __syncthreads();
+                    if (mk1 > mk0) {
+                        // the chunk's masked positions: a counter that qualifies is a
+                        // removed site; zeroed, it cannot qualify below (the positions
+                        // are unique: one thread per counter)
+                        const uint32_t cb = pmin + (uint32_t)sup + (ch << CHB);
+                        const uint32_t m0 = mask_lower(d.mask_pos, mk0, mk1, cb);
+                        const uint32_t m1 = mask_lower(d.mask_pos, m0, mk1, cb + CH);
+                        if (m1 > m0) {
+                            uint32_t gone = 0;
+                            for (uint32_t j = m0 + tid; j < m1; j += NT) {
+                                const uint32_t o = d.mask_pos[j] - cb;
+                                const uint32_t v = ccnt[o];
+                                if ((int)(v & 4095u) >= cov && (int)((v >> 16) & 4095u) >= cov) gone++;
+                                ccnt[o] = 0;
+                            }
+                            if (gone) atomicAdd(&sh_misc[6], gone);
+                            __syncthreads();
+                        }
+                    }
                     uint32_t qmask = 0;
                     constexpr uint32_t PER = CH / NT;        // 16 positions per thread
 #pragma unroll
@@ -1106,6 +1166,7 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
     if (tid == 0) {
         d.win_S[w] = S;
         d.k12_path[w] = fast ? (uint8_t)nseg : (uint8_t)3;
+        d.win_masked[w] = sh_misc[6];
     }
 
     // ---- revbuf order: reads ascending by (end<<32 | idx) (blockjoin.c:1126, 1140)

@@ -258,6 +258,11 @@ struct pf_mp_plan {
     int est_deferred;
     int32_t *ucov, *utrunc;
     uint8_t *uhave;
+    /* masked reference positions of the window jobs (mask_path, mask_variants) */
+    char *mask_path;
+    pf_mask_t *mask;           /* per window contig; NULL: no mask */
+    uint64_t mask_loaded;      /* its positions */
+    uint64_t masked_sites;     /* qualifying positions it removed, over the jobs run here (st_mu) */
 };
 
 static double now_s(void) {
@@ -324,6 +329,8 @@ void pf_mp_free(pf_mp_plan_t *p) {
     free(p->utid); free(p->bnd_off); free(p->bnd); free(p->bext);
     free(p->bam_path); free(p->vcf_path); free(p->out_prefix); free(p->interval_path);
     free(p->ucov); free(p->utrunc); free(p->uhave);
+    pf_mask_free(p->mask);
+    free(p->mask_path);
     pthread_mutex_destroy(&p->st_mu);
     free(p);
 }
@@ -395,6 +402,7 @@ static int mp_plan(const pf_methphase_opts_t *o, pf_mp_plan_t **out, int defer_e
     if ((o->untagged || o->mode == PF_MODE_REPORT) && !o->vcf_path) return PF_ERR_ARG;
     if (o->mode == PF_MODE_REPORT && ifmt != PF_INTERVALS_VCF) return PF_ERR_ARG;
     if (o->mode == PF_MODE_REPORT && (o->chunk_size <= 0 || o->chunk_stride <= 0)) return PF_ERR_ARG;
+    if (o->mask_variants && !o->vcf_path) return PF_ERR_ARG;
     *out = NULL;
     const double t_plan0 = now_s();
     pf_mp_plan_t *p = (pf_mp_plan_t *)calloc(1, sizeof *p);
@@ -409,6 +417,8 @@ static int mp_plan(const pf_methphase_opts_t *o, pf_mp_plan_t **out, int defer_e
     p->o.vcf_path = p->vcf_path;
     p->o.out_prefix = p->out_prefix;
     p->o.interval_path = p->interval_path;
+    p->mask_path = dupstr(o->mask_path);
+    p->o.mask_path = p->mask_path;
     p->o.ctxs = NULL;
     p->o.n_ctxs = 0;
     /* -u: the VCF's contigs are pre-haplotagged (load_intervals_from_file with
@@ -422,6 +432,24 @@ static int mp_plan(const pf_methphase_opts_t *o, pf_mp_plan_t **out, int defer_e
     const pf_gaps_t *g = p->gaps;
     const uint32_t C = g->n_contigs;
     p->n_contigs = C;
+    /* the mask of the windows' contigs, before anything touches the BAM or a
+     * device; every rank of a multi-process run builds the same one */
+    if (o->mask_path || o->mask_variants) {
+        rc = pf_mask_load(o->mask_path, o->mask_variants ? o->vcf_path : NULL, C, (const char *const *)g->names,
+                          &p->mask);
+        if (rc) {
+            fprintf(stderr, "[E::pomfret_amd] cannot load the mask (%s%s)\n", o->mask_path ? o->mask_path : "",
+                    o->mask_variants ? o->mask_path ? " + variants" : "variants" : "");
+            pf_mp_free(p);
+            return rc;
+        }
+        for (uint32_t c = 0; c < C; c++) {
+            const uint32_t *mp;
+            uint64_t mn = 0;
+            pf_mask_contig(p->mask, c, &mp, &mn);
+            p->mask_loaded += mn;
+        }
+    }
     p->tid = (int32_t *)calloc(C ? C : 1, sizeof(int32_t));
     p->cfg = (pf_cfg_t *)calloc(C ? C : 1, sizeof(pf_cfg_t));
     p->win_off = (uint64_t *)calloc(C + 1, sizeof(uint64_t));
@@ -947,8 +975,37 @@ static int job_fetch(const pf_mp_plan_t *p, pf_bam_t *bam, const job_t *J, fetch
     return f->rc;
 }
 
+/* the job's contig's masked positions onto its batch, whole: the reads of a
+ * job overhang its windows by their own lengths, and every window's K12
+ * cuts the array to its own position range */
+static int job_set_mask(const pf_mp_plan_t *p, const job_t *J, pf_dbatch_t *db) {
+    if (!p->mask) return PF_OK;
+    const uint32_t *mp = NULL;
+    uint64_t mn = 0;
+    int rc = pf_mask_contig(p->mask, J->contig, &mp, &mn);
+    if (!rc && mn) rc = pf_batch_set_mask(db, mp, mn, NULL);
+    return rc;
+}
+
+/* after a finished run: the sites the mask removed, added to the plan's total */
+static int job_count_masked(pf_mp_plan_t *p, pf_dbatch_t *db, uint32_t W) {
+    if (!p->mask || !W) return PF_OK;
+    uint32_t *m = (uint32_t *)malloc(W * sizeof(uint32_t));
+    if (!m) return PF_ERR_NOMEM;
+    const int rc = pf_batch_masked_sites(db, m, W);
+    uint64_t t = 0;
+    for (uint32_t w = 0; w < W && !rc; w++) t += m[w];
+    free(m);
+    if (!rc) {
+        pthread_mutex_lock(&p->st_mu);
+        p->masked_sites += t;
+        pthread_mutex_unlock(&p->st_mu);
+    }
+    return rc;
+}
+
 /* upload + run a sub-batch of windows [a, b) of the fetched records */
-static int run_windows(const pf_mp_plan_t *p, pf_ctx_t *ctx, const job_t *J, const pf_bam_records_t *R,
+static int run_windows(pf_mp_plan_t *p, pf_ctx_t *ctx, const job_t *J, const pf_bam_records_t *R,
                        const uint32_t *sel, uint32_t n_sel, int8_t *dec, entlist_t *ent, uint64_t *win_ent) {
     const pf_aln_batch_t *A = &R->aln;
     const pf_cfg_t *cf = &p->cfg[J->contig];
@@ -975,6 +1032,7 @@ static int run_windows(const pf_mp_plan_t *p, pf_ctx_t *ctx, const job_t *J, con
     }
     pf_dbatch_t *db = NULL;
     int rc = pf_batch_upload_aln(ctx, cf, &lc, &a, &db);
+    if (!rc) rc = job_set_mask(p, J, db);
     /* the kept reads are known after a run (K0 sizes the batch on the
      * device); the records bound them */
     const uint32_t W = a.n_windows, cap = a.n_recs ? a.n_recs : 1;
@@ -995,6 +1053,7 @@ static int run_windows(const pf_mp_plan_t *p, pf_ctx_t *ctx, const job_t *J, con
         o.read_hp = rhp;
         rc = pf_methphase_run(ctx, db, &o);
     }
+    if (!rc) rc = job_count_masked(p, db, W);
     if (!rc) {
         R_ = pf_batch_n_reads(db);
         if (R_ > cap) rc = PF_ERR_INTERNAL;
@@ -1130,6 +1189,7 @@ static int job_device_fetch(pf_mp_plan_t *p, pf_ctx_t *ctx, pf_bam_t *bam, job_t
             n_limit++;
         }
     }
+    if (!rc) rc = job_set_mask(p, J, db);
     if (!rc && p->o.untagged && NR) {           /* the -u table replaces HP (1114-1122) */
         hp = (uint8_t *)malloc(NR);
         if (!hp) rc = PF_ERR_NOMEM;
@@ -1148,6 +1208,7 @@ static int job_device_fetch(pf_mp_plan_t *p, pf_ctx_t *ctx, pf_bam_t *bam, job_t
         rc = pf_methphase_run(ctx, db, &o);
         st_fetch(p, 0, NULL, (now_s() - t0) * 1e3);
     }
+    if (!rc) rc = job_count_masked(p, db, n);
     uint32_t R_ = 0;
     if (!rc) {
         R_ = pf_batch_n_reads(db);
@@ -1435,6 +1496,9 @@ int pf_mp_finish(pf_mp_plan_t *p) {
     }
     free(by_w0);
     if (rc) return rc;
+    if (p->mask)
+        mp_log(p, "[M::pf_mp_finish] mask%s: %ld positions loaded, %ld sites removed", "", (long)p->mask_loaded,
+               (long)p->masked_sites);
     if (p->o.mode == PF_MODE_REPORT) {
         if (p->out_prefix) rc = write_report(p);
     } else {
@@ -1444,6 +1508,14 @@ int pf_mp_finish(pf_mp_plan_t *p) {
     if (!rc) p->finished = 1;
     p->st.s_finish += now_s() - t0;
     return rc;
+}
+
+int pf_mp_masked_sites(const pf_mp_plan_t *p, uint64_t *total) {
+    if (!p || !total) return PF_ERR_ARG;
+    pthread_mutex_lock((pthread_mutex_t *)&p->st_mu);
+    *total = p->masked_sites;
+    pthread_mutex_unlock((pthread_mutex_t *)&p->st_mu);
+    return PF_OK;
 }
 
 int pf_mp_report_counts(const pf_mp_plan_t *p, double *counts3) {
@@ -1780,6 +1852,8 @@ static int methphase_main_(const pf_methphase_opts_t *o, pf_mp_plan_t **out) {
         v.mode = PF_MODE_METHPHASE;
         v.untagged = 1;
         v.cov_for_selection = 1;                   /* no coverage estimate: no window runs */
+        v.mask_path = NULL;                        /* and no sites: the mask has no use */
+        v.mask_variants = 0;
         pf_mp_plan_t *p = NULL;
         int rc = pf_mp_plan(&v, &p);
         if (!rc) rc = run_on_devices(p, &v, PF_JOB_HAPTAG);

@@ -621,3 +621,150 @@ int pf_vcf_known_vars(const char *vcf_path, const char *contig, pf_known_table_t
     *out = &o->pub;
     return PF_OK;
 }
+
+/* ------------------------------------------------------------------ */
+/* Masked reference positions (pf_batch_set_mask): per contig the sorted
+ * unique positions of a BED's intervals and / or of the phased variants'
+ * [pos, pos+len), the masked_poss sets of main_methreport (:5006-5029).
+ * Intervals are collected as (start, end) pairs per contig, sorted, merged
+ * and expanded. */
+
+struct pf_mask {
+    uint32_t n_contigs;
+    uint64_t *off;          /* [n_contigs+1] */
+    uint32_t *pos;
+};
+
+#define PF_MASK_POS_LIMIT (1u << 29)   /* the call positions' bound */
+
+typedef struct {
+    uint32_t n;
+    const char *const *names;
+    u32v *iv;               /* [n] start, end, start, end, ... */
+} mask_acc_t;
+
+static int mask_add(mask_acc_t *M, uint32_t c, uint64_t s, uint64_t e) {
+    if (e <= s) return 0;
+    if (e > PF_MASK_POS_LIMIT) return PF_ERR_LIMIT;
+    if (u32v_push(&M->iv[c], (uint32_t)s) || u32v_push(&M->iv[c], (uint32_t)e)) return PF_ERR_NOMEM;
+    return 0;
+}
+
+/* a column's decimal digits; -1 when it is empty or holds anything else */
+static int mask_num(const char *s, size_t l, uint64_t *v) {
+    if (l == 0 || l > 18) return -1;
+    uint64_t x = 0;
+    for (size_t i = 0; i < l; i++) {
+        if (s[i] < '0' || s[i] > '9') return -1;
+        x = x * 10 + (uint64_t)(s[i] - '0');
+    }
+    *v = x;
+    return 0;
+}
+
+static int mask_bed_line(void *arg, const char *s, size_t l) {
+    mask_acc_t *M = (mask_acc_t *)arg;
+    if (l > 0 && s[l - 1] == '\r') l--;
+    if (l == 0 || s[0] == '#') return 0;
+    const char *tok[3];
+    size_t tl[3];
+    int nt = 0;
+    for (size_t i = 0; i < l && nt < 3;) {
+        while (i < l && (s[i] == '\t' || s[i] == ' ')) i++;
+        if (i >= l) break;
+        tok[nt] = s + i;
+        const size_t st = i;
+        while (i < l && s[i] != '\t' && s[i] != ' ') i++;
+        tl[nt++] = i - st;
+    }
+    if (nt == 0) return 0;
+    if (nt < 3) return PF_ERR_ARG;
+    uint64_t a, b;
+    if (mask_num(tok[1], tl[1], &a) || mask_num(tok[2], tl[2], &b)) return PF_ERR_ARG;
+    for (uint32_t c = 0; c < M->n; c++)
+        if (strlen(M->names[c]) == tl[0] && memcmp(M->names[c], tok[0], tl[0]) == 0) return mask_add(M, c, a, b);
+    return 0;                                             /* a contig the run does not have */
+}
+
+static int cmp_iv(const void *a, const void *b) {
+    const uint32_t *x = (const uint32_t *)a, *y = (const uint32_t *)b;
+    if (x[0] != y[0]) return x[0] < y[0] ? -1 : 1;
+    return x[1] < y[1] ? -1 : x[1] > y[1];
+}
+
+void pf_mask_free(pf_mask_t *m) {
+    if (!m) return;
+    free(m->off);
+    free(m->pos);
+    free(m);
+}
+
+int pf_mask_load(const char *bed_path, const char *vcf_path, uint32_t n_contigs, const char *const *names,
+                 pf_mask_t **out) {
+    if (!out || (n_contigs && !names)) return PF_ERR_ARG;
+    *out = NULL;
+    for (uint32_t c = 0; c < n_contigs; c++) if (!names[c]) return PF_ERR_ARG;
+    mask_acc_t M = {n_contigs, names, (u32v *)calloc(n_contigs ? n_contigs : 1, sizeof(u32v))};
+    pf_mask_t *m = (pf_mask_t *)calloc(1, sizeof *m);
+    int rc = M.iv && m ? PF_OK : PF_ERR_NOMEM;
+    if (!rc && bed_path) rc = each_line(bed_path, mask_bed_line, &M);
+    if (!rc && vcf_path && n_contigs) {
+        pf_known_table_t **kt = (pf_known_table_t **)calloc(n_contigs, sizeof *kt);
+        rc = kt ? pf_vcf_known_vars_multi(vcf_path, n_contigs, names, kt) : PF_ERR_NOMEM;
+        for (uint32_t c = 0; c < n_contigs && !rc; c++) {
+            const pf_known_vars_t *v = &kt[c]->vars;
+            for (uint32_t i = 0; i < v->n && !rc; i++)
+                rc = mask_add(&M, c, v->pos[i], (uint64_t)v->pos[i] + v->len[i]);
+        }
+        if (kt)
+            for (uint32_t c = 0; c < n_contigs; c++) if (kt[c]) pf_known_table_free(kt[c]);
+        free(kt);
+    }
+    if (!rc) {
+        m->n_contigs = n_contigs;
+        m->off = (uint64_t *)calloc((size_t)n_contigs + 1, sizeof(uint64_t));
+        if (!m->off) rc = PF_ERR_NOMEM;
+    }
+    /* sort and merge each contig's intervals in place, then expand */
+    for (uint32_t c = 0; c < n_contigs && !rc; c++) {
+        u32v *v = &M.iv[c];
+        const size_t ni = v->n / 2;
+        if (ni) qsort(v->a, ni, 2 * sizeof(uint32_t), cmp_iv);
+        size_t k = 0;
+        uint64_t tot = 0;
+        for (size_t i = 0; i < ni; i++) {
+            if (k && v->a[2 * i] <= v->a[2 * k - 1]) {
+                if (v->a[2 * i + 1] > v->a[2 * k - 1]) { tot += v->a[2 * i + 1] - v->a[2 * k - 1]; v->a[2 * k - 1] = v->a[2 * i + 1]; }
+            } else {
+                v->a[2 * k] = v->a[2 * i]; v->a[2 * k + 1] = v->a[2 * i + 1];
+                tot += v->a[2 * k + 1] - v->a[2 * k];
+                k++;
+            }
+        }
+        v->n = 2 * k;
+        m->off[c + 1] = m->off[c] + tot;
+    }
+    if (!rc) {
+        const uint64_t tot = m->off[n_contigs];
+        m->pos = (uint32_t *)malloc((tot ? tot : 1) * sizeof(uint32_t));
+        if (!m->pos) rc = PF_ERR_NOMEM;
+        for (uint32_t c = 0; c < n_contigs && !rc; c++) {
+            uint32_t *p = m->pos + m->off[c];
+            for (size_t i = 0; i < M.iv[c].n / 2; i++)
+                for (uint32_t x = M.iv[c].a[2 * i]; x < M.iv[c].a[2 * i + 1]; x++) *p++ = x;
+        }
+    }
+    if (M.iv)
+        for (uint32_t c = 0; c < n_contigs; c++) free(M.iv[c].a);
+    free(M.iv);
+    if (rc) { pf_mask_free(m); return rc; }
+    *out = m;
+    return PF_OK;
+}
+
+int pf_mask_contig(const pf_mask_t *m, uint32_t c, const uint32_t **pos, uint64_t *n) {
+    if (!m || !pos || !n || c >= m->n_contigs) return PF_ERR_ARG;
+    *n = m->off[c + 1] - m->off[c];
+    *pos = *n ? m->pos + m->off[c] : NULL;
+    return PF_OK;
+}

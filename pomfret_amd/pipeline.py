@@ -48,7 +48,8 @@ class PfMethphaseOpts(C.Structure):
                 ("n_devices", C.c_int32), ("devices", C.c_void_p), ("ctxs", C.c_void_p), ("n_ctxs", C.c_int32),
                 ("rank", C.c_int32), ("world", C.c_int32), ("job_windows", C.c_uint32), ("verbose", C.c_int32),
                 ("host_fetch", C.c_int32), ("interval_path", C.c_char_p), ("interval_format", C.c_int32),
-                ("write_input_tagging", C.c_int32), ("bam_threads", C.c_int32)]
+                ("write_input_tagging", C.c_int32), ("bam_threads", C.c_int32),
+                ("mask_path", C.c_char_p), ("mask_variants", C.c_int32)]
 
 
 class PfQnameTagsC(C.Structure):
@@ -108,6 +109,10 @@ def _bind():
     L.pf_mp_raw_hp.restype = vp
     L.pf_mp_report_counts.argtypes = [vp, C.POINTER(C.c_double)]
     L.pf_mp_stats.argtypes = [vp, C.POINTER(PfMpStats)]
+    L.pf_mp_masked_sites.argtypes = [vp, C.POINTER(C.c_uint64)]
+    L.pf_mask_load.argtypes = [C.c_char_p, C.c_char_p, u32, C.POINTER(C.c_char_p), C.POINTER(vp)]
+    L.pf_mask_contig.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_uint64)]
+    L.pf_mask_free.argtypes = [vp]
     L.pf_tags_new.restype = vp
     L.pf_tags_free.argtypes = [vp]
     L.pf_tags_size.argtypes = [vp]
@@ -201,11 +206,14 @@ def make_opts(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg: Opti
               lcfg: Optional[LoadConfig] = None, mode: int = MODE_METHPHASE, untagged: bool = False,
               tsv: bool = False, threads: int = 8, n_devices: int = 0, ctxs=None, rank: int = 0, world: int = 1,
               job_windows: int = 0, cov: int = 0, chunk_size: int = 50_000, chunk_stride: int = 1_000_000,
-              verbose: int = 0, host_fetch: bool = False, intervals=None, write_input_tagging: bool = False):
+              verbose: int = 0, host_fetch: bool = False, intervals=None, write_input_tagging: bool = False,
+              mask_bed: Optional[str] = None, mask_variants: bool = False):
     """pf_methphase_opts_t from Python values.  cfg None: per-contig
     parameters from the BAM's coverage estimate (runs without -c).
     intervals: (path, INTERVALS_GTF | INTERVALS_TSV), the --gtf / --tsv phase
-    blocks (vcf_path may then be None unless untagged)."""
+    blocks (vcf_path may then be None unless untagged).  mask_bed /
+    mask_variants: --mask-bed / --mask-variants, reference positions no
+    methylation site may lie on (load_mask)."""
     lcfg = lcfg or LoadConfig()
     o = PfMethphaseOpts()
     o.mode = mode
@@ -237,6 +245,8 @@ def make_opts(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg: Opti
     o.job_windows = int(job_windows)
     o.verbose = int(verbose)
     o.host_fetch = int(bool(host_fetch))
+    o.mask_path = mask_bed.encode() if mask_bed else None
+    o.mask_variants = int(bool(mask_variants))
     o._keep = keep
     return o
 
@@ -327,6 +337,13 @@ class Plan:
         _check(lib().pf_mp_report_counts(self.h, c), "pf_mp_report_counts")
         return dict(correct=int(c[0]), switch=int(c[1]), fail=int(c[2]))
 
+    def masked_sites(self) -> int:
+        """Qualifying positions the mask removed, over the window jobs this
+        process ran (pf_mp_masked_sites); 0 with no mask."""
+        t = C.c_uint64()
+        _check(lib().pf_mp_masked_sites(self.h, C.byref(t)), "pf_mp_masked_sites")
+        return int(t.value)
+
     def stats(self) -> Dict:
         """Wall seconds per phase and the device-fetch sums of the run
         (pf_mp_stats; a measurement hook)."""
@@ -356,16 +373,40 @@ class Plan:
 def _result(plan: Plan, mode: int) -> Dict:
     dec = plan.decisions()
     if mode == MODE_REPORT:
-        return dict(decision=dec, counts=plan.report_counts(), n_limit=plan.n_limit)
+        return dict(decision=dec, counts=plan.report_counts(), n_limit=plan.n_limit,
+                    masked_sites=plan.masked_sites())
     return dict(decision=dec, contigs=plan.contigs(), qname_hp=plan.qname_hp(), raw_hp=plan.raw_hp(),
-                n_limit=plan.n_limit, stats=plan.stats())
+                n_limit=plan.n_limit, stats=plan.stats(), masked_sites=plan.masked_sites())
+
+
+def load_mask(names: List[str], bed_path: Optional[str] = None, vcf_path: Optional[str] = None) -> List[np.ndarray]:
+    """Masked reference positions per contig of `names` (pf_mask_load): the
+    sorted unique union of the BED's intervals (chrom, start, end; 0-based
+    half-open; plain or gzipped) and of [pos, pos+len) of every phased variant
+    of the VCF.  Returns one uint32 array per contig, as DeviceBatch.set_mask
+    takes them."""
+    L = _bind()
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    h = C.c_void_p()
+    _check(L.pf_mask_load(bed_path.encode() if bed_path else None, vcf_path.encode() if vcf_path else None,
+                          len(names), arr, C.byref(h)), "pf_mask_load")
+    try:
+        out = []
+        for c in range(len(names)):
+            p, n = C.c_void_p(), C.c_uint64()
+            _check(L.pf_mask_contig(h, c, C.byref(p), C.byref(n)), "pf_mask_contig")
+            out.append(_arr(p, n.value, np.uint32))
+        return out
+    finally:
+        L.pf_mask_free(h)
 
 
 def methphase_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg: Optional[Config],
                     lcfg: Optional[LoadConfig] = None, device: int = 0, threads: int = 8, ctx=None,
                     untagged: bool = False, tsv: bool = False, n_devices: int = 1, job_windows: int = 0,
                     host_fetch: bool = False, ctxs=None, intervals=None,
-                    write_input_tagging: bool = False) -> Dict:
+                    write_input_tagging: bool = False, mask_bed: Optional[str] = None,
+                    mask_variants: bool = False) -> Dict:
     """`pomfret methphase` over every gap of vcf_path with the reads of
     bam_path, in this process (pf_methphase_main).  Writes out_prefix +
     .mp.gtf / .mp.vcf (and .mp.tsv with tsv=True, the reference's
@@ -377,7 +418,9 @@ def methphase_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg
     Returns dict(decision=int8[n_gaps], contigs=[...], qname_hp={qname: hp},
     raw_hp={qname: hp} (the -u table), n_limit).  intervals=(path,
     INTERVALS_GTF | INTERVALS_TSV): the --gtf / --tsv phase blocks instead of
-    the VCF's (vcf_path None: no VCF written); write_input_tagging: -U."""
+    the VCF's (vcf_path None: no VCF written); write_input_tagging: -U.
+    mask_bed / mask_variants: --mask-bed / --mask-variants; the result's
+    masked_sites counts the sites they removed."""
     L = _bind()
     devs = None
     if ctx is not None:
@@ -387,7 +430,7 @@ def methphase_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg
     o = make_opts(bam_path, vcf_path, out_prefix, cfg, lcfg, untagged=untagged, tsv=tsv, threads=threads,
                   n_devices=0 if ctxs else n_devices, ctxs=ctxs or None,
                   job_windows=job_windows, host_fetch=host_fetch, intervals=intervals,
-                  write_input_tagging=write_input_tagging)
+                  write_input_tagging=write_input_tagging, mask_bed=mask_bed, mask_variants=mask_variants)
     if devs is not None:
         o.devices = C.cast(devs, C.c_void_p)
     h = C.c_void_p()
@@ -402,18 +445,20 @@ def methphase_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg
 def report_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cov: int = 0,
                  chunk_size: int = 50_000, chunk_stride: int = 1_000_000, lcfg: Optional[LoadConfig] = None,
                  untagged: bool = False, threads: int = 8, ctx=None, n_devices: int = 1, k: int = 3,
-                 k_span: int = 5000, host_fetch: bool = False, ctxs=None) -> Dict:
+                 k_span: int = 5000, host_fetch: bool = False, ctxs=None, mask_bed: Optional[str] = None,
+                 mask_variants: bool = False) -> Dict:
     """`pomfret report` (main_methreport, 4901-5089): chunk windows inside the
     phased blocks, one methphase decision each; writes
     {out_prefix}.report.tsv and the running totals to stdout.  cov: -c
-    (0: the per-contig estimate).  Returns dict(decision, counts)."""
+    (0: the per-contig estimate).  mask_bed / mask_variants: --mask-bed /
+    --mask-variants.  Returns dict(decision, counts, n_limit, masked_sites)."""
     L = _bind()
     if ctx is not None:
         ctxs = [ctx]
     o = make_opts(bam_path, vcf_path, out_prefix, Config(k=k, k_span=k_span), lcfg, mode=MODE_REPORT,
                   untagged=untagged, threads=threads, n_devices=0 if ctxs else n_devices,
                   ctxs=ctxs or None, cov=cov, chunk_size=chunk_size, chunk_stride=chunk_stride,
-                  host_fetch=host_fetch)
+                  host_fetch=host_fetch, mask_bed=mask_bed, mask_variants=mask_variants)
     h = C.c_void_p()
     _check(L.pf_methphase_main(C.byref(o), C.byref(h)), "pf_methphase_main")
     plan = Plan(o, handle=h)
@@ -428,7 +473,8 @@ def methphase_files_dist(bam_path: str, vcf_path: str, out_prefix: Optional[str]
                          threads: int = 8, ctx=None, group=None, job_windows: int = 0, mode: int = MODE_METHPHASE,
                          cov: int = 0, chunk_size: int = 50_000, chunk_stride: int = 1_000_000,
                          runner: Optional[Callable] = None, writer: int = 0, host_fetch: bool = False,
-                         intervals=None, write_input_tagging: bool = False) -> Dict:
+                         intervals=None, write_input_tagging: bool = False, mask_bed: Optional[str] = None,
+                         mask_variants: bool = False) -> Dict:
     """One process per GPU (torch.distributed initialised; RCCL on GPUs,
     gloo on CPU).  Every rank plans the same jobs and runs the ones its
     static LPT shard owns on `ctx` (or its LOCAL_RANK device); -u tables are
@@ -436,13 +482,16 @@ def methphase_files_dist(bam_path: str, vcf_path: str, out_prefix: Optional[str]
     results are gathered to `writer`, which merges them in (contig, window)
     order, writes the outputs and broadcasts the decisions.
     `runner(plan, kind, j) -> result dict` replaces the device for a job
-    (the CPU tests plug the oracle in here)."""
+    (the CPU tests plug the oracle in here).  mask_bed / mask_variants:
+    every rank loads the same mask; the result's masked_sites counts the
+    writer's own jobs only."""
     import torch.distributed as dist
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     o = make_opts(bam_path, vcf_path, out_prefix if rank == writer else None, cfg, lcfg, mode=mode,
                   untagged=untagged, tsv=tsv, threads=threads, rank=rank, world=world, job_windows=job_windows,
                   cov=cov, chunk_size=chunk_size, chunk_stride=chunk_stride, host_fetch=host_fetch,
-                  intervals=intervals, write_input_tagging=write_input_tagging)
+                  intervals=intervals, write_input_tagging=write_input_tagging, mask_bed=mask_bed,
+                  mask_variants=mask_variants)
     plan = Plan(o)
     try:
         def run(kind):
