@@ -542,8 +542,8 @@ int  pf_batch_upload_bam(pf_ctx_t *ctx, const pf_cfg_t *cfg, const pf_load_cfg_t
                          uint32_t readback, uint32_t max_win_recs, pf_dbatch_t **out, pf_bam_dev_fetch_t **fetch);
 void pf_bam_dev_fetch_free(pf_bam_dev_fetch_t *fetch);
 /* The -u pre-pass with the device fetch: the reads pf_bam_fetch_contig_reads
- * returns (the whole contig, primary mapped, MD:Z required: PF_ERR_ARG
- * otherwise) inflated, selected and gathered on the device and haptagged there
+ * returns (the whole contig, primary mapped, MD:Z required unless a
+ * reference is attached: PF_ERR_ARG otherwise) inflated, selected and gathered on the device and haptagged there
  * by K4 against `known` (pf_haptag_reads' semantics).  *fetch holds n_recs
  * reads in BAM order: read_hp, qnames. */
 int  pf_haptag_bam(pf_ctx_t *ctx, const pf_known_vars_t *known, pf_bam_t *bam, const char *chrom,
@@ -580,7 +580,8 @@ uint64_t pf_bam_contig_pieces(pf_bam_t *bam, int32_t tid, uint64_t piece_bytes, 
  * 1841-1898: sam_itr_querys over the whole contig, flags 4/256/2048
  * skipped), in BAM order, as pf_haptag_reads takes them, plus qnames for
  * its first-wins table.  A primary mapped record without MD:Z returns
- * PF_ERR_ARG (the reference asserts, 1594-1595). */
+ * PF_ERR_ARG (the reference asserts, 1594-1595) unless a reference is attached
+ * (pf_bam_set_ref: every record's MD is then synthesised, its tag ignored). */
 typedef struct pf_bam_reads {
     pf_read_aln_batch_t reads;
     const uint64_t *qname_off;     /* [n_reads+1] */
@@ -610,6 +611,58 @@ int  pf_bam_estimate_coverage_dev(pf_ctx_t *ctx, pf_bam_t *bam, int32_t *covs, i
 int  pf_bam_estimate_contig_dev(pf_ctx_t *ctx, pf_bam_t *bam, int32_t tid, int32_t *cov, int32_t *truncated);
 
 
+/* ------------------------------------------------------------------ */
+/* MD synthesis from a reference FASTA (DESIGN.md "MD synthesis"): for  */
+/* BAMs whose records carry no MD:Z.                                     */
+
+/* The FASTA, read once front to back (plain or gzipped; no .fai / BGZF
+ * random access).  A name runs from '>' to the first whitespace; in the
+ * sequence all whitespace is dropped, case folded, A C G T -> 1 2 4 8, U -> 8,
+ * every other byte -> 15 (N).  PF_ERR_ARG for a duplicate name or sequence
+ * before the first header, -1 when the file cannot be read. */
+typedef struct pf_ref pf_ref_t;
+int  pf_ref_open(const char *path, pf_ref_t **out);
+uint32_t pf_ref_n(const pf_ref_t *ref);
+const char *pf_ref_name(const pf_ref_t *ref, uint32_t i);
+/* contig `name`: its packed nibbles, high nibble first as BAM SEQ is packed
+ * ((len + 1) / 2 bytes, valid until pf_ref_free), and its length in bases;
+ * PF_ERR_ARG when absent */
+int  pf_ref_contig(const pf_ref_t *ref, const char *name, const uint8_t **nib, uint64_t *len);
+void pf_ref_free(pf_ref_t *ref);
+
+/* Attach a reference to a BAM handle (NULL detaches; the handle does not own
+ * it).  PF_ERR_ARG when a BAM target is present in the FASTA with another
+ * length; a target absent from the FASTA is an error only when a record on it
+ * needs its MD.  With a reference attached pf_haptag_bam, _cov, _pieces,
+ * pf_bam_fetch_contig_reads and pf_rescue_dropped, _mt, _multi synthesise the
+ * MD of every record they would have read MD:Z from and ignore the tags. */
+int  pf_bam_set_ref(pf_bam_t *bam, const pf_ref_t *ref);
+/* target tid's nibbles in the attached reference: 1 and (*nib, *len), 0 when
+ * no reference is attached, PF_ERR_ARG when the FASTA lacks the target */
+int  pf_bam_ref_contig(const pf_bam_t *bam, int32_t tid, const uint8_t **nib, uint64_t *len);
+
+/* The MD rule on the host: md_off[n_reads + 1] and the MD bytes of every read
+ * of `reads` against the contig's nibbles (reads->md and md_off are ignored).
+ * PF_ERR_ARG when an M/=/X/D op reaches past ref_len.  Free with pf_md_free. */
+int  pf_md_synth_host(const pf_read_aln_batch_t *reads, const uint8_t *ref_nib, uint64_t ref_len, uint64_t **md_off,
+                      uint8_t **md);
+void pf_md_free(uint64_t *md_off, uint8_t *md);
+/* The same bytes from the device kernels (pf_k4_mdlen, pf_k4_mdfill), copied
+ * back: for tests and callers that want the tag.  ref_len < 2^32. */
+int  pf_md_synth(pf_ctx_t *ctx, const pf_read_aln_batch_t *reads, const uint8_t *ref_nib, uint64_t ref_len,
+                 uint64_t **md_off, uint8_t **md);
+/* pf_haptag_reads on the synthesised MD, which never leaves the device */
+int  pf_haptag_reads_ref(pf_ctx_t *ctx, const pf_known_vars_t *known, const pf_read_aln_batch_t *reads,
+                         const uint8_t *ref_nib, uint64_t ref_len, uint8_t *hp_out);
+/* measurement hook: the context's MD synthesis so far -- reference bytes
+ * uploaded, reads synthesised, MD bytes written, and the two kernels' summed
+ * times */
+typedef struct pf_md_stats {
+    uint64_t ref_upload_bytes, n_reads, md_bytes;
+    double ms_len, ms_fill;
+} pf_md_stats_t;
+int  pf_ctx_md_stats(const pf_ctx_t *ctx, pf_md_stats_t *out);
+
 /* qname -> tag table across the boundary (first entry of a qname wins). */
 typedef struct pf_qname_tags {
     uint32_t n;
@@ -629,7 +682,8 @@ typedef struct pf_qname_tags {
  * REF on hap0, else 254.  A known position sorted last among the interval's
  * entries gets no vote (the loop stops at n-1).  Positions ascending, last
  * write wins.  PF_ERR_ARG for an MD-less selected record (the reference
- * asserts) or an invalid MD character (it exits). */
+ * asserts) unless a reference is attached (pf_bam_set_ref), or an invalid MD
+ * character (it exits). */
 typedef struct pf_rescue_map {
     uint32_t n;
     const uint32_t *pos;
@@ -770,6 +824,9 @@ typedef struct pf_methphase_opts {
     int32_t mask_variants;         /* --mask-variants: also every phased variant's [pos, pos+len)
                                       of --vcf, the set main_methreport builds and leaves unused
                                       (blockjoin.c:5006-5029, 4250-4251); needs vcf_path         */
+    const char *ref_path;          /* --ref: reference FASTA (plain or gzipped; NULL: none).  Every
+                                      BAM handle of the run gets it attached (pf_bam_set_ref): the -u
+                                      pre-pass and the rescue synthesise MD and need no MD:Z tags */
 } pf_methphase_opts_t;
 
 typedef struct pf_mp_plan pf_mp_plan_t;

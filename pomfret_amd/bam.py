@@ -10,12 +10,14 @@ table of blockjoin.c:4408-4423).  Host code; no GPU involved.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
 from ._lib import PomfretError, _check, lib
 from .abi import AlnBatch, KnownVars, PfAlnBatch, PfKnownVars, ReadAlnBatch
+from .abi import PfReadAlnBatch as _PfReadAln
 
 READBACK = 50_000  # blockjoin.c READBACK, the region margin of 1053-1054
 
@@ -45,6 +47,11 @@ class PfQnameTags(C.Structure):
 
 class PfRescueMap(C.Structure):
     _fields_ = [("n", C.c_uint32), ("pos", C.c_void_p), ("hap_of_ref", C.c_void_p)]
+
+
+class PfMdStats(C.Structure):
+    _fields_ = [("ref_upload_bytes", C.c_uint64), ("n_reads", C.c_uint64), ("md_bytes", C.c_uint64),
+                ("ms_len", C.c_double), ("ms_fill", C.c_double)]
 
 
 _bound = False
@@ -105,6 +112,26 @@ def _bind():
     L.pf_bam_dev_fetch_free.argtypes = [C.POINTER(PfBamDevFetch)]
     L.pf_haptag_bam.argtypes = [C.c_void_p, C.POINTER(PfKnownVars), C.c_void_p, C.c_char_p,
                                 C.POINTER(C.POINTER(PfBamDevFetch))]
+    L.pf_haptag_bam_pieces.argtypes = [C.c_void_p, C.POINTER(PfKnownVars), C.c_void_p, C.c_char_p, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.POINTER(C.POINTER(PfBamDevFetch)), C.c_void_p,
+                                       C.c_void_p]
+    L.pf_ref_open.argtypes = [C.c_char_p, C.POINTER(C.c_void_p)]
+    L.pf_ref_free.argtypes = [C.c_void_p]
+    L.pf_ref_free.restype = None
+    L.pf_ref_n.argtypes = [C.c_void_p]
+    L.pf_ref_n.restype = C.c_uint32
+    L.pf_ref_name.argtypes = [C.c_void_p, C.c_uint32]
+    L.pf_ref_name.restype = C.c_char_p
+    L.pf_ref_contig.argtypes = [C.c_void_p, C.c_char_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+    L.pf_bam_set_ref.argtypes = [C.c_void_p, C.c_void_p]
+    md_args = [C.POINTER(_PfReadAln), C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
+    L.pf_md_synth_host.argtypes = md_args
+    L.pf_md_synth.argtypes = [C.c_void_p] + md_args
+    L.pf_md_free.argtypes = [C.c_void_p, C.c_void_p]
+    L.pf_md_free.restype = None
+    L.pf_haptag_reads_ref.argtypes = [C.c_void_p, C.POINTER(PfKnownVars), C.POINTER(_PfReadAln), C.c_void_p,
+                                      C.c_uint64, C.c_void_p]
+    L.pf_ctx_md_stats.argtypes = [C.c_void_p, C.POINTER(PfMdStats)]
     _bound = True
     return L
 
@@ -150,6 +177,13 @@ class BamFile:
             self.close()
         except Exception:
             pass
+
+    def set_ref(self, ref: Optional["Reference"]):
+        """Attach a reference (pf_bam_set_ref; None detaches): the -u pre-pass
+        and the rescue then synthesise every record's MD from it and need no
+        MD:Z tags.  A target the FASTA holds with another length is refused."""
+        _check(_bind().pf_bam_set_ref(self.handle, ref.handle if ref is not None else None), "pf_bam_set_ref")
+        self._ref = ref                      # the handle does not own it: keep it alive
 
     @property
     def n_targets(self) -> int:
@@ -254,15 +288,24 @@ class BamFile:
             L.pf_bam_dev_fetch_free(f)
         return DeviceBatch._wrap(ctx, h, W), qnames, info
 
-    def haptag_device(self, ctx, chrom: str, known) -> Tuple[np.ndarray, List[str], dict]:
+    def haptag_device(self, ctx, chrom: str, known, bounds: Optional[Sequence[int]] = None
+                      ) -> Tuple[np.ndarray, List[str], dict]:
         """The -u pre-pass of one contig through the device fetch
-        (pf_haptag_bam): (tag per read, qnames, info), reads in BAM order."""
+        (pf_haptag_bam): (tag per read, qnames, info), reads in BAM order.
+        bounds: the contig fetched in the position pieces they split it into
+        (pf_haptag_bam_pieces)."""
         if self.path is None:
             raise PomfretError("index-only BamFile cannot fetch")
         L = _bind()
         kc = known.to_c()
         f = C.POINTER(PfBamDevFetch)()
-        _check(L.pf_haptag_bam(ctx.handle, C.byref(kc), self.handle, chrom.encode(), C.byref(f)), "pf_haptag_bam")
+        if bounds is None:
+            _check(L.pf_haptag_bam(ctx.handle, C.byref(kc), self.handle, chrom.encode(), C.byref(f)),
+                   "pf_haptag_bam")
+        else:
+            bd = np.ascontiguousarray(bounds, np.int64)
+            _check(L.pf_haptag_bam_pieces(ctx.handle, C.byref(kc), self.handle, chrom.encode(), bd.size,
+                                          bd.ctypes.data, None, C.byref(f), None, None), "pf_haptag_bam_pieces")
         try:
             r = f.contents
             n = int(r.n_recs)
@@ -324,6 +367,107 @@ class BamFile:
         finally:
             L.pf_bam_reads_free(out)
         return reads, qnames, info
+
+
+Bam = BamFile
+
+
+class Reference:
+    """A reference FASTA held on the host (pf_ref_open): plain or gzipped, read
+    once front to back.  `contig(name)` gives the packed nibbles (high nibble
+    first, BAM SEQ's code: A 1, C 2, G 4, T/U 8, anything else 15) and the
+    length in bases."""
+
+    def __init__(self, path: str):
+        L = _bind()
+        h = C.c_void_p()
+        rc = L.pf_ref_open(path.encode(), C.byref(h))
+        if rc == -1 and not os.path.exists(path):      # -1 is PF_ERR_ARG too (a malformed FASTA)
+            raise FileNotFoundError(path)
+        _check(rc, "pf_ref_open")
+        self.handle = h
+        self.path = path
+
+    @classmethod
+    def open(cls, path: str) -> "Reference":
+        return cls(path)
+
+    @property
+    def names(self) -> List[str]:
+        L = lib()
+        return [L.pf_ref_name(self.handle, i).decode() for i in range(int(L.pf_ref_n(self.handle)))]
+
+    def contig(self, name: str) -> Tuple[np.ndarray, int]:
+        p, n = C.c_void_p(), C.c_uint64()
+        _check(lib().pf_ref_contig(self.handle, name.encode(), C.byref(p), C.byref(n)), "pf_ref_contig")
+        return _arr(p.value, (n.value + 1) // 2, np.uint8), int(n.value)
+
+    def close(self):
+        if self.handle:
+            lib().pf_ref_free(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _md_out(L, off_p, md_p, n) -> Tuple[np.ndarray, np.ndarray]:
+    try:
+        off = _arr(off_p.value, n + 1, np.uint64)
+        return off, _arr(md_p.value, off[-1], np.uint8)
+    finally:
+        L.pf_md_free(off_p, md_p)
+
+
+def md_synth_host(reads: ReadAlnBatch, nib: np.ndarray, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(md_off, md) of every read from CIGAR, SEQ and the contig's packed
+    nibbles `nib` of `n` bases (pf_md_synth_host: the MD rule on the host)."""
+    L = _bind()
+    nib = np.ascontiguousarray(nib, np.uint8)
+    r = reads.to_c()
+    off_p, md_p = C.c_void_p(), C.c_void_p()
+    _check(L.pf_md_synth_host(C.byref(r), nib.ctypes.data, int(n), C.byref(off_p), C.byref(md_p)),
+           "pf_md_synth_host")
+    return _md_out(L, off_p, md_p, reads.n_reads)
+
+
+def md_synth(ctx, reads: ReadAlnBatch, nib: np.ndarray, n: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The same bytes from the device kernels (pf_md_synth)."""
+    L = _bind()
+    nib = np.ascontiguousarray(nib, np.uint8)
+    r = reads.to_c()
+    off_p, md_p = C.c_void_p(), C.c_void_p()
+    _check(L.pf_md_synth(ctx.handle, C.byref(r), nib.ctypes.data, int(n), C.byref(off_p), C.byref(md_p)),
+           "pf_md_synth")
+    return _md_out(L, off_p, md_p, reads.n_reads)
+
+
+def haptag_reads_ref(ctx, known: KnownVars, reads: ReadAlnBatch, nib: np.ndarray, n: int) -> np.ndarray:
+    """pf_haptag_reads on MD synthesised on the device from `nib`
+    (pf_haptag_reads_ref); reads.md is ignored."""
+    L = _bind()
+    nib = np.ascontiguousarray(nib, np.uint8)
+    out = np.zeros(max(reads.n_reads, 1), np.uint8)
+    k, r = known.to_c(), reads.to_c()
+    _check(L.pf_haptag_reads_ref(ctx.handle, C.byref(k), C.byref(r), nib.ctypes.data, int(n), out.ctypes.data),
+           "pf_haptag_reads_ref")
+    return out[:reads.n_reads]
+
+
+def md_stats(ctx) -> dict:
+    """The context's MD synthesis so far (pf_ctx_md_stats)."""
+    s = PfMdStats()
+    _check(_bind().pf_ctx_md_stats(ctx.handle, C.byref(s)), "pf_ctx_md_stats")
+    return {k: getattr(s, k) for k, _ in PfMdStats._fields_}
 
 
 def _known_of(L, t) -> KnownVars:

@@ -34,6 +34,7 @@
 #include <zlib.h>
 
 #include "../../include/pomfret_amd.h"
+#include "pf_host.h"
 
 /* ------------------------------------------------------------------ */
 /* BGZF */
@@ -439,6 +440,11 @@ struct pf_bam {
     ref_idx_t *idx;
     int64_t n_no_coor;           /* the index's count of unplaced records; -1 when it has none */
     int n_threads;               /* inflate threads of the whole-file / whole-contig passes */
+    /* attached reference (pf_bam_set_ref; not owned): per target its nibbles
+     * and length, ref_nib[tid] NULL when the FASTA lacks the target */
+    const pf_ref_t *ref;
+    const uint8_t **ref_nib;
+    uint64_t *ref_len;
 };
 
 static int cmp_bin(const void *a, const void *b) {
@@ -616,7 +622,39 @@ void pf_bam_close(pf_bam_t *b) {
     }
     free(b->idx);
     free(b->path);
+    free(b->ref_nib);
+    free(b->ref_len);
     free(b);
+}
+
+int pf_bam_set_ref(pf_bam_t *b, const pf_ref_t *ref) {
+    if (!b) return PF_ERR_ARG;
+    if (!ref) {
+        free(b->ref_nib); free(b->ref_len);
+        b->ref = NULL; b->ref_nib = NULL; b->ref_len = NULL;
+        return PF_OK;
+    }
+    if (!b->names || !b->lens) return PF_ERR_ARG;
+    const size_t n = b->n_ref > 0 ? (size_t)b->n_ref : 1;
+    const uint8_t **nib = (const uint8_t **)calloc(n, sizeof *nib);
+    uint64_t *len = (uint64_t *)calloc(n, sizeof *len);
+    if (!nib || !len) { free(nib); free(len); return PF_ERR_NOMEM; }
+    for (int32_t r = 0; r < b->n_ref; r++) {
+        if (pf_ref_contig(ref, b->names[r], &nib[r], &len[r]) != PF_OK) { nib[r] = NULL; continue; }
+        if (len[r] != b->lens[r]) { free(nib); free(len); return PF_ERR_ARG; }
+    }
+    free(b->ref_nib); free(b->ref_len);
+    b->ref = ref; b->ref_nib = nib; b->ref_len = len;
+    return PF_OK;
+}
+
+int pf_bam_ref_contig(const pf_bam_t *b, int32_t tid, const uint8_t **nib, uint64_t *len) {
+    if (!b) return PF_ERR_ARG;
+    if (!b->ref) return 0;
+    if (tid < 0 || tid >= b->n_ref || !b->ref_nib[tid]) return PF_ERR_ARG;
+    if (nib) *nib = b->ref_nib[tid];
+    if (len) *len = b->ref_len[tid];
+    return 1;
 }
 
 const char *pf_bam_path(const pf_bam_t *b) { return b ? b->path : NULL; }
@@ -804,7 +842,38 @@ typedef struct {
     size_t chunk_cap;
     int reads_mode;           /* 1: pre_haplotagging_read_in_one_ref's records (1869-1871);
                                  2: every record (the rescue pass, 2510-2545) */
+    uint8_t *md;              /* a record's synthesised MD (reference attached) */
+    uint64_t md_cap;
 } fetcher_t;
+
+/* where a record's MD comes from: its MD:Z tag (have 0), or the rule over the
+ * attached reference (have 1; < 0: the FASTA lacks the contig) */
+typedef struct {
+    int have;
+    const uint8_t *nib;
+    uint64_t len;
+    uint8_t **buf;
+    uint64_t *cap;
+} mdsrc_t;
+
+/* the record's MD bytes: 1 and (*mdz, *mdl), 0 when it has none, < 0 on an error */
+static int rec_md(const mdsrc_t *M, const rec_t *r, const uint8_t *cg, uint32_t ncg, const char **mdz, size_t *mdl) {
+    if (M->have) {
+        if (M->have < 0) return PF_ERR_ARG;
+        uint64_t n = 0;
+        const int rc = pf_md_synth_rec(cg, ncg, r->seq, r->l_qseq, (uint32_t)r->pos, M->nib, M->len, M->buf, &n,
+                                       M->cap);
+        if (rc) return rc;
+        *mdz = (const char *)*M->buf;
+        *mdl = (size_t)n;
+        return 1;
+    }
+    const uint8_t *md = aux_find(r->aux, r->aux_end, "MD");
+    if (!md || md[2] != 'Z') { *mdz = ""; *mdl = 0; return 0; }
+    *mdz = (const char *)(md + 3);
+    *mdl = strlen(*mdz);
+    return 1;
+}
 
 static int push_record(recbuf_t *rb, const rec_t *r, const uint8_t *cg, uint32_t ncg) {
     int rc = 0;
@@ -864,13 +933,15 @@ static int push_record(recbuf_t *rb, const rec_t *r, const uint8_t *cg, uint32_t
 }
 
 /* -u pre-pass record: primary mapped only, MD:Z required (the reference
- * asserts on it, 1594-1595) */
-static int push_read(recbuf_t *rb, const rec_t *r, const uint8_t *cg, uint32_t ncg, uint32_t end) {
+ * asserts on it, 1594-1595) unless a reference is attached: then the MD is
+ * the rule's (pf_md_synth_rec) and the tag is ignored */
+static int push_read(recbuf_t *rb, const rec_t *r, const uint8_t *cg, uint32_t ncg, uint32_t end,
+                     const mdsrc_t *M) {
     int rc = 0;
-    const uint8_t *md = aux_find(r->aux, r->aux_end, "MD");
-    if (!md || md[2] != 'Z') return PF_ERR_ARG;
-    const char *mdz = (const char *)(md + 3);
-    const size_t mdl = strlen(mdz);
+    const char *mdz = "";
+    size_t mdl = 0;
+    const int got = rec_md(M, r, cg, ncg, &mdz, &mdl);
+    if (got <= 0) return got < 0 ? got : PF_ERR_ARG;
     const uint32_t pos = (uint32_t)r->pos, lq = r->l_qseq;
     uint64_t off;
 #define PUTV(fi, ptr, nb) do { if ((rc = vb_put(&rb->f[fi], (ptr), (nb)))) return rc; } while (0)
@@ -890,13 +961,22 @@ static int push_read(recbuf_t *rb, const rec_t *r, const uint8_t *cg, uint32_t n
     return 0;
 }
 
-/* rescue pass record: pos, get_hp_from_aln, CIGAR, MD (F_FLAG = 1 when present), qname */
-static int push_any(recbuf_t *rb, const rec_t *r, const uint8_t *cg, uint32_t ncg) {
+/* rescue pass record: pos, get_hp_from_aln, CIGAR, MD (F_FLAG = 1 when present; with a
+ * reference attached the synthesised one), qname */
+static int push_any(recbuf_t *rb, const rec_t *r, const uint8_t *cg, uint32_t ncg, const mdsrc_t *M) {
     int rc = 0;
-    const uint8_t *md = aux_find(r->aux, r->aux_end, "MD");
-    const uint16_t has_md = (md && md[2] == 'Z') ? 1 : 0;
-    const char *mdz = has_md ? (const char *)(md + 3) : "";
-    const size_t mdl = strlen(mdz);
+    const char *mdz = "";
+    size_t mdl = 0;
+    /* with a reference only records that can carry variants get an MD: an
+     * unmapped or CIGAR-less record is never voted on a position */
+    int got = 0;
+    if (!M->have) got = rec_md(M, r, cg, ncg, &mdz, &mdl);
+    else if (!(r->flag & 4) && ncg > 0) got = rec_md(M, r, cg, ncg, &mdz, &mdl);
+    if (got == PF_ERR_NOMEM) return got;
+    /* no MD to synthesise (the FASTA lacks the contig, an op past its end):
+     * an error only when the record is selected, as a missing tag is */
+    if (got < 0) { got = 0; mdz = ""; mdl = 0; }
+    const uint16_t has_md = got ? 1 : 0;
     uint8_t hp = 254;
     const uint8_t *t = aux_find(r->aux, r->aux_end, "HP");
     if (t) {
@@ -980,6 +1060,8 @@ static int fetch_region(fetcher_t *F, int64_t beg, int64_t end, recbuf_t *rb) {
     if (nci <= 0) return (int)nci;
     const size_t nc = (size_t)nci;
     uint64_t done = 0;                          /* records before this offset were read */
+    mdsrc_t M = {0, NULL, 0, &F->md, &F->md_cap};
+    M.have = pf_bam_ref_contig(F->b, F->tid, &M.nib, &M.len);
     for (size_t c = 0; c < nc; c++) {
         uint64_t at = F->chunks[c].u > done ? F->chunks[c].u : done;
         if (at >= F->chunks[c].v) continue;
@@ -1023,8 +1105,8 @@ static int fetch_region(fetcher_t *F, int64_t beg, int64_t end, recbuf_t *rb) {
             if (r.tid != F->tid || (int64_t)r.pos >= end) return 0;
             if ((int64_t)r.pos + (int64_t)rlen > beg) {
                 if (!F->reads_mode) rc = push_record(rb, &r, cg, ncg);
-                else if (F->reads_mode == 2) rc = push_any(rb, &r, cg, ncg);
-                else if (!(r.flag & (4 | 256 | 2048))) rc = push_read(rb, &r, cg, ncg, (uint32_t)(r.pos + rlen));
+                else if (F->reads_mode == 2) rc = push_any(rb, &r, cg, ncg, &M);
+                else if (!(r.flag & (4 | 256 | 2048))) rc = push_read(rb, &r, cg, ncg, (uint32_t)(r.pos + rlen), &M);
                 if (rc) return rc;
             }
         }
@@ -1061,6 +1143,7 @@ static void *fetch_job(void *arg) {
     }
     bgzf_close(&F.z);
     free(F.rec);
+    free(F.md);
     free(F.chunks);
     j->rc = rc;
     return NULL;
@@ -1241,6 +1324,7 @@ int pf_bam_fetch_contig_reads(pf_bam_t *b, const char *chrom, pf_bam_reads_t **o
     if (!rc) rc = fetch_region(&F, 0, INT64_MAX, &o->rb);
     bgzf_close(&F.z);
     free(F.rec);
+    free(F.md);
     free(F.chunks);
     recbuf_t *R = &o->rb;
     static const int offs[4][2] = {{F_CIGOFF, F_CIG}, {F_SEQOFF, F_SEQ}, {F_MMOFF, F_MM}, {F_QNOFF, F_QN}};
@@ -1521,6 +1605,7 @@ static void *rescue_main(void *arg) {
     }
     if (open) bgzf_close(&F.z);
     free(F.rec);
+    free(F.md);
     free(F.chunks);
     free(pb.a);
     J->rc = rc;

@@ -16,7 +16,10 @@
  * decoded on the host instead of the device fetch), --job-windows W (windows per device
  * job), and --mask-bed FILE / --mask-variants (reference positions no
  * methylation site may lie on: a BED's intervals, the phased variants of
- * --vcf; methphase and report).  Phase blocks come from --tsv, else --gtf, else --vcf (main_blockjoin
+ * --vcf; methphase and report), and --ref FILE (a reference FASTA, plain or
+ * gz'd: MD is synthesised on the device for the -u pre-pass and on the host
+ * for the rescue, so the BAM needs no MD:Z tags; methphase, report and
+ * varhaptag).  Phase blocks come from --tsv, else --gtf, else --vcf (main_blockjoin
  * 4661-4666); with -u the VCF still supplies the variants and the contigs to
  * pre-haplotag.  -U writes {prefix}.mp.input_haptag.tsv (4494-4517).  --dbg's
  * {prefix}.mp.dbg.read2tag (2223-2248) lists a khash in bucket order, which
@@ -74,10 +77,12 @@ static void help_methphase(const char *prefix) {
                     "               positions that are never used as methylation sites (methphase, report).\n");
     fprintf(stderr, "  --mask-variants [opt] Also mask every phased variant of --vcf (its position and length):\n"
                     "               a CpG a heterozygous variant creates or destroys is no site.\n");
+    fprintf(stderr, "  --ref FILE [opt] Reference FASTA (plain or gz'd).  With it the bam needs no MD tags: -u and the\n"
+                    "               VCF writer's rescue compute MD from CIGAR, SEQ and the reference (also varhaptag).\n");
 }
 
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
-       O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR };
+       O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -91,13 +96,14 @@ static const struct option longopts[] = {
     {"gpus", required_argument, 0, O_GPUS},      {"job-windows", required_argument, 0, O_JOBW},
     {"host-fetch", no_argument, 0, O_HFETCH},
     {"mask-bed", required_argument, 0, O_MBED},  {"mask-variants", no_argument, 0, O_MVAR},
+    {"ref", required_argument, 0, O_REF},
     {0, 0, 0, 0}};
 
 typedef struct {
     int help, threads, lo, hi, readlen, mapq, k, k_span, cov, cov_sel, n_cand, untagged, out_tsv, out_bam;
     int chunk_size, chunk_stride, gpus, job_windows, verbose, host_fetch, write_input_tagging, dbg, bam_threads;
     int mask_variants;
-    char *prefix, *vcf, *gtf, *tsv, *bam, *mask_bed;
+    char *prefix, *vcf, *gtf, *tsv, *bam, *mask_bed, *ref;
 } cli_t;
 
 static int parse(int argc, char **argv, cli_t *c) {
@@ -137,6 +143,7 @@ static int parse(int argc, char **argv, cli_t *c) {
         case O_HFETCH: c->host_fetch = 1; break;
         case O_MBED: c->mask_bed = optarg; break;
         case O_MVAR: c->mask_variants = 1; break;
+        case O_REF: c->ref = optarg; break;
         default:
             fprintf(stderr, "[E::parse_cli] unknown or incomplete option \"%s\"\n", argv[optind - 1]);
             return 1;
@@ -175,6 +182,11 @@ static int sancheck(cli_t *c) {                       /* sancheck_cliopt, cli.c:
         if (!fp) { fprintf(stderr, "[E::sancheck_cliopt] cannot read --mask-bed %s\n", c->mask_bed); return 1; }
         fclose(fp);
     }
+    if (c->ref) {
+        FILE *fp = fopen(c->ref, "rb");
+        if (!fp) { fprintf(stderr, "[E::sancheck_cliopt] cannot read --ref %s\n", c->ref); return 1; }
+        fclose(fp);
+    }
     if (!c->bam) { fprintf(stderr, "[E::sancheck_cliopt] missing bam file\n"); return 1; }
     size_t l = c->prefix ? strlen(c->prefix) : 0;
     while (l > 0 && c->prefix[l - 1] == '/') c->prefix[--l] = 0;
@@ -195,13 +207,13 @@ static int sancheck(cli_t *c) {                       /* sancheck_cliopt, cli.c:
 /* varhaptag: parse_cli_varhaptag (cli.c:386-446): -o out.bam, -t, -v,
  * --write-bam (disables the BAM), positional in.vcf then in.bam */
 static int varhaptag(int argc, char **argv) {
-    const char *out = "pomfret_varhaptag", *vcf = NULL, *bam = NULL;
+    const char *out = "pomfret_varhaptag", *vcf = NULL, *bam = NULL, *ref = NULL;
     int threads = 1, verbose = 0, write_bam = 1, gpus = 0, o;
     optind = 1;
     while ((o = getopt_long(argc, argv, "ho:t:r:v", longopts, NULL)) >= 0) {
         switch (o) {
         case 'h': case O_HELP:
-            fprintf(stderr, "Usage: pomfret-amd varhaptag [-t threads] -o out.bam in.vcf in.bam 2>log\n");
+            fprintf(stderr, "Usage: pomfret-amd varhaptag [-t threads] [--ref ref.fa] -o out.bam in.vcf in.bam 2>log\n");
             return 1;
         case 'o': out = optarg; break;
         case 't': threads = atoi(optarg); break;
@@ -209,6 +221,7 @@ static int varhaptag(int argc, char **argv) {
         case 'r': break;
         case O_WBAM: write_bam = 0; break;
         case O_GPUS: gpus = atoi(optarg); break;
+        case O_REF: ref = optarg; break;
         default:
             fprintf(stderr, "[E::parse_cli_varhaptag] unknown or incomplete option \"%s\"\n", argv[optind - 1]);
             return 1;
@@ -221,6 +234,11 @@ static int varhaptag(int argc, char **argv) {
     }
     if (!vcf || !bam) { fprintf(stderr, "[E::sancheck_cliopt_varhaptag] need a vcf and a bam\n"); return 1; }
     if (threads < 1) threads = 1;
+    if (ref) {
+        FILE *fp = fopen(ref, "rb");
+        if (!fp) { fprintf(stderr, "[E::sancheck_cliopt_varhaptag] cannot read --ref %s\n", ref); return 1; }
+        fclose(fp);
+    }
     pf_methphase_opts_t op;
     memset(&op, 0, sizeof op);
     op.mode = PF_MODE_VARHAPTAG;
@@ -231,6 +249,7 @@ static int varhaptag(int argc, char **argv) {
     op.threads = threads;
     op.n_devices = gpus;
     op.verbose = verbose;
+    op.ref_path = ref;
     pf_mp_plan_t *p = NULL;
     const int rc = pf_methphase_main(&op, &p);
     if (rc) {
@@ -296,6 +315,7 @@ int main(int argc, char **argv) {
     o.write_input_tagging = c.write_input_tagging;
     o.mask_path = c.mask_bed;
     o.mask_variants = c.mask_variants;
+    o.ref_path = c.ref;
     pf_mp_plan_t *p = NULL;
     const int rc = pf_methphase_main(&o, &p);
     if (rc) {

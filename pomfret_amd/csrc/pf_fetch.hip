@@ -330,7 +330,7 @@ __global__ __launch_bounds__(256) void pf_select(const pf_win_dev *wins, uint32_
             // -u reads (pre_haplotagging_read_in_one_ref, 1869-1871): primary mapped only
             const bool take = in && lane < fh && (int64_t)rp + (int64_t)(in ? R.rlen[k] : 0) > W.beg &&
                               (!W.reads || !(R.flag[k] & (4u | 256u | 2048u)));
-            if (W.reads && __ballot(take && !(rst & PF_REC_MD))) { status = PF_WIN_ERR; stop = true; break; }
+            if (W.reads == 1 && __ballot(take && !(rst & PF_REC_MD))) { status = PF_WIN_ERR; stop = true; break; }
             const uint64_t mt = __ballot(take);
             if (write && take) out[W.out + cnt + (uint32_t)__popcll(mt & lanemask_lt(lane))] = k;
             cnt += (uint32_t)__popcll(mt);

@@ -60,7 +60,8 @@ typedef struct pf_win_dev {
     uint32_t c0, c1;          // its chunks
     int32_t tid;
     uint16_t skip;            // write pass: window emptied (over the record limit)
-    uint16_t reads;           // the -u pre-pass fetch: primary mapped records only, MD:Z required
+    uint16_t reads;           // the -u pre-pass fetch: primary mapped records only; 1: MD:Z required,
+                              // 2: not (a reference is attached, the MD is synthesised)
     uint64_t out;             // write pass: first slot of its record list
 } pf_win_dev;
 

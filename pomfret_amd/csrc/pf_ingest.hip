@@ -1165,9 +1165,17 @@ static void cov_add(std::vector<uint64_t> &bins, const Small &S, uint64_t i) {
 // The -u pre-pass of one contig (pf_haptag_bam) and, with cov != nullptr,
 // the contig's coverage estimate from the same whole-contig fetch: every
 // record of the contig is selected (the estimate's pass), the primary mapped
-// ones go to K4 (the -u pass's records, which must carry MD).  *trunc is set
+// ones go to K4 (the -u pass's records, which must carry MD unless the handle
+// has a reference attached: then pf_mdsynth.hip writes it).  *trunc is set
 // when a truncated record ended the fetch (the estimate's serial pass stops
 // there).
+// pf_mdsynth.hip: the contig's reference on the context's device, and MD
+// synthesised from the gathered CIGAR / SEQ (pf_k4_mdlen, pf_k4_mdfill)
+int pf_mdsynth_ref_dev(pf_ctx_t *ctx, const uint8_t *nib, uint64_t len, const uint8_t **d_ref);
+int pf_mdsynth_dev(pf_ctx_t *ctx, hipStream_t st, uint32_t N, const pf_k4_reads_dev &in, const uint8_t *d_ref,
+                   uint64_t ref_len, std::vector<uint32_t> &md_len, std::vector<uint64_t> &md_off,
+                   std::vector<void *> &al, uint64_t **d_md_off, uint8_t **d_md);
+
 static int haptag_bam_impl(pf_ctx_t *ctx, const pf_known_vars_t *K, pf_bam_t *bam, const char *chrom,
                            pf_bam_dev_fetch_t **fetch_out, int32_t *cov, int32_t *trunc, uint32_t nb = 0,
                            const int64_t *bounds = nullptr, const int64_t *fetch_ends = nullptr) {
@@ -1180,6 +1188,11 @@ static int haptag_bam_impl(pf_ctx_t *ctx, const pf_known_vars_t *K, pf_bam_t *ba
     // piece's overlap list); the K4 cursor chain runs on across pieces
     const int32_t tid = pf_bam_tid(bam, chrom);
     if (tid < 0) return PF_ERR_ARG;
+    // a reference attached to the handle: every read's MD is synthesised from
+    // it (its tag, if any, is neither required nor gathered)
+    const uint8_t *ref_nib = nullptr;
+    uint64_t ref_len = 0;
+    const int with_ref = pf_bam_ref_contig(bam, tid, &ref_nib, &ref_len);
     int64_t step = 0;
     // the pieces' bounds: the caller's (the driver places them between its
     // windows' fetch regions), else K pieces of equal reference length
@@ -1206,7 +1219,7 @@ static int haptag_bam_impl(pf_ctx_t *ctx, const pf_known_vars_t *K, pf_bam_t *ba
         std::vector<uint32_t> take;                           // this piece's -u reads: selection positions
         ArenaCache *keep = cache_enabled(ctx) ? new ArenaCache() : nullptr;
         if (keep) { keep->pbeg = beg; keep->pend = fend; }
-        rc = dev_fetch(ctx, bam, tid, 1, &beg, &fend, with_cov ? 0u : 1u, 0u, &P, [&](FetchOut &fo) -> int {
+        rc = dev_fetch(ctx, bam, tid, 1, &beg, &fend, with_cov ? 0u : with_ref ? 2u : 1u, 0u, &P, [&](FetchOut &fo) -> int {
             const Small &S = *fo.S;
             uint64_t m = 0;                                   // records counted in an earlier piece
             if (k) while (m < fo.n && (int32_t)S.pos[m] < beg) m++;
@@ -1216,7 +1229,7 @@ static int haptag_bam_impl(pf_ctx_t *ctx, const pf_known_vars_t *K, pf_bam_t *ba
                 if (with_cov) {
                     cov_add(bins, S, i);
                     if (S.flag[i] & (4u | 256u | 2048u)) continue;              // primary mapped only (1869-1871)
-                    if (!(S.st[i] & PF_REC_MD)) return PF_ERR_ARG;              // the reference asserts MD
+                    if (!with_ref && !(S.st[i] & PF_REC_MD)) return PF_ERR_ARG; // the reference asserts MD
                 }
                 take.push_back((uint32_t)i);
             }
@@ -1225,16 +1238,17 @@ static int haptag_bam_impl(pf_ctx_t *ctx, const pf_known_vars_t *K, pf_bam_t *ba
             const size_t h0 = F->read_hp.size();
             F->read_hp.resize(h0 + N, 0);
             if (!N) return PF_OK;
+            if (with_ref < 0) return PF_ERR_ARG;                               // a read needs MD and the FASTA lacks the contig
             std::vector<uint32_t> start(N), endp(N), nins(N), ncig(N), mdl(N), lq(N);
             std::vector<uint64_t> co(N + 1, 0), so(N + 1, 0), mo(N + 1, 0);
             for (uint64_t i = 0; i < N; i++) {
                 const uint64_t r = take[i];
                 start[i] = S.pos[r];
                 endp[i] = (uint32_t)((int64_t)(int32_t)S.pos[r] + (int64_t)S.rlen[r]);   // bam_endpos
-                nins[i] = S.nins[r]; ncig[i] = S.ncig[r]; mdl[i] = S.md_len[r]; lq[i] = S.l_qseq[r];
+                nins[i] = S.nins[r]; ncig[i] = S.ncig[r]; mdl[i] = with_ref ? 0u : S.md_len[r]; lq[i] = S.l_qseq[r];
                 co[i + 1] = co[i] + S.ncig[r];
                 so[i + 1] = so[i] + (S.l_qseq[r] + 1ull) / 2;
-                mo[i + 1] = mo[i] + S.md_len[r];
+                mo[i + 1] = mo[i] + mdl[i];
             }
             DevBuf &D = *fo.D;
             hipStream_t st = fo.st;
@@ -1265,12 +1279,25 @@ static int haptag_bam_impl(pf_ctx_t *ctx, const pf_known_vars_t *K, pf_bam_t *ba
                                    N, fo.R, (const uint64_t *)d_co, d_cig, (const uint64_t *)d_so, d_seq,
                                    (const uint64_t *)nullptr, (uint8_t *)nullptr, (const uint64_t *)nullptr,
                                    (uint8_t *)nullptr, (const uint64_t *)nullptr, (uint8_t *)nullptr,
-                                   (const uint64_t *)d_mo, d_md);
+                                   with_ref ? (const uint64_t *)nullptr : (const uint64_t *)d_mo,
+                                   with_ref ? (uint8_t *)nullptr : d_md);
                 ok = hipGetLastError() == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
             }
             if (!ok) return PF_ERR_HIP;
             pf_k4_reads_host h{start.data(), endp.data(), nins.data(), ncig.data(), mdl.data()};
             pf_k4_reads_dev dv{d_start, d_end, d_co, d_cig, d_so, d_len, d_seq, d_mo, d_md};
+            std::vector<uint64_t> smo;
+            if (with_ref) {
+                const uint8_t *d_ref = nullptr;
+                int mrc = pf_mdsynth_ref_dev(ctx, ref_nib, ref_len, &d_ref);
+                uint64_t *s_mo = nullptr;
+                uint8_t *s_md = nullptr;
+                if (!mrc) mrc = pf_mdsynth_dev(ctx, st, (uint32_t)N, dv, d_ref, ref_len, mdl, smo, D.p, &s_mo, &s_md);
+                if (mrc) return mrc;
+                h.md_len = mdl.data();
+                dv.md_off = s_mo;
+                dv.md = s_md;
+            }
             return pf_haptag_core(ctx, K, (uint32_t)N, h, nullptr, &dv, F->read_hp.data() + h0, &prev_left);
         }, keep);
         if (keep && keep->d_arena && !rc) {

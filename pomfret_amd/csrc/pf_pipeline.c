@@ -263,7 +263,25 @@ struct pf_mp_plan {
     pf_mask_t *mask;           /* per window contig; NULL: no mask */
     uint64_t mask_loaded;      /* its positions */
     uint64_t masked_sites;     /* qualifying positions it removed, over the jobs run here (st_mu) */
+    /* --ref: the reference FASTA, opened at plan time and attached to every
+     * BAM handle the run opens (the -u pre-pass and the rescue synthesise MD) */
+    char *ref_path;
+    pf_ref_t *ref;             /* NULL: none */
 };
+
+/* the run's BAM, with the run's reference attached */
+static int plan_bam_open(const pf_mp_plan_t *p, pf_bam_t **bam) {
+    int rc = pf_bam_open(p->bam_path, NULL, bam);
+    if (!rc && p->ref) {
+        rc = pf_bam_set_ref(*bam, p->ref);
+        if (rc) {
+            fprintf(stderr, "[E::pomfret_amd] --ref %s: a contig's length differs from the BAM header's\n", p->ref_path);
+            pf_bam_close(*bam);
+            *bam = NULL;
+        }
+    }
+    return rc;
+}
 
 static double now_s(void) {
     struct timespec t;
@@ -331,6 +349,8 @@ void pf_mp_free(pf_mp_plan_t *p) {
     free(p->ucov); free(p->utrunc); free(p->uhave);
     pf_mask_free(p->mask);
     free(p->mask_path);
+    pf_ref_free(p->ref);
+    free(p->ref_path);
     pthread_mutex_destroy(&p->st_mu);
     free(p);
 }
@@ -419,6 +439,8 @@ static int mp_plan(const pf_methphase_opts_t *o, pf_mp_plan_t **out, int defer_e
     p->o.interval_path = p->interval_path;
     p->mask_path = dupstr(o->mask_path);
     p->o.mask_path = p->mask_path;
+    p->ref_path = dupstr(o->ref_path);
+    p->o.ref_path = p->ref_path;
     p->o.ctxs = NULL;
     p->o.n_ctxs = 0;
     /* -u: the VCF's contigs are pre-haplotagged (load_intervals_from_file with
@@ -449,6 +471,15 @@ static int mp_plan(const pf_methphase_opts_t *o, pf_mp_plan_t **out, int defer_e
             pf_mask_contig(p->mask, c, &mp, &mn);
             p->mask_loaded += mn;
         }
+    }
+    /* the reference, and its lengths against the BAM header's, before any job runs */
+    if (o->ref_path) {
+        rc = pf_ref_open(o->ref_path, &p->ref);
+        pf_bam_t *rb = NULL;
+        if (rc) fprintf(stderr, "[E::pomfret_amd] cannot load the reference %s\n", o->ref_path);
+        else rc = plan_bam_open(p, &rb);
+        if (rb) pf_bam_close(rb);
+        if (rc) { pf_mp_free(p); return rc; }
     }
     p->tid = (int32_t *)calloc(C ? C : 1, sizeof(int32_t));
     p->cfg = (pf_cfg_t *)calloc(C ? C : 1, sizeof(pf_cfg_t));
@@ -868,7 +899,7 @@ int pf_mp_run_haptag_job(pf_mp_plan_t *p, pf_ctx_t *ctx, uint32_t j) {
     entlist_t e = {0};
     pf_tags_t *seen = NULL;
     int rc = pf_vcf_known_vars(p->vcf_path, contig, &kt);
-    if (!rc && kt->vars.n) rc = pf_bam_open(p->bam_path, NULL, &bam);
+    if (!rc && kt->vars.n) rc = plan_bam_open(p, &bam);
     if (!rc && bam) pf_bam_set_threads(bam, p->o.threads);
     if (!rc && kt->vars.n && !p->o.host_fetch) {
         /* device fetch + K4 on the device (pf_haptag_bam) */
@@ -1253,7 +1284,7 @@ int pf_mp_run_job(pf_mp_plan_t *p, pf_ctx_t *ctx, uint32_t j) {
     if (!J || !ctx) return PF_ERR_ARG;
     if (p->o.untagged && !p->raw_merged) return PF_ERR_ARG;
     pf_bam_t *bam = NULL;
-    int rc = pf_bam_open(p->bam_path, NULL, &bam);
+    int rc = plan_bam_open(p, &bam);
     if (rc) return rc;
     if (!p->o.host_fetch) {
         rc = job_device_fetch(p, ctx, bam, J);
@@ -1358,7 +1389,7 @@ static int write_rescued_vcf(pf_mp_plan_t *p, char *fn, size_t L, int trace, dou
     for (uint32_t c = 0; kall && c < C; c++) pf_known_table_free(kall[c]);
     free(kall);
     WTRACE("known-variant tables");
-    if (!rc && nr) rc = pf_bam_open(p->bam_path, NULL, &bam);
+    if (!rc && nr) rc = plan_bam_open(p, &bam);
     if (!rc && nr)
         rc = pf_rescue_dropped_multi(bam, nr, rn_names, rn_nd, rn_ds, rn_de, kvs, &tm, p->o.untagged ? &tr : NULL,
                                      p->o.threads > 0 ? p->o.threads : 1, maps);
@@ -1535,7 +1566,7 @@ static int finish_deferred_estimate(pf_mp_plan_t *p, pf_ctx_t *ctx) {
     if (!p->est_deferred) return PF_OK;
     const double t0 = now_s();
     pf_bam_t *bam = NULL;
-    int rc = pf_bam_open(p->bam_path, NULL, &bam);
+    int rc = plan_bam_open(p, &bam);
     if (rc) return rc;
     const int32_t nt = pf_bam_n_targets(bam);
     int32_t *covs = (int32_t *)calloc(nt > 0 ? nt : 1, sizeof(int32_t));
@@ -1661,8 +1692,8 @@ static void *dev_main(void *arg) {
     /* window jobs: the fetch of the next job runs on a helper thread while
      * this thread drives the device on the current one */
     pf_bam_t *bam[2] = {NULL, NULL};
-    rc = pf_bam_open(p->bam_path, NULL, &bam[0]);
-    if (!rc) rc = pf_bam_open(p->bam_path, NULL, &bam[1]);
+    rc = plan_bam_open(p, &bam[0]);
+    if (!rc) rc = plan_bam_open(p, &bam[1]);
     if (!rc && !p->o.host_fetch) {              /* device fetch: host planning + reads, the rest on the GPU */
         while (!rc && next_job(W, &jb)) rc = job_device_fetch(p, W->ctx, bam[0], &p->jobs[jb]);
         pf_bam_close(bam[0]);

@@ -49,7 +49,8 @@ class PfMethphaseOpts(C.Structure):
                 ("rank", C.c_int32), ("world", C.c_int32), ("job_windows", C.c_uint32), ("verbose", C.c_int32),
                 ("host_fetch", C.c_int32), ("interval_path", C.c_char_p), ("interval_format", C.c_int32),
                 ("write_input_tagging", C.c_int32), ("bam_threads", C.c_int32),
-                ("mask_path", C.c_char_p), ("mask_variants", C.c_int32)]
+                ("mask_path", C.c_char_p), ("mask_variants", C.c_int32),
+                ("ref_path", C.c_char_p)]
 
 
 class PfQnameTagsC(C.Structure):
@@ -207,13 +208,15 @@ def make_opts(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg: Opti
               tsv: bool = False, threads: int = 8, n_devices: int = 0, ctxs=None, rank: int = 0, world: int = 1,
               job_windows: int = 0, cov: int = 0, chunk_size: int = 50_000, chunk_stride: int = 1_000_000,
               verbose: int = 0, host_fetch: bool = False, intervals=None, write_input_tagging: bool = False,
-              mask_bed: Optional[str] = None, mask_variants: bool = False):
+              mask_bed: Optional[str] = None, mask_variants: bool = False, ref: Optional[str] = None):
     """pf_methphase_opts_t from Python values.  cfg None: per-contig
     parameters from the BAM's coverage estimate (runs without -c).
     intervals: (path, INTERVALS_GTF | INTERVALS_TSV), the --gtf / --tsv phase
     blocks (vcf_path may then be None unless untagged).  mask_bed /
     mask_variants: --mask-bed / --mask-variants, reference positions no
-    methylation site may lie on (load_mask)."""
+    methylation site may lie on (load_mask).  ref: --ref, a reference FASTA
+    the -u pre-pass and the rescue synthesise MD from (the BAM then needs no
+    MD:Z tags)."""
     lcfg = lcfg or LoadConfig()
     o = PfMethphaseOpts()
     o.mode = mode
@@ -247,6 +250,7 @@ def make_opts(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg: Opti
     o.host_fetch = int(bool(host_fetch))
     o.mask_path = mask_bed.encode() if mask_bed else None
     o.mask_variants = int(bool(mask_variants))
+    o.ref_path = ref.encode() if ref else None
     o._keep = keep
     return o
 
@@ -406,7 +410,7 @@ def methphase_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg
                     untagged: bool = False, tsv: bool = False, n_devices: int = 1, job_windows: int = 0,
                     host_fetch: bool = False, ctxs=None, intervals=None,
                     write_input_tagging: bool = False, mask_bed: Optional[str] = None,
-                    mask_variants: bool = False) -> Dict:
+                    mask_variants: bool = False, ref: Optional[str] = None) -> Dict:
     """`pomfret methphase` over every gap of vcf_path with the reads of
     bam_path, in this process (pf_methphase_main).  Writes out_prefix +
     .mp.gtf / .mp.vcf (and .mp.tsv with tsv=True, the reference's
@@ -420,7 +424,8 @@ def methphase_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg
     INTERVALS_GTF | INTERVALS_TSV): the --gtf / --tsv phase blocks instead of
     the VCF's (vcf_path None: no VCF written); write_input_tagging: -U.
     mask_bed / mask_variants: --mask-bed / --mask-variants; the result's
-    masked_sites counts the sites they removed."""
+    masked_sites counts the sites they removed.  ref: --ref, the reference
+    FASTA MD is synthesised from (a BAM without MD:Z tags)."""
     L = _bind()
     devs = None
     if ctx is not None:
@@ -430,7 +435,7 @@ def methphase_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg
     o = make_opts(bam_path, vcf_path, out_prefix, cfg, lcfg, untagged=untagged, tsv=tsv, threads=threads,
                   n_devices=0 if ctxs else n_devices, ctxs=ctxs or None,
                   job_windows=job_windows, host_fetch=host_fetch, intervals=intervals,
-                  write_input_tagging=write_input_tagging, mask_bed=mask_bed, mask_variants=mask_variants)
+                  write_input_tagging=write_input_tagging, mask_bed=mask_bed, mask_variants=mask_variants, ref=ref)
     if devs is not None:
         o.devices = C.cast(devs, C.c_void_p)
     h = C.c_void_p()
@@ -446,19 +451,20 @@ def report_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cov: i
                  chunk_size: int = 50_000, chunk_stride: int = 1_000_000, lcfg: Optional[LoadConfig] = None,
                  untagged: bool = False, threads: int = 8, ctx=None, n_devices: int = 1, k: int = 3,
                  k_span: int = 5000, host_fetch: bool = False, ctxs=None, mask_bed: Optional[str] = None,
-                 mask_variants: bool = False) -> Dict:
+                 mask_variants: bool = False, ref: Optional[str] = None) -> Dict:
     """`pomfret report` (main_methreport, 4901-5089): chunk windows inside the
     phased blocks, one methphase decision each; writes
     {out_prefix}.report.tsv and the running totals to stdout.  cov: -c
     (0: the per-contig estimate).  mask_bed / mask_variants: --mask-bed /
-    --mask-variants.  Returns dict(decision, counts, n_limit, masked_sites)."""
+    --mask-variants.  ref: --ref (with untagged: MD synthesised from the
+    FASTA).  Returns dict(decision, counts, n_limit, masked_sites)."""
     L = _bind()
     if ctx is not None:
         ctxs = [ctx]
     o = make_opts(bam_path, vcf_path, out_prefix, Config(k=k, k_span=k_span), lcfg, mode=MODE_REPORT,
                   untagged=untagged, threads=threads, n_devices=0 if ctxs else n_devices,
                   ctxs=ctxs or None, cov=cov, chunk_size=chunk_size, chunk_stride=chunk_stride,
-                  host_fetch=host_fetch, mask_bed=mask_bed, mask_variants=mask_variants)
+                  host_fetch=host_fetch, mask_bed=mask_bed, mask_variants=mask_variants, ref=ref)
     h = C.c_void_p()
     _check(L.pf_methphase_main(C.byref(o), C.byref(h)), "pf_methphase_main")
     plan = Plan(o, handle=h)
