@@ -34,6 +34,7 @@
 #include <zlib.h>
 
 #include "../../include/pomfret_amd.h"
+#include "pf_bgzf.h"
 #include "pf_host.h"
 
 /* ------------------------------------------------------------------ */
@@ -63,33 +64,22 @@ static int bgzf_read_raw(bgzf_t *z, uint64_t addr, uint8_t *h, uint32_t *xlen_ou
         if (fseeko(z->f, (off_t)addr, SEEK_SET) != 0) return -1;
         z->fpos = addr;
     }
-    size_t got = fread(h, 1, 18, z->f);
-    z->fpos += got;
-    if (got == 0) return 0;
-    if (got < 12 || h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) return -2;
-    const uint32_t xlen = rd16(h + 10);
-    if (xlen < 6 || 12 + xlen > 65536 + 64) return -2;
-    if (got < 12 + (size_t)xlen) {
-        const size_t k = fread(h + got, 1, 12 + xlen - got, z->f);
+    /* the header rule asks for the bytes it needs (pf_bgzf.h: at most the
+     * block, or a few bytes past a 65535-byte extra field: cbuf holds either) */
+    pf_bgzf_hdr hd = {0, 0};
+    size_t got = 0;
+    for (int need = 18; need > 0;) {
+        const size_t k = fread(h + got, 1, (size_t)need - got, z->f);
         z->fpos += k;
-        if (k != 12 + xlen - got) return -2;
-        got = 12 + xlen;
+        if (got + k == 0) return 0;
+        if (k != (size_t)need - got) return -2;
+        got = (size_t)need;
+        need = pf_bgzf_header(h, got, &hd);
+        if (need == PF_BGZF_MALFORMED) return -2;
     }
-    uint32_t bsize = 0;
-    for (uint32_t x = 0; x + 4 <= xlen;) {
-        const uint8_t *sf = h + 12 + x;
-        const uint32_t slen = rd16(sf + 2);
-        if (sf[0] == 'B' && sf[1] == 'C' && slen == 2) bsize = rd16(sf + 4) + 1;
-        x += 4 + slen;
-    }
-    if (bsize < 12 + xlen + 8 || bsize > 65536) return -2;
-    if (got < bsize) {
-        const size_t k = fread(h + got, 1, bsize - got, z->f);
-        z->fpos += k;
-        if (k != bsize - got) return -2;
-    }
-    *xlen_out = xlen;
-    return (int)bsize;
+    if (hd.xlen < 6) return -2;
+    *xlen_out = hd.xlen;
+    return (int)hd.bsize;
 }
 
 /* libdeflate, when the system has its runtime library (htslib links the same

@@ -115,9 +115,23 @@ typedef struct pf_k4_reads_dev {
     const uint8_t *md;
 } pf_k4_reads_dev;
 #ifdef __cplusplus
+#include <vector>
 struct pf_ctx;
 struct pf_known_vars;
 struct pf_read_aln_batch;
+// the context's device, streams and pinned staging buffer (pf_api.hip)
+extern "C" int pf_ctx_device(const pf_ctx *c);
+extern "C" hipStream_t pf_ctx_stream(const pf_ctx *c);
+extern "C" hipStream_t pf_ctx_stream2(const pf_ctx *c);
+extern "C" hipStream_t pf_ctx_stream3(const pf_ctx *c);
+extern "C" uint8_t *pf_ctx_stage(pf_ctx *c, size_t n);
+extern "C" void pf_ctx_stage_trim(pf_ctx *c, size_t keep);
+// pf_mdsynth.hip: the contig's reference on the context's device, and MD
+// synthesised from the gathered CIGAR / SEQ (pf_k4_mdlen, pf_k4_mdfill)
+int pf_mdsynth_ref_dev(pf_ctx *ctx, const uint8_t *nib, uint64_t len, const uint8_t **d_ref);
+int pf_mdsynth_dev(pf_ctx *ctx, hipStream_t st, uint32_t N, const pf_k4_reads_dev &in, const uint8_t *d_ref,
+                   uint64_t ref_len, std::vector<uint32_t> &md_len, std::vector<uint64_t> &md_off,
+                   std::vector<void *> &al, uint64_t **d_md_off, uint8_t **d_md);
 // prev_left: the reference's prev_i_left cursor (blockjoin.c:1716-1720) going
 // in and coming out, so that a contig haptagged in pieces chains like one
 // call (null: starts at 0)

@@ -206,6 +206,47 @@ def test_errors(tmp_path):
         BamFile(str(bad), p + ".bai")
 
 
+def test_malformed_bgzf_headers(tmp_path):
+    """A file whose first block has a malformed BGZF header is refused at open
+    (the header rule of pf_bgzf.h, here through bgzf_read_raw)."""
+    from _bgzf import bgzf_block, malformed_headers
+    p = str(tmp_path / "e.bam")
+    write_bam(p, [("c", 1000)], [])
+    data = open(p, "rb").read()
+    first = int.from_bytes(data[16:18], "little") + 1
+    good = bgzf_block(b"x" * 1000)
+    for name, blk in [("intact", data[:first])] + malformed_headers(data[:first]):
+        q = tmp_path / "m.bam"
+        q.write_bytes(blk + good + data[first:])
+        if name == "intact":
+            BamFile(str(q), p + ".bai").close()
+            continue
+        with pytest.raises(Exception):
+            BamFile(str(q), p + ".bai")
+            pytest.fail(name)
+
+
+def test_bgzf_header_rule_under_sanitizers(tmp_path):
+    """tests/bgzf_header_check.c, a program of its own: every prefix of a
+    valid header in an allocation of exactly its size, under ASan and UBSan."""
+    import shutil
+    import subprocess
+    cc = shutil.which(os.environ.get("CC", "cc")) or shutil.which("gcc")
+    # (the runtimes linked statically: the program starts whatever the environment preloads)
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan"]
+    probe = tmp_path / "probe.c"
+    probe.write_text("int main(void) { return 0; }\n")
+    if not cc or subprocess.run([cc] + san + [str(probe), "-o", str(tmp_path / "probe")],
+                                capture_output=True).returncode != 0:
+        pytest.skip("the host compiler cannot link the sanitizer runtimes")
+    exe = str(tmp_path / "bgzf_header_check")
+    subprocess.run([cc, "-std=c11", "-O1", "-g", "-Wall", "-Werror"] + san +
+                   ["-I", os.path.join(HERE, "..", "pomfret_amd", "csrc"), os.path.join(HERE, "bgzf_header_check.c"),
+                    "-o", exe], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "ok", r.stdout + r.stderr
+
+
 # ---------------------------------------------------------------- -u ingest
 def _py_known(lines, contig):
     """insert_variant_from_vcf_line (blockjoin.c:1432-1543) restated for the

@@ -146,6 +146,39 @@ def test_device_fetch_record_limit(gpu_ctx, tmp_path):
     assert np.array_equal(got, np.where(per > lim, 0, per))
 
 
+def test_device_fetch_malformed_block(gpu_ctx, tmp_path):
+    """A block with a bad magic byte in the middle of the first window's chunk
+    range (the index is the intact file's): both readers refuse the fetch, and
+    the context's next fetch, from the intact file, is whole -- the error exit
+    left its staging buffer and streams usable."""
+    from pomfret_amd import Config, LoadConfig
+    from pomfret_amd._lib import PomfretError
+    from pomfret_amd.bam import BamFile
+    aln, recs, bam, vcf = tagged(tmp_path, n_windows=2, coverage=20)
+    cfg, lcfg = Config.from_coverage(20, given=False), LoadConfig()
+    data = bytearray(open(bam, "rb").read())
+    with BamFile(bam) as b:
+        ch = b.query_chunks("chrS", int(aln.win_start[0]), int(aln.win_end[0]))
+    lo, hi = int(ch[:, 0].min()) >> 16, int(ch[:, 1].max()) >> 16
+    blocks, o = [], 0
+    while o < len(data):
+        blocks.append(o)
+        o += struct.unpack_from("<H", data, o + 16)[0] + 1
+    inside = [a for a in blocks if lo < a < hi]
+    assert len(inside) >= 3
+    data[inside[len(inside) // 2] + 1] ^= 1
+    bad = str(tmp_path / "bad.bam")
+    open(bad, "wb").write(data)
+    with BamFile(bad, bam + ".bai") as b:
+        with pytest.raises(PomfretError):
+            b.fetch_windows("chrS", aln.win_start, aln.win_end)
+        with pytest.raises(PomfretError):
+            b.fetch_windows_device(gpu_ctx, cfg, "chrS", aln.win_start, aln.win_end, lcfg)
+    host, hqn, hinfo, db, dqn, dinfo = _both(gpu_ctx, bam, "chrS", aln.win_start, aln.win_end, cfg, lcfg)
+    assert host.n_recs > 0 and dinfo["from_arena"] == 0
+    _compare(host, hqn, hinfo, db, dqn, dinfo)
+
+
 @pytest.mark.parametrize("mode", ["tagged", "untagged", "report"])
 def test_pipeline_device_vs_host_fetch(gpu_ctx, tmp_path, mode):
     """The C driver with the device fetch (default) and with --host-fetch:

@@ -10,18 +10,9 @@ import numpy as np
 import pytest
 
 from tests import _bamio
+from tests._bgzf import bgzf_block, malformed_headers
 
 pytestmark = pytest.mark.gpu
-
-
-def bgzf_block(data: bytes, level=6, strategy=zlib.Z_DEFAULT_STRATEGY, mem=8) -> bytes:
-    c = zlib.compressobj(level, zlib.DEFLATED, -15, mem, strategy)
-    z = c.compress(data) + c.flush()
-    bsize = 18 + len(z) + 8
-    if bsize > 65536:                    # htslib shrinks such an input; not a valid block
-        return None
-    hdr = struct.pack("<BBBBIBBHBBHH", 31, 139, 8, 4, 0, 0, 255, 6, 66, 67, 2, bsize - 1)
-    return hdr + z + struct.pack("<II", zlib.crc32(data) & 0xFFFFFFFF, len(data))
 
 
 def payloads(rng):
@@ -97,6 +88,11 @@ def test_inflate_errors(gpu_ctx):
     with pytest.raises(PomfretError):
         gpu_ctx.bgzf_inflate(bytes(junk) + good)
     assert gpu_ctx.last_inflate_status[0] != 0 and gpu_ctx.last_inflate_status[1] == 0
+    # malformed headers: the host's block scan refuses the input
+    for name, bad in malformed_headers(good):
+        with pytest.raises(PomfretError):
+            gpu_ctx.bgzf_inflate(good + bad + good)
+            pytest.fail(name)
 
 
 def test_inflate_throughput(gpu_ctx):

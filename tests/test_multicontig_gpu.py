@@ -313,7 +313,9 @@ def test_untagged_piece_arenas(oracle_lib, gpu_ctx, tmp_path, monkeypatch, shape
     "dense": the 4-contig genome whose regions overlap end to end, so a bound
     falls inside them and the piece before it fetches past the bound over the
     windows starting in it.  Outputs equal the one-piece run, the run without
-    arenas and the oracle pipeline (blockjoin.c:1841-1898, 4350-4426)."""
+    arenas and the oracle pipeline (blockjoin.c:1841-1898, 4350-4426).
+    "separate" then runs twice under an arena budget of half the contig's
+    inflated bytes: 2 of the 4 window fetches hit and 2 miss, in both runs."""
     import os
     from tests import _genome
     from pomfret_amd.pipeline import methphase_files
@@ -342,3 +344,22 @@ def test_untagged_piece_arenas(oracle_lib, gpu_ctx, tmp_path, monkeypatch, shape
     assert st["arena_hits"] == n_fetch and st["arena_misses"] == 0 and st["reread_bytes"] == 0
     assert runs["nocache"][0]["stats"]["arena_hits"] == 0
     assert (ref["decision"] >= 0).sum() >= 2
+    if shape != "separate":
+        return
+    # A budget of half the contig's inflated bytes (PF_ARENA_KEEP_MAX, as
+    # tools/genome_scale.py sets it): some pieces are kept and some are not
+    # (observed: 2 hits, 2 misses, 18,371,950 bytes re-read), and a second run
+    # in the same process does exactly as the first, because the first gave
+    # its whole budget back when it cleared its cache.
+    monkeypatch.delenv("PF_FETCH_CACHE")
+    monkeypatch.setenv("PF_FETCH_PIECE_BYTES", str(piece))
+    monkeypatch.setenv("PF_ARENA_KEEP_MAX", str(st["haptag"]["inflated_bytes"] // 2))
+    capped = []
+    for name in ("cap1", "cap2"):
+        out = str(tmp_path / name)
+        res = methphase_files(g["bam"], g["vcf"], out, None, ctx=gpu_ctx, untagged=True, tsv=True, job_windows=4)
+        assert _outputs(out) == runs["nocache"][1], name
+        capped.append({k: res["stats"][k] for k in ("arena_hits", "arena_misses", "reread_bytes")})
+    print(f"\n[arena budget] inflated {st['haptag']['inflated_bytes']} bytes, half kept: {capped}")
+    assert capped[0]["arena_hits"] > 0 and capped[0]["arena_misses"] > 0
+    assert capped[1] == capped[0]
