@@ -668,6 +668,10 @@ DEV void inflate_blocks(const uint8_t *in, const pf_bgzf_blk *blk, uint32_t nblk
         }
         if (b.over && !err) err = PF_INF_EINPUT;
     }
+    // the stream must end inside the payload: `over` allows for the reader's
+    // look-ahead and the slack dwords, so a stream cut short by a few bytes
+    // would take its last codes from the footer; the exact count, once per block
+    if (!err && 32u * uni(b.rd) - uni(b.cnt) > 8u * ((uint32_t)(in_off & 3u) + in_len)) err = PF_INF_EINPUT;
     if (!err && o.a != o.hi) err = PF_INF_ESIZE;
     // the partial last chunk (bytes below o.a only)
     if (o.a > o.cb) out_flush(o, lane);
