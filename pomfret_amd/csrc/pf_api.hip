@@ -34,7 +34,8 @@ __global__ void pf_k0_load(pf_load_dev d);
 __global__ void pf_k0_multi(pf_load_dev d);
 __global__ void pf_k0_scan(pf_load_dev d);
 __global__ void pf_k0_pack(pf_load_dev d);
-__global__ void pf_k0_pack_small(pf_load_dev d);
+__global__ void pf_k0_gather_calls(const uint64_t *src_off, const uint64_t *dst_off, uint32_t R, const uint32_t *spos,
+                                   const uint8_t *scat, uint32_t *dpos, uint8_t *dcat);
 __global__ void pf_selftest_div(unsigned long long *bad);
 __global__ void pf_selftest_wave(unsigned long long *bad);
 
@@ -51,7 +52,7 @@ __global__ void pf_selftest_wave(unsigned long long *bad);
 // kernel timing slots: "pf_k0_pack" is the scan + pack pair
 static const char *k_names[PF_NKERN] = {"pf_k0_load", "pf_k0_pack", "pf_k12_sites_methmers", "pf_k12_chunks",
                                         "pf_k2_methmers", "pf_k3_wave", "pf_k3_fallback"};
-#define PF_GROWABLE (PF_ST_KEYS_OVF | PF_ST_BIG_OVF | PF_ST_SCR_OVF | PF_ST_STAGE_OVF | PF_ST_CALL_OVF | PF_ST_SITES_OVF)
+#define PF_GROWABLE (PF_ST_KEYS_OVF | PF_ST_BIG_OVF | PF_ST_SCR_OVF | PF_ST_STAGE_OVF | PF_ST_SITES_OVF)
 
 struct pf_ctx {
     int device;
@@ -135,6 +136,12 @@ struct pf_dbatch {
     pf_load_dev ld;
     std::vector<uint32_t> h_rec_of_read;
     unsigned long long *k0_ctr = nullptr;
+    int stage_fill = -1;                     // PF_TEST_STAGE_FILL: the byte the staging arrays start from (tests)
+    // pf_batch_debug_calls' gathered copy of the calls (record level), allocated on first use
+    uint64_t *dbg_off = nullptr;
+    uint32_t *dbg_pos = nullptr;
+    uint8_t *dbg_cat = nullptr;
+    uint64_t dbg_cap = 0;
 };
 
 // views of one host slot of the I/O block
@@ -415,6 +422,18 @@ static void free_arena(pf_dbatch *b, void *p) {
         if (b->allocs[i] == p) { (void)hipFree(p); b->allocs.erase(b->allocs.begin() + i); return; }
 }
 
+// PF_TEST_STAGE_FILL=<byte> (tests): K0's staging arrays start from that byte
+// after their allocation and after a growth.  The slices' slack (unused
+// tails, filtered records' slices) is otherwise uninitialised memory; a run
+// whose results do not depend on the byte reads none of it.
+static int stage_test_fill(pf_dbatch *b) {
+    if (b->stage_fill < 0) return PF_OK;
+    const pf_load_dev &ld = b->ld;
+    HIPCHK(hipMemsetAsync(ld.stage_pos, b->stage_fill, 4ull * ld.stage_cap, b->ctx->stream));
+    HIPCHK(hipMemsetAsync(ld.stage_cat, b->stage_fill, ld.stage_cap, b->ctx->stream));
+    return PF_OK;
+}
+
 extern "C" void pf_batch_free(pf_dbatch_t *b) {
     if (!b) return;
     (void)hipSetDevice(b->ctx->device);
@@ -530,8 +549,9 @@ extern "C" int pf_batch_upload(pf_ctx_t *ctx, const pf_cfg_t *cfg, const pf_wind
 // Allocate and fill the device side of a batch.  Calls level: everything from
 // `in`.  Record level (win_calls != NULL): `in` holds the windows' records
 // (win_read_off = records per window, which also orders the greedy problems)
-// and b->R / b->N are capacities; the read, call and site arrays are only
-// allocated -- K0, scan and pack fill them on every run -- and the site
+// and b->R / b->N are capacities; the read and site arrays are only
+// allocated -- K0, scan and pack fill them on every run; the calls stay in
+// K0's staging arrays, which become the batch's call arrays -- and the site
 // slots are sized from win_calls, an upper bound of each window's calls.
 // The main greedy kernel's largest dynamic LDS that still holds four
 // problems per CU (its 128 VGPRs allow four waves per SIMD): a quarter of the
@@ -620,8 +640,15 @@ static int batch_build(pf_dbatch *b, const pf_window_batch_t *in, const uint32_t
         PUTA(p, aln ? nullptr : read_win.data(), R); d.read_win = p;
         uint8_t *bp; PUTA(bp, in->read_hp, R); d.read_hp = bp;
         PUTA(up, in->read_call_off, R + 1); d.read_call_off = up;
-        PUTA(p, cpos, N); d.call_pos = p;
-        PUTA(bp, ccat, N); d.call_cat = bp;
+        if (aln) {
+            // record level: the pack writes each read's range in K0's staging
+            // arrays, which pf_aln_build makes the batch's call arrays
+            ALLOC(up, R); d.read_call_end = up;
+        } else {
+            d.read_call_end = d.read_call_off + 1;           // one contiguous run in read order
+            PUT(p, cpos, N); d.call_pos = p;
+            PUT(bp, ccat, N); d.call_cat = bp;
+        }
         // greedy problems heaviest first (reads per window, direction 1 --
         // the longer chains -- first on ties): the first wave of workgroups
         // spreads the long chains over distinct CUs and pairs them with the
@@ -988,6 +1015,9 @@ extern "C" int pf_aln_build(pf_ctx_t *ctx, const pf_cfg_t *cfg, const pf_load_cf
         uint64_t *p64; PUT(p64, so_.data(), n + 1); ld.stage_off = p64;
         uint32_t *p32; ALLOC(p32, ld.stage_cap); ld.stage_pos = p32;
         uint8_t *p8; ALLOC(p8, ld.stage_cap); ld.stage_cat = p8;
+        const char *sf = getenv("PF_TEST_STAGE_FILL");
+        b->stage_fill = sf ? (atoi(sf) & 255) : -1;
+        if ((rc = stage_test_fill(b))) return fail(rc);
         // K0's per-slot record rows (the wave slots' order: longest first)
         std::vector<uint32_t> ordh(n);
         for (uint32_t r = 0; r < n; r++) ordh[r] = r;
@@ -1032,7 +1062,6 @@ extern "C" int pf_aln_build(pf_ctx_t *ctx, const pf_cfg_t *cfg, const pf_load_cf
     ld.n_windows = W;
     ld.status = d.status;
     ld.io = b->io;
-    ld.call_cap = b->N;
     ld.sites_cap = b->site_total;
     ld.win_read_off = const_cast<uint32_t *>(d.win_read_off);
     ld.io_win_read_off = reinterpret_cast<uint32_t *>(b->io + b->o_wro);
@@ -1048,8 +1077,9 @@ extern "C" int pf_aln_build(pf_ctx_t *ctx, const pf_cfg_t *cfg, const pf_load_cf
     ld.read_hp = const_cast<uint8_t *>(d.read_hp);
     ld.hp_raw = b->io + b->o_hpraw;
     ld.read_call_off = const_cast<uint64_t *>(d.read_call_off);
-    ld.call_pos = const_cast<uint32_t *>(d.call_pos);
-    ld.call_cat = const_cast<uint8_t *>(d.call_cat);
+    ld.read_call_end = const_cast<uint64_t *>(d.read_call_end);
+    d.call_pos = ld.stage_pos;                  // K12 reads the calls where K0 staged them
+    d.call_cat = ld.stage_cat;
     ld.stage_ctr = reinterpret_cast<unsigned long long *>(b->io + PF_IO_STAGE);
     ld.multi_ctr = reinterpret_cast<uint32_t *>(b->io + 96);
     b->N = 0;                                   // calls: known once a run has finished
@@ -1224,11 +1254,10 @@ static int enqueue(pf_dbatch *b, int slot, int stages = 3) {
     }
     HIPCHK(hipEventRecord(b->ev[slot][1], st));
     if (b->has_aln) {
-        // window offsets, then the batch's read and call arrays
+        // window offsets, then the batch's read arrays and call ranges
         hipLaunchKernelGGL(pf_k0_scan, dim3(1), dim3(PF_SCAN_THREADS), 0, st, b->ld);
         HIPCHK(hipGetLastError());
-        if (b->W >= PF_PACK_PIPE_MIN) hipLaunchKernelGGL(pf_k0_pack, dim3(b->W), dim3(PF_PACK_THREADS), 0, st, b->ld);
-        else hipLaunchKernelGGL(pf_k0_pack_small, dim3(b->W), dim3(PF_PACK_THREADS), 0, st, b->ld);
+        hipLaunchKernelGGL(pf_k0_pack, dim3(b->W), dim3(PF_PACK_THREADS), 0, st, b->ld);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(b->ev[slot][2], st));
@@ -1367,13 +1396,12 @@ static int grow_for(pf_dbatch *b, uint32_t stt, const IoView &v) {
         const uint64_t cap = std::max<uint64_t>(need + v.stage / 8 + 4096, ld.stage_cap + (ld.stage_cap - base));
         rc = realloc_arr(b, &ld.stage_pos, cap);
         if (!rc) rc = realloc_arr(b, &ld.stage_cat, cap);
-        if (!rc) ld.stage_cap = cap;
-    }
-    if (!rc && (stt & PF_ST_CALL_OVF)) {
-        const uint64_t cap = v.N + v.N / 8 + 4096;
-        rc = realloc_arr(b, &ld.call_pos, cap);
-        if (!rc) rc = realloc_arr(b, &ld.call_cat, cap);
-        if (!rc) { d.call_pos = ld.call_pos; d.call_cat = ld.call_cat; ld.call_cap = cap; }
+        if (!rc) {
+            ld.stage_cap = cap;
+            d.call_pos = ld.stage_pos;          // the batch's call arrays are the staging arrays
+            d.call_cat = ld.stage_cat;
+            rc = stage_test_fill(b);
+        }
     }
     if (!rc && (stt & PF_ST_SITES_OVF)) {
         const uint64_t cap = v.sites + v.sites / 8 + 1024;
@@ -1628,10 +1656,41 @@ extern "C" int64_t pf_batch_debug_calls(pf_dbatch_t *b, uint64_t *call_off, uint
     if (rc) return rc;
     if (b->N > cap) return PF_ERR_ARG;
     if (b->R == 0) { call_off[0] = 0; return 0; }
-    HIPCHK(hipMemcpy(call_off, b->d.read_call_off, 8ull * (b->R + 1), hipMemcpyDeviceToHost));
+    const uint32_t *dpos = b->d.call_pos;
+    const uint8_t *dcat = b->d.call_cat;
+    if (b->has_aln) {
+        // record level: the calls lie in K0's staging slices; this hook (and
+        // no timed path) gathers them into one run in read order, with the
+        // prefix sums of the reads' call counts as offsets
+        std::vector<uint64_t> beg(b->R), end(b->R);
+        HIPCHK(hipMemcpy(beg.data(), b->d.read_call_off, 8ull * b->R, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(end.data(), b->d.read_call_end, 8ull * b->R, hipMemcpyDeviceToHost));
+        call_off[0] = 0;
+        for (uint32_t r = 0; r < b->R; r++) call_off[r + 1] = call_off[r] + (end[r] - beg[r]);
+        if (call_off[b->R] != b->N) return PF_ERR_INTERNAL;
+        if (b->dbg_cap < b->N || !b->dbg_off) {
+            if (b->dbg_off) { free_arena(b, b->dbg_off); free_arena(b, b->dbg_pos); free_arena(b, b->dbg_cat); }
+            b->dbg_off = nullptr; b->dbg_pos = nullptr; b->dbg_cat = nullptr; b->dbg_cap = 0;
+            int ra = dev_alloc(b, &b->dbg_off, (size_t)b->ld.n_recs + 1);
+            if (!ra) ra = dev_alloc(b, &b->dbg_pos, (size_t)b->N);
+            if (!ra) ra = dev_alloc(b, &b->dbg_cat, (size_t)b->N);
+            if (ra) return ra;
+            b->dbg_cap = b->N;
+        }
+        hipStream_t st = b->ctx->stream;
+        HIPCHK(hipMemcpyAsync(b->dbg_off, call_off, 8ull * (b->R + 1), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(pf_k0_gather_calls, dim3(std::min<uint32_t>((b->R + 3) / 4, 4096)), dim3(256), 0, st,
+                           b->d.read_call_off, b->dbg_off, b->R, b->d.call_pos, b->d.call_cat, b->dbg_pos, b->dbg_cat);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(st));
+        dpos = b->dbg_pos;
+        dcat = b->dbg_cat;
+    } else {
+        HIPCHK(hipMemcpy(call_off, b->d.read_call_off, 8ull * (b->R + 1), hipMemcpyDeviceToHost));
+    }
     if (b->N) {
-        HIPCHK(hipMemcpy(pos, b->d.call_pos, 4ull * b->N, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(cat, b->d.call_cat, b->N, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(pos, dpos, 4ull * b->N, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(cat, dcat, b->N, hipMemcpyDeviceToHost));
     }
     if (b->R) {
         HIPCHK(hipMemcpy(first, b->d.read_first, 4ull * b->R, hipMemcpyDeviceToHost));

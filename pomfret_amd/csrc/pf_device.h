@@ -4,9 +4,13 @@
  * HBM layout of one resident batch (all SoA, one allocation per array):
  *   windows : win_start/win_end/win_read_off/win_par          [W]
  *   reads   : read_start/end/first/last/win, read_hp           [R]
- *             read_call_off                                     [R+1]
- *   calls   : call_pos (u32), call_cat (u8)                     [N]
- *             calls of a read sorted by (pos, cat)
+ *             read_call_off, read_call_end                      [R]
+ *   calls   : call_pos (u32), call_cat (u8)
+ *             read r's calls are [read_call_off[r], read_call_end[r]),
+ *             sorted by (pos, cat).  A calls-level batch holds them as one
+ *             run of N in read order (read_call_end = read_call_off + 1); a
+ *             record-level batch reads them where K0 staged them (pf_load.h),
+ *             in no order across reads and with unused slots between them
  *   sites   : per window a slice [site_off[w], +site_cap[w]) of
  *             site_pos, st1_pos, site_q1 (u32) and len0, len1 (u8)
  *   methmers: per (read, dir) a slice of the key arena (u32): methmer keys,
@@ -55,7 +59,7 @@ struct pf_dev_batch {
     /* reads */
     const uint32_t *read_start, *read_end, *read_first, *read_last, *read_win;
     const uint8_t *read_hp;
-    const uint64_t *read_call_off;
+    const uint64_t *read_call_off, *read_call_end;   /* read r's calls: [off[r], end[r]) */
     /* calls */
     const uint32_t *call_pos;
     const uint8_t *call_cat;

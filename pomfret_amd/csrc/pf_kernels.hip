@@ -419,7 +419,7 @@ DEV void k2_calls_sites(K2Calls &cl, const uint32_t *sp, uint32_t S, const K2Sit
 
 DEV void k2_load_scalars(const pf_dev_batch &d, uint32_t r, K2Read &rd) {
     rd.c0 = d.read_call_off[r];
-    rd.c1 = d.read_call_off[r + 1];
+    rd.c1 = d.read_call_end[r];
     rd.F = d.read_first[r];
     rd.L = d.read_last[r];
     rd.cap = d.mmr_cap[r];
@@ -615,7 +615,7 @@ __global__ __launch_bounds__(PF_K2_WAVES * 64) void pf_k2_methmers(pf_dev_batch 
         const uint64_t bo = d.big_off[r];
         K2Read rd;
         rd.c0 = d.read_call_off[r];
-        rd.c1 = d.read_call_off[r + 1];
+        rd.c1 = d.read_call_end[r];
         rd.F = d.read_first[r];
         rd.L = d.read_last[r];
         rd.cap = d.mmr_cap[r];
@@ -739,6 +739,80 @@ DEV void k12_methmers(const pf_dev_batch &d, uint32_t r0, uint32_t i0, uint32_t 
 // K12: sites + directional methmer ranges + end-order + arena reservation,
 // then every read's methmers (both directions) from LDS-resident site arrays
 // ========================================================================
+// K12's passes over every call of a window.  Read r's calls are one run
+// [read_call_off[r], read_call_end[r]), but the runs of a window's reads need
+// not be adjacent (a record-level batch reads them in K0's staging slices,
+// pf_load.h), so the passes walk read by read: wave wid of NW takes the reads
+// wid, wid + NW, ...  The ranges of the wave's next 64 reads sit one per lane
+// and are read back by readlane, so the walk is scalar and no load inside it
+// depends on another.  A round first lays out PF_K12_CU groups of 64 calls in
+// the walk's order (where the current read ends inside a group, the group's
+// upper lanes take the next read's first calls, so lanes idle only where a
+// read is shorter than the rest of a group), then issues every group's (cat,
+// pos) loads, then hands them to f.  The loads are unconditional -- a lane
+// without a call loads slot 0 and is given cat 2 (neither meth nor unmeth,
+// which every pass skips) afterwards -- so that no branch on a loaded value
+// sits between two groups' loads.  f(cat, pos) runs in whole waves.
+#ifndef PF_K12_CU
+#define PF_K12_CU 4
+#endif
+template <typename F>
+DEV void k12_each_call(const pf_dev_batch &d, uint32_t r0, uint32_t R, uint32_t wid, uint32_t NW, uint32_t lane,
+                       F &&f) {
+    constexpr uint32_t U = PF_K12_CU;
+    const uint32_t wu = (uint32_t)__builtin_amdgcn_readfirstlane((int)wid);
+    for (uint32_t ib = wu; ib < R; ib += 64 * NW) {
+        const uint32_t i = ib + lane * NW;
+        uint32_t blo = 0, bhi = 0, n = 0;
+        if (i < R) {
+            const uint64_t b = d.read_call_off[r0 + i];
+            blo = (uint32_t)b;
+            bhi = (uint32_t)(b >> 32);
+            n = (uint32_t)(d.read_call_end[r0 + i] - b);     // a window's calls fit u32
+        }
+        const uint32_t cnt = min(64u, (R - ib + NW - 1) / NW);   // this wave's reads of this round
+        auto range = [&](uint32_t j, uint64_t &b, uint32_t &m) {  // of the read in lane j (none: empty)
+            const uint32_t jj = min(j, 63u);
+            b = ((uint64_t)rdl(bhi, jj) << 32) | rdl(blo, jj);
+            m = j < cnt ? rdl(n, jj) : 0u;
+        };
+        uint32_t j = 0, o = 0, cn, nn;                           // the current read's lane, its calls already taken
+        uint64_t cb, nb;
+        range(0, cb, cn);
+        range(1, nb, nn);
+        while (j < cnt) {
+            uint64_t c[U];
+            bool ok[U];
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                const uint32_t rem = cn - o;                     // lanes [0, rem): the current read
+                const bool cur = lane < rem;
+                const uint32_t l2 = lane - rem;                  // the rest: the next read's first calls
+                ok[u] = cur || l2 < nn;
+                c[u] = !ok[u] ? 0ull : cur ? cb + o + lane : nb + l2;
+                if (rem > 64) {
+                    o += 64;
+                } else {
+                    // the current read is done: the next one becomes current, behind the calls just taken
+                    o = min(64u - rem, nn);
+                    j++;
+                    cb = nb;
+                    cn = nn;
+                    range(j + 1, nb, nn);
+                }
+            }
+            uint32_t cat[U], pos[U];
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) {
+                cat[u] = d.call_cat[c[u]];
+                pos[u] = d.call_pos[c[u]];
+            }
+#pragma unroll
+            for (uint32_t u = 0; u < U; u++) f(ok[u] ? cat[u] : 2u, pos[u]);
+        }
+    }
+}
+
 // first index in [lo, hi) of the ascending p whose value is >= x (hi: none)
 __device__ __forceinline__ uint32_t mask_lower(const uint32_t *p, uint32_t lo, uint32_t hi, uint32_t x) {
     while (lo < hi) {
@@ -778,10 +852,11 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
             const uint32_t hp = d.read_hp[r];
             if (hp < 2) atomicAdd(&sh_misc[hp], 1u);
         }
-        const uint64_t c0 = d.read_call_off[r], c1 = d.read_call_off[r + 1];
+        const uint64_t c0 = d.read_call_off[r], c1 = d.read_call_end[r];
         if (c1 > c0) {
             atomicMin(&sh_misc[2], d.call_pos[c0]);
             atomicMax(&sh_misc[3], d.call_pos[c1 - 1]);
+            atomicAdd(&sh_misc[7], (uint32_t)(c1 - c0));     // the window's calls (they fit u32)
         }
     }
     __syncthreads();
@@ -830,9 +905,7 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
     const bool range_ok = nseg >= 1 && nseg <= MAXSEG;
     bool fast = range_ok;
     [[maybe_unused]] uint32_t rep_seen = 0;             // the profile's dense-path reason
-    // the window's calls are one contiguous run: flat passes, four
-    // independent (cat, pos) loads in flight per thread
-    const uint64_t C0 = d.read_call_off[r0], C1 = d.read_call_off[r0 + R];
+    // the passes over the window's calls go read by read (k12_each_call)
     // Pass A marks in bmap the positions with >= 2 meth/unmeth calls: a site
     // needs >= cov_sel calls of each kind, so no other position can qualify.
     // Pass B counts only those.  Sequencing errors put CpG calls at positions
@@ -844,24 +917,13 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
             uint64_t *once = reinterpret_cast<uint64_t *>(tile);   // the first half of the tile
             for (uint32_t j = tid; j < BW; j += NT) { once[j] = 0; bmap[j] = 0; }
             __syncthreads();
-            for (uint64_t cb = C0 + tid; cb < C1; cb += 4ull * NT) {
-                uint32_t cat4[4], pos4[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const uint64_t c = cb + (uint64_t)u * NT;
-                    const bool ok = c < C1;
-                    cat4[u] = ok ? d.call_cat[c] : 2u;
-                    pos4[u] = ok ? d.call_pos[c] : 0u;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    const uint32_t o = pos4[u] - base;
-                    if (cat4[u] >= 2 || o >= SEGB) continue;
-                    const unsigned long long bit = 1ull << (o & 63);
-                    if (atomicOr((unsigned long long *)&once[o >> 6], bit) & bit)
-                        atomicOr((unsigned long long *)&bmap[o >> 6], bit);
-                }
-            }
+            k12_each_call(d, r0, R, wid, NW, lane, [&](uint32_t cat, uint32_t pos) {
+                const uint32_t o = pos - base;
+                if (cat >= 2 || o >= SEGB) return;
+                const unsigned long long bit = 1ull << (o & 63);
+                if (atomicOr((unsigned long long *)&once[o >> 6], bit) & bit)
+                    atomicOr((unsigned long long *)&bmap[o >> 6], bit);
+            });
             __syncthreads();
         }
         // more repeated positions than counters: the dense path
@@ -890,26 +952,15 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
         }
         for (uint32_t j = tid; j < rep_tot; j += NT) rcnt[j] = 0;
         __syncthreads();
-        for (uint64_t cb = C0 + tid; cb < C1; cb += 4ull * NT) {
-            uint32_t cat4[4], pos4[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint64_t c = cb + (uint64_t)u * NT;
-                const bool ok = c < C1;
-                cat4[u] = ok ? d.call_cat[c] : 2u;
-                pos4[u] = ok ? d.call_pos[c] : 0u;
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const uint32_t o = pos4[u] - base;
-                if (cat4[u] >= 2 || o >= SEGB) continue;
-                const uint64_t bits = bmap[o >> 6];
-                const uint64_t below = (1ull << (o & 63)) - 1ull;
-                if (!((bits >> (o & 63)) & 1ull)) continue;
-                const uint32_t ix = (uint32_t)wrank[o >> 6] + (uint32_t)__popcll(bits & below);
-                atomicAdd(&rcnt[ix], cat4[u] == 0 ? 1u : 0x10000u);
-            }
-        }
+        k12_each_call(d, r0, R, wid, NW, lane, [&](uint32_t cat, uint32_t pos) {
+            const uint32_t o = pos - base;
+            if (cat >= 2 || o >= SEGB) return;
+            const uint64_t bits = bmap[o >> 6];
+            const uint64_t below = (1ull << (o & 63)) - 1ull;
+            if (!((bits >> (o & 63)) & 1ull)) return;
+            const uint32_t ix = (uint32_t)wrank[o >> 6] + (uint32_t)__popcll(bits & below);
+            atomicAdd(&rcnt[ix], cat == 0 ? 1u : 0x10000u);
+        });
         __syncthreads();
         // bmap becomes the qualifying bitmap, each thread over its own words
         // counts are uint16 holding count<<4 in the reference: count mod 4096 (blockjoin.c:3236)
@@ -993,7 +1044,7 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
         constexpr uint32_t CHB = 14, CH = 1u << CHB, MAXCH = 8191;
         static_assert(CH + 2 * (MAXCH + 1) <= PF_K1_TILE, "chunk counters + chunk offsets fit the tile");
         uint32_t *ccnt = tile, *coff = tile + CH, *cfill = coff + MAXCH + 1;
-        const uint64_t ncall = C1 - C0;
+        const uint64_t ncall = sh_misc[7];
         const uint64_t need = (2ull * ncall + 15) & ~15ull;
         if (tid == 0) {
             const unsigned long long o = atomicAdd(d.scr_ctr, (unsigned long long)need);
@@ -1014,7 +1065,7 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
             uint16_t *sc = reinterpret_cast<uint16_t *>(d.scr + so);
             const uint32_t span = pmax - pmin + 1;
             // one wave-aggregated LDS add per distinct chunk among the lanes
-            // (a wave's 64 consecutive calls are mostly one read's, 1-2 chunks)
+            // (a wave's 64 consecutive calls are one read's, 1-2 chunks)
             auto chunk_add = [&](bool act, uint32_t ch, uint32_t *ctr, bool ret) -> uint32_t {
                 uint32_t mine = 0;
                 uint64_t todo = __ballot(act);
@@ -1033,28 +1084,17 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
                 }
                 return mine;
             };
-            const uint64_t cend4 = C0 + (ncall + 4 * NT - 1) / (4 * NT) * (4 * NT);   // whole waves in every pass
             for (uint64_t sup = 0; sup < span; sup += (uint64_t)MAXCH << CHB) {
                 const uint32_t nch = (uint32_t)min<uint64_t>((span - sup + CH - 1) >> CHB, MAXCH);
                 const uint64_t slim = min<uint64_t>((uint64_t)nch << CHB, span - sup);
                 for (uint32_t j = tid; j <= nch; j += NT) { coff[j] = 0; cfill[j] = 0; }
                 __syncthreads();
-                // A: calls per chunk (four calls per thread per step, loads first)
-                for (uint64_t c0 = C0 + tid; c0 < cend4; c0 += 4ull * NT) {
-                    uint32_t cat4[4], pos4[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const uint64_t c = c0 + (uint64_t)u * NT;
-                        cat4[u] = c < C1 ? d.call_cat[c] : 2u;
-                        pos4[u] = c < C1 ? d.call_pos[c] : pmin;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const uint64_t rel = (uint64_t)(pos4[u] - pmin) - sup;
-                        const bool act = cat4[u] < 2 && rel < slim;
-                        chunk_add(act, act ? (uint32_t)(rel >> CHB) : 0u, coff, false);
-                    }
-                }
+                // A: calls per chunk (whole waves: chunk_add's ballots)
+                k12_each_call(d, r0, R, wid, NW, lane, [&](uint32_t cat, uint32_t pos) {
+                    const uint64_t rel = (uint64_t)(pos - pmin) - sup;
+                    const bool act = cat < 2 && rel < slim;
+                    chunk_add(act, act ? (uint32_t)(rel >> CHB) : 0u, coff, false);
+                });
                 __syncthreads();
                 // chunk offsets (exclusive scan, 8 chunks per thread)
                 {
@@ -1069,23 +1109,13 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
                 }
                 __syncthreads();
                 // C: scatter the calls into their chunks' lists
-                for (uint64_t c0 = C0 + tid; c0 < cend4; c0 += 4ull * NT) {
-                    uint32_t cat4[4], pos4[4];
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const uint64_t c = c0 + (uint64_t)u * NT;
-                        cat4[u] = c < C1 ? d.call_cat[c] : 2u;
-                        pos4[u] = c < C1 ? d.call_pos[c] : pmin;
-                    }
-#pragma unroll
-                    for (int u = 0; u < 4; u++) {
-                        const uint64_t rel = (uint64_t)(pos4[u] - pmin) - sup;
-                        const bool act = cat4[u] < 2 && rel < slim;
-                        const uint32_t ch = act ? (uint32_t)(rel >> CHB) : 0u;
-                        const uint32_t slot = chunk_add(act, ch, cfill, true);
-                        if (act) sc[coff[ch] + slot] = (uint16_t)(((uint32_t)rel & (CH - 1)) | (cat4[u] << 15));
-                    }
-                }
+                k12_each_call(d, r0, R, wid, NW, lane, [&](uint32_t cat, uint32_t pos) {
+                    const uint64_t rel = (uint64_t)(pos - pmin) - sup;
+                    const bool act = cat < 2 && rel < slim;
+                    const uint32_t ch = act ? (uint32_t)(rel >> CHB) : 0u;
+                    const uint32_t slot = chunk_add(act, ch, cfill, true);
+                    if (act) sc[coff[ch] + slot] = (uint16_t)(((uint32_t)rel & (CH - 1)) | (cat << 15));
+                });
                 __threadfence();                         // the lists are read back through L2 (L1 invalidated)
                 __syncthreads();
                 // D: each chunk counted in LDS, scanned in position order
@@ -1241,7 +1271,7 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
         uint32_t bound = 0, bigb = 0;
         if (i < R) {
             const uint32_t r = r0 + i;
-            const uint64_t c0 = d.read_call_off[r], c1 = d.read_call_off[r + 1];
+            const uint64_t c0 = d.read_call_off[r], c1 = d.read_call_end[r];
             if (c1 > c0 && S > 0) {
                 const uint32_t F = d.read_first[r], L = d.read_last[r];
                 const uint64_t lbF = lb_u32(a, 0, S, F), ubL = ub_u32(a, 0, S, L);

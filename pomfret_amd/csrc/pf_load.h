@@ -16,8 +16,9 @@
  *         grows the arrays and re-runs);
  *   pack  one workgroup per window: kept records -> read indices in record
  *         order (the reference's rs->a order), the batch's read arrays, and
- *         each read's calls copied from its staging slice to the window's
- *         contiguous run.
+ *         each read's call range [begin, end) in the staging arena.  No call
+ *         is copied: K12 and its helpers read the staging slices in place
+ *         (the batch's call_pos / call_cat are the staging arrays).
  * No count pass and no host round trip sit between the records and K12.
  */
 #ifndef PF_LOAD_H
@@ -30,13 +31,6 @@
 #define PF_K0_EC (PF_K0_CB / 2)   /* explicit / implicit calls per chunk (CpGs are >= 2 apart) */
 #define PF_K0_SEQ_ALIGN 16        /* per-record SEQ slices are 16-byte aligned and padded */
 #define PF_PACK_THREADS 1024
-/* pf_k0_pack's pipelined copy pays in batches that fill the device with pack
- * workgroups (a 1024-window batch: 0.755 -> 0.628 ms); in the 512-window
- * batches of an 8-GPU rank its 256-call chunks lost (the N=8 step 12.63 ->
- * 13.0 ms), so smaller batches run pf_k0_pack_small (512-call chunks) */
-#ifndef PF_PACK_PIPE_MIN
-#define PF_PACK_PIPE_MIN 768u
-#endif
 #define PF_SCAN_THREADS 1024
 
 /* status bits of K0 and the pack step (share the batch status word with
@@ -44,7 +38,7 @@
 #define PF_ST_FATAL_CIGAR 32u     /* H/=/X/P/... reached in the CIGAR walk: exit(1) at 776-779 */
 #define PF_ST_POS_LIMIT   64u     /* a call position >= 2^29 */
 #define PF_ST_STAGE_OVF  128u     /* K0's call staging arena is too small (grow, re-run) */
-#define PF_ST_CALL_OVF   256u     /* the batch call arrays are too small (grow, re-run) */
+/* 256u was PF_ST_CALL_OVF: the batch has no call arrays of its own to overflow */
 #define PF_ST_SITES_OVF  512u     /* the batch site arrays are too small (grow, re-run) */
 #define PF_ST_MM_LIMIT  1024u     /* a record's MM tag has more than PF_K0_MAXT (8) C m entries */
 
@@ -118,9 +112,9 @@ struct pf_load_dev {
     unsigned long long *ctr;         /* PF_K0_NCTR */
     uint32_t *multi_list;            /* [n_recs] wave slots of records with several C m entries (pf_k0_multi) */
     uint32_t *multi_ctr;             /* their count (I/O block header, zeroed per run) */
-    /* scan + pack output: the batch's window / read / call arrays */
+    /* scan + pack output: the batch's window / read arrays */
     uint8_t *io;                     /* I/O block (header totals, bump pointer) */
-    uint64_t call_cap, sites_cap;
+    uint64_t sites_cap;
     uint32_t *win_read_off;          /* [W+1] device copy the kernels read */
     uint32_t *io_win_read_off;       /* [W+1] I/O block copy for the host epilogue */
     uint64_t *win_site_off;          /* [W] */
@@ -130,9 +124,8 @@ struct pf_load_dev {
     uint32_t *read_start, *read_end, *read_first, *read_last, *read_win;
     uint32_t *read_rec;              /* [R] record of each read (I/O block) */
     uint8_t *read_hp, *hp_raw;       /* read_hp: the kernels' copy; hp_raw: the I/O block's */
-    uint64_t *read_call_off;         /* [R+1] */
-    uint32_t *call_pos;
-    uint8_t *call_cat;
+    uint64_t *read_call_off;         /* [R] each read's calls in the staging arena: begin ... */
+    uint64_t *read_call_end;         /* [R] ... and end (begin + the record's calls) */
 };
 
 #ifdef __cplusplus

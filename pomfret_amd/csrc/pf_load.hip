@@ -116,14 +116,6 @@ DEV unsigned long long k0_now() {
 #ifndef PF_K0_RANKDPP
 #define PF_K0_RANKDPP 1
 #endif
-// pack (round 6): 1 = each wave's next 512-call chunk loaded before the
-// current chunk is stored
-#ifndef PF_PACK_PIPE
-#define PF_PACK_PIPE 1
-#endif
-#ifndef PF_PACK_U
-#define PF_PACK_U 4                        // calls per lane per chunk of the pipelined pack
-#endif
 // MM entries (round 6): 1 = a one-code header ("C+m?") parsed from one
 // 4-byte window instead of byte by byte
 #ifndef PF_K0_HDRFAST
@@ -1834,15 +1826,14 @@ __global__ __launch_bounds__(PF_SCAN_THREADS) void pf_k0_scan(pf_load_dev d) {
         sc += ts;
     }
     const uint32_t st = __hip_atomic_load(d.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool c_ovf = cc > d.call_cap, s_ovf = sc > d.sites_cap;
-    const bool empty = c_ovf || s_ovf || (st & (PF_ST_STAGE_OVF | PF_ST_FATAL_CIGAR | PF_ST_POS_LIMIT));
+    const bool s_ovf = sc > d.sites_cap;
+    const bool empty = s_ovf || (st & (PF_ST_STAGE_OVF | PF_ST_FATAL_CIGAR | PF_ST_POS_LIMIT));
     if (tid == 0) {
         d.win_read_off[W] = rc;
         d.win_call_off[W] = cc;
         *reinterpret_cast<uint32_t *>(d.io + PF_IO_R) = rc;
         *reinterpret_cast<uint64_t *>(d.io + PF_IO_N) = cc;
         *reinterpret_cast<uint64_t *>(d.io + PF_IO_SITES) = sc;
-        if (c_ovf) atomicOr(d.status, PF_ST_CALL_OVF);
         if (s_ovf) atomicOr(d.status, PF_ST_SITES_OVF);
     }
     __syncthreads();
@@ -1857,35 +1848,25 @@ __global__ __launch_bounds__(PF_SCAN_THREADS) void pf_k0_scan(pf_load_dev d) {
 
 // ---------------------------------------------------------------------------
 // pack: one workgroup per window.  Kept records become reads in record
-// order; their scalars move to the read arrays and their calls from the
-// staging slices to the window's contiguous run (one wave per read).
-template <bool PIPE>
-DEV void k0_pack(pf_load_dev d) {
+// order; their scalars move to the read arrays.  A read's calls stay where K0
+// staged them (a static slice or the bump tail, rec_out words 4-5): the pack
+// records the range [begin, begin + rec_n) and K12 reads it in place.
+__global__ __launch_bounds__(PF_PACK_THREADS) void pf_k0_pack(pf_load_dev d) {
     constexpr uint32_t NT = PF_PACK_THREADS, NW = NT / 64;
     __shared__ uint32_t sh32[2 * NW];
-    __shared__ uint32_t l_n[NT];
-    __shared__ uint64_t l_src[NT], l_dst[NT];
-    const uint32_t w = d.win_order[blockIdx.x], tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+    const uint32_t w = d.win_order[blockIdx.x], tid = threadIdx.x;
     const uint32_t rb = d.win_read_off[w], re = d.win_read_off[w + 1];
-    const bool last = w + 1 == d.n_windows;
-    if (re == rb) {
-        if (last && tid == 0) d.read_call_off[re] = re ? d.win_call_off[d.n_windows] : 0ull;
-        return;
-    }
+    if (re == rb) return;
     const uint32_t rec0 = d.win_rec_off[w], rec1 = d.win_rec_off[w + 1];
-    uint32_t kc = 0, ccarry = 0;
-    const uint64_t cb = d.win_call_off[w];
+    uint32_t kc = 0;
     for (uint32_t i0 = rec0; i0 < rec1; i0 += NT) {
         const uint32_t r = i0 + tid;
         const uint32_t n = r < rec1 ? d.rec_n[r] : PF_NONE;
         const bool keep = n != PF_NONE;
-        uint32_t tk, tc;
+        uint32_t tk;
         const uint32_t ek = blk_excl_scan<NT, uint32_t>(keep ? 1u : 0u, sh32, tk);
-        // per-window calls fit u32 (the window totals are u32 atomics)
-        const uint32_t ec = blk_excl_scan<NT, uint32_t>(keep ? n : 0u, sh32, tc);
         if (keep) {
             const uint32_t ri = rb + kc + ek;
-            const uint64_t co = cb + ccarry + ec;
             const uint4 ro = reinterpret_cast<const uint4 *>(d.rec_out)[2ull * r];
             const uint2 rc = reinterpret_cast<const uint2 *>(d.rec_out)[4ull * r + 2];
             d.read_start[ri] = ro.x;
@@ -1897,83 +1878,26 @@ DEV void k0_pack(pf_load_dev d) {
             const uint8_t h = d.hp[r];
             d.read_hp[ri] = h;
             d.hp_raw[ri] = h;
-            d.read_call_off[ri] = co;
-            l_n[ek] = n;
-            l_src[ek] = ((uint64_t)rc.y << 32) | rc.x;
-            l_dst[ek] = co;
+            const uint64_t src = ((uint64_t)rc.y << 32) | rc.x;
+            d.read_call_off[ri] = src;
+            d.read_call_end[ri] = src + n;
         }
-        __syncthreads();
-        if constexpr (PIPE) {
-        // one wave per read, 256-call chunks (4 calls per lane); the next
-        // chunk's loads are issued before this chunk's stores, so a wave's
-        // chunks overlap one memory round trip with the next (two chunks in
-        // registers: the kernel keeps 8 waves per SIMD)
-        {
-            constexpr uint32_t U = PF_PACK_U;
-            uint32_t j = wid, c0 = 0;
-            uint32_t pv[U];
-            uint8_t cv[U];
-            auto load = [&](uint32_t jj, uint32_t cc, uint32_t *p8, uint8_t *q8) {
-                const uint32_t cn = l_n[jj];
-                const uint64_t s = l_src[jj];
-#pragma unroll
-                for (uint32_t u = 0; u < U; u++) {
-                    const uint32_t c = cc + u * 64 + lane;
-                    p8[u] = c < cn ? d.stage_pos[s + c] : 0u;
-                    q8[u] = c < cn ? d.stage_cat[s + c] : (uint8_t)0;
-                }
-            };
-            if (j < tk) load(j, 0, pv, cv);
-            while (j < tk) {
-                uint32_t jn = j, cn0 = c0 + U * 64;
-                if (cn0 >= l_n[j]) { jn = j + NW; cn0 = 0; }
-                uint32_t pn[U];
-                uint8_t qn[U];
-                if (jn < tk) load(jn, cn0, pn, qn);
-                const uint32_t cn = l_n[j];
-                const uint64_t t = l_dst[j];
-#pragma unroll
-                for (uint32_t u = 0; u < U; u++) {
-                    const uint32_t c = c0 + u * 64 + lane;
-                    if (c < cn) { d.call_pos[t + c] = pv[u]; d.call_cat[t + c] = cv[u]; }
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < U; u++) { pv[u] = pn[u]; cv[u] = qn[u]; }
-                j = jn;
-                c0 = cn0;
-            }
-        }
-        } else {
-        // one wave per read, 8 calls per lane in flight (loads before stores)
-        for (uint32_t j = wid; j < tk; j += NW) {
-            const uint32_t cn = l_n[j];
-            const uint64_t s = l_src[j], t = l_dst[j];
-            for (uint32_t c0 = 0; c0 < cn; c0 += 8 * 64) {
-                uint32_t pv[8];
-                uint8_t cv[8];
-#pragma unroll
-                for (uint32_t u = 0; u < 8; u++) {
-                    const uint32_t c = c0 + u * 64 + lane;
-                    pv[u] = c < cn ? d.stage_pos[s + c] : 0u;
-                    cv[u] = c < cn ? d.stage_cat[s + c] : (uint8_t)0;
-                }
-#pragma unroll
-                for (uint32_t u = 0; u < 8; u++) {
-                    const uint32_t c = c0 + u * 64 + lane;
-                    if (c < cn) { d.call_pos[t + c] = pv[u]; d.call_cat[t + c] = cv[u]; }
-                }
-            }
-        }
-        }
-        __syncthreads();
         kc += tk;
-        ccarry += tc;
     }
-    if (last && tid == 0) d.read_call_off[re] = d.win_call_off[d.n_windows];
 }
-// a batch of PF_PACK_PIPE_MIN+ windows takes the pipelined copy (two
-// workgroups per CU held by the register budget), a smaller one the plain one
-__global__ __launch_bounds__(PF_PACK_THREADS) __attribute__((amdgpu_waves_per_eu(8))) void pf_k0_pack(pf_load_dev d) {
-    k0_pack<PF_PACK_PIPE != 0>(d);
+
+// debug / parity only (pf_batch_debug_calls): the reads' calls gathered from
+// their staging slices into one run in read order, dst_off its prefix sums
+// (the oracle's layout).  One wavefront per read; no timed path runs it.
+__global__ __launch_bounds__(256) void pf_k0_gather_calls(const uint64_t *src_off, const uint64_t *dst_off, uint32_t R,
+                                                          const uint32_t *spos, const uint8_t *scat, uint32_t *dpos,
+                                                          uint8_t *dcat) {
+    const uint32_t lane = threadIdx.x & 63u, wid = threadIdx.x >> 6;
+    for (uint64_t r = (uint64_t)blockIdx.x * 4 + wid; r < R; r += (uint64_t)gridDim.x * 4) {
+        const uint64_t s = src_off[r], t = dst_off[r], n = dst_off[r + 1] - t;
+        for (uint64_t c = lane; c < n; c += 64) {
+            dpos[t + c] = spos[s + c];
+            dcat[t + c] = scat[s + c];
+        }
+    }
 }
-__global__ __launch_bounds__(PF_PACK_THREADS) void pf_k0_pack_small(pf_load_dev d) { k0_pack<false>(d); }
