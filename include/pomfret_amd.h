@@ -332,6 +332,35 @@ int  pf_batch_debug_sites(pf_dbatch_t *db, uint32_t w, int dir, uint32_t *real,
 int64_t pf_batch_debug_methmers(pf_dbatch_t *db, int dir, uint32_t *mmr_n,
                                 uint32_t *mmr_start, uint32_t *keys, uint64_t cap);
 
+/* Per-haplotype CpG methylation pileup of a batch's calls (pf_pileup.hip; no
+ * reference counterpart).  For window w every call entry of its reads with
+ * win_start[w] <= pos < win_end[w] and cat 0 (meth) or 1 (unmeth) adds one to
+ * cnt[pos][h][cat]; h = 0 / 1 for read_hp 0 / 1 and 2 for every other tag (254
+ * untagged, HP >= 3).  No-calls (cat 2) count nowhere; a read with two entries
+ * at one position counts twice; a read of two windows counts in each, inside
+ * that window's range; K12's left-coverage check does not apply.  A position
+ * with a non-zero counter is a site.  The result is an exactly sized CSR owned
+ * by the library (pf_pileup_free), the same for any tile size. */
+typedef struct pf_pileup {
+    uint32_t n_windows;
+    uint64_t n_sites;
+    const uint64_t *win_off;   /* [n_windows+1]                                  */
+    const uint32_t *pos;       /* [n_sites] ascending inside a window            */
+    const uint32_t *cnt;       /* [n_sites*6] index h*2+cat; h 0,1,2=other; cat 0 meth,1 unmeth */
+    float ms_kernels;          /* event-timed: the pileup kernels only           */
+} pf_pileup_t;
+/* Record-level batches run their load stage (K0, scan, pack) first.  read_hp
+ * NULL: the batch's own tags; else [n_hp] tags in read order that replace them
+ * for this call only (e.g. pf_window_out_t.read_hp of a run), n_hp equal to
+ * pf_batch_n_reads after the load (PF_ERR_ARG otherwise).  PF_ERR_ARG while a
+ * launched run is unfinished.  The batch is left as it was.  Counts are exact
+ * up to 65,535 per counter; a count past that (duplicate entries only: a
+ * window holds at most 65,535 reads) returns PF_ERR_LIMIT.  PF_PILE_TILE=<n>
+ * in the environment (tests) sets the LDS tile to n positions, a power of two
+ * in [64, 8192]; the default is 4,096. */
+int  pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, pf_pileup_t **out);
+void pf_pileup_free(pf_pileup_t *p);
+
 /* -u pre-pass: hp_out[r] in {0, 1, 254} for every read of one contig. */
 int  pf_haptag_reads(pf_ctx_t *ctx, const pf_known_vars_t *known,
                      const pf_read_aln_batch_t *reads, uint8_t *hp_out);
@@ -958,6 +987,46 @@ int  pf_retag_bam(const char *bam_in, const char *bam_out, const char *bai_out, 
 int  pf_retag_bam_threads(const char *bam_in, const char *bam_out, const char *bai_out, const char *tsv_out, int mode,
                           const pf_gaps_t *g, const pf_blocks_t *blk, const pf_tags_t *methphased,
                           const pf_tags_t *raw, int level, int threads, uint64_t *n_records);
+
+/* ------------------------------------------------------------------ */
+/* hapmeth: per-haplotype CpG methylation of a haplotagged BAM (no reference
+ * counterpart).  Host only: the sites of windows [w0, w1) of a pileup as BED
+ * lines, tab-separated:
+ *   chrom start start+1 h1_meth h1_unmeth h2_meth h2_unmeth other_meth other_unmeth asm_p
+ * start the 0-based position of the CpG's C (strands combined), asm_p the
+ * two-sided pf_fisher_exact(h1_meth, h1_unmeth, h2_meth, h2_unmeth) as %.6g.
+ * header != 0 creates (truncates) the file and writes the column names behind
+ * a '#' first; header == 0 appends to it.  Returns PF_OK, PF_ERR_ARG, or -1
+ * when the file cannot be written. */
+int  pf_write_hapmeth(const char *path, const char *chrom, const pf_pileup_t *p, uint32_t w0, uint32_t w1, int header);
+
+typedef struct pf_hapmeth_opts {
+    const char *bam_path;      /* sorted, indexed, haplotagged (HP)                        */
+    const char *out_prefix;    /* writes {out_prefix}.hapmeth.bed                          */
+    const char *region;        /* NULL: every contig in header order; else chrom or
+                                  chrom:beg-end, 1-based inclusive (samtools style)        */
+    uint32_t chunk_size;       /* window (fetch unit) length in bases; 0 -> 100,000        */
+    uint32_t job_windows;      /* windows per device job; 0 -> 1024                        */
+    pf_load_cfg_t load;        /* K0's filters and ML bands                                */
+    int32_t threads;           /* host threads of --host-fetch                             */
+    int32_t host_fetch;        /* records inflated and decoded on the host                 */
+    int32_t device;
+    int32_t verbose;
+} pf_hapmeth_opts_t;
+
+typedef struct pf_hapmeth_stats {
+    uint64_t n_windows;        /* windows planned                                          */
+    uint64_t n_skipped;        /* of those, windows the index holds no chunk for (not fetched) */
+    uint64_t n_records;        /* records fetched                                          */
+    uint64_t n_sites;          /* lines written                                            */
+    double ms_kernels;         /* summed pf_pileup_t.ms_kernels                            */
+} pf_hapmeth_stats_t;
+
+/* The windows of each contig (or of the region) in order, jobs of job_windows
+ * windows one after another on one device: the device fetch (or the host
+ * fetch) with no read-back margin, pf_batch_pileup under the records' HP
+ * tags, pf_write_hapmeth.  stats may be NULL. */
+int  pf_hapmeth_main(const pf_hapmeth_opts_t *o, pf_hapmeth_stats_t *stats);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

@@ -12,7 +12,7 @@ import weakref
 
 import numpy as np
 
-from .abi import (AlnBatch, Config, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfKnownVars, PfLoadCfg,
+from .abi import (AlnBatch, Config, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfKnownVars, PfLoadCfg, PfPileup,
                   PfReadAlnBatch, PfWindowBatch, PfWindowOut, ReadAlnBatch, WindowBatch, WindowResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -77,6 +77,10 @@ def lib():
         L.pf_batch_debug_recs.argtypes = [C.c_void_p] * 16
         L.pf_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                       C.POINTER(C.c_uint64), C.c_void_p, C.c_uint32, C.POINTER(C.c_float)]
+        L.pf_batch_pileup.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                      C.POINTER(C.POINTER(PfPileup))]
+        L.pf_pileup_free.argtypes = [C.POINTER(PfPileup)]
+        L.pf_write_hapmeth.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfPileup), C.c_uint32, C.c_uint32, C.c_int]
         if hasattr(L, "pf_haptag_reads"):
             L.pf_haptag_reads.argtypes = [C.c_void_p, C.POINTER(PfKnownVars),
                                           C.POINTER(PfReadAlnBatch), C.c_void_p]
@@ -472,6 +476,32 @@ class DeviceBatch:
         if fresh:
             out.read_hp = out.read_hp[:self.n_reads]
         return out
+
+    def pileup(self, read_hp=None) -> dict:
+        """Per-haplotype CpG methylation pileup of the batch's calls
+        (pf_batch_pileup): dict(win_off [W+1], pos [n] ascending inside a
+        window, cnt [n, 3, 2] indexed [site, h, cat] with h 0 / 1 / 2 = other
+        and cat 0 meth / 1 unmeth, ms the pileup kernels' time).  read_hp:
+        tags in read order that replace the batch's own for this call (e.g.
+        a run's WindowResult.read_hp); a record-level batch runs its loader
+        first."""
+        hp_ptr, n_hp = None, 0
+        if read_hp is not None:
+            # one spare byte keeps the pointer valid (and non-NULL) for zero reads
+            hp = np.zeros(np.size(read_hp) + 1, np.uint8)
+            hp[:-1] = np.asarray(read_hp, np.uint8).ravel()
+            hp_ptr, n_hp = hp.ctypes.data, hp.size - 1
+        p = C.POINTER(PfPileup)()
+        _check(lib().pf_batch_pileup(self.ctx.handle, self.handle, hp_ptr, n_hp, C.byref(p)), "pf_batch_pileup")
+        try:
+            r = p.contents
+            W, n = int(r.n_windows), int(r.n_sites)
+            win_off = np.ctypeslib.as_array(r.win_off, (W + 1,)).copy()
+            pos = np.ctypeslib.as_array(r.pos, (n,)).copy() if n else np.zeros(0, np.uint32)
+            cnt = np.ctypeslib.as_array(r.cnt, (n * 6,)).copy() if n else np.zeros(0, np.uint32)
+            return dict(win_off=win_off, pos=pos, cnt=cnt.reshape(n, 3, 2), ms=float(r.ms_kernels))
+        finally:
+            lib().pf_pileup_free(p)
 
     def stats(self) -> np.ndarray:
         """Per-(window, dir) counters of the last run: [W, 2, 8] (see pf_batch_stats)."""

@@ -342,6 +342,25 @@ class LoadConfig:
         return PfLoadCfg(self.min_mapq, self.min_len, self.qual_lo, self.qual_hi)
 
 
+class PfPileup(C.Structure):
+    """pf_pileup_t: the per-haplotype pileup's CSR (pf_batch_pileup)."""
+    _fields_ = [("n_windows", C.c_uint32), ("n_sites", C.c_uint64), ("win_off", C.POINTER(C.c_uint64)),
+                ("pos", C.POINTER(C.c_uint32)), ("cnt", C.POINTER(C.c_uint32)), ("ms_kernels", C.c_float)]
+
+
+class PfHapmethOpts(C.Structure):
+    """pf_hapmeth_opts_t (pf_hapmeth_main)."""
+    _fields_ = [("bam_path", C.c_char_p), ("out_prefix", C.c_char_p), ("region", C.c_char_p),
+                ("chunk_size", C.c_uint32), ("job_windows", C.c_uint32), ("load", PfLoadCfg),
+                ("threads", C.c_int32), ("host_fetch", C.c_int32), ("device", C.c_int32), ("verbose", C.c_int32)]
+
+
+class PfHapmethStats(C.Structure):
+    """pf_hapmeth_stats_t."""
+    _fields_ = [("n_windows", C.c_uint64), ("n_skipped", C.c_uint64), ("n_records", C.c_uint64),
+                ("n_sites", C.c_uint64), ("ms_kernels", C.c_double)]
+
+
 class PfAlnBatch(C.Structure):
     _fields_ = [("n_windows", C.c_uint32), ("n_recs", C.c_uint32)] + [
         (n, C.c_void_p) for n in (

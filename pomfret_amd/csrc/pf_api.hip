@@ -36,6 +36,9 @@ __global__ void pf_k0_scan(pf_load_dev d);
 __global__ void pf_k0_pack(pf_load_dev d);
 __global__ void pf_k0_gather_calls(const uint64_t *src_off, const uint64_t *dst_off, uint32_t R, const uint32_t *spos,
                                    const uint8_t *scat, uint32_t *dpos, uint8_t *dcat);
+__global__ void pf_pile_count(pf_pile_args a);
+__global__ void pf_pile_scan(pf_pile_args a);
+__global__ void pf_pile_emit(pf_pile_args a);
 __global__ void pf_selftest_div(unsigned long long *bad);
 __global__ void pf_selftest_wave(unsigned long long *bad);
 
@@ -80,7 +83,7 @@ struct pf_ctx {
 // a lock and only ever raised, so one context's smaller batch never lowers the
 // limit another context's launch relies on.
 static std::mutex g_lds_mu;
-static uint32_t g_lds_set[64][4];             // [device][greedy, fallback, one-wave, heavy]
+static uint32_t g_lds_set[64][5];             // [device][greedy, fallback, one-wave, heavy, pileup]
 static int raise_lds_limit(int dev, int which, const void *const *fns, int nf, uint32_t need) {
     if (dev < 0 || dev >= 64) return PF_ERR_ARG;
     std::lock_guard<std::mutex> lk(g_lds_mu);
@@ -1508,6 +1511,152 @@ static int run_debug(pf_dbatch *b, int stages) {
             return PF_OK;
         }
     }
+}
+
+// ---- per-haplotype pileup of the batch's calls (pf_pileup.hip)
+extern "C" void pf_pileup_free(pf_pileup_t *p) {
+    if (!p) return;
+    free(const_cast<uint64_t *>(p->win_off));
+    free(const_cast<uint32_t *>(p->pos));
+    free(const_cast<uint32_t *>(p->cnt));
+    free(p);
+}
+
+// the tile in positions: PF_PILE_TILE=<n> (tests: tile edges at tiny shapes),
+// n a power of two in [64, PF_PILE_TILE_MAX]; 0 for any other value
+static uint32_t pile_tile() {
+    const char *e = getenv("PF_PILE_TILE");
+    if (!e) return PF_PILE_TILE;
+    const long n = atol(e);
+    if (n < 64 || n > PF_PILE_TILE_MAX || (n & (n - 1))) return 0;
+    return (uint32_t)n;
+}
+
+extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *read_hp, uint32_t n_hp,
+                               pf_pileup_t **out) {
+    if (!ctx || !b || !out || b->ctx != ctx) return PF_ERR_ARG;
+    *out = nullptr;
+    if (b->n_launch != b->n_finish) return PF_ERR_ARG;       // a run is in flight
+    const uint32_t T = pile_tile();
+    if (!T) return PF_ERR_ARG;
+    HIPCHK(hipSetDevice(ctx->device));
+    // record level: K0, scan and pack size the batch and leave its reads and calls
+    if (b->has_aln) {
+        const int rc = run_debug(b, 0);
+        if (rc) return rc;
+    }
+    const uint32_t W = b->W, R = b->R;
+    if (read_hp && n_hp != R) return PF_ERR_ARG;
+    hipStream_t st = ctx->stream;
+    const pf_dev_batch &d = b->d;
+
+    pf_pileup_t *res = (pf_pileup_t *)calloc(1, sizeof(pf_pileup_t));
+    uint64_t *h_win_off = (uint64_t *)calloc((size_t)W + 1, sizeof(uint64_t));
+    std::vector<void *> tmp;                                  // this call's device arrays
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    auto done = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        for (void *p : tmp) (void)hipFree(p);
+        for (auto e : ev) if (e) (void)hipEventDestroy(e);
+        if (rc) {
+            if (res) { res->win_off = h_win_off; pf_pileup_free(res); } else free(h_win_off);
+        } else
+            *out = res;
+        return rc;
+    };
+    if (!res || !h_win_off) return done(PF_ERR_NOMEM);
+    res->n_windows = W;
+    res->win_off = h_win_off;
+    if (W == 0) return done(PF_OK);
+
+    // items: the tiles of every window
+    std::vector<uint32_t> hws(W), hwe(W), tile_off((size_t)W + 1, 0);
+    if (hipMemcpyAsync(hws.data(), d.win_start, 4ull * W, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(hwe.data(), d.win_end, 4ull * W, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return done(PF_ERR_HIP);
+    uint64_t n_items = 0;
+    for (uint32_t w = 0; w < W; w++) {
+        n_items += hwe[w] > hws[w] ? ((uint64_t)(hwe[w] - hws[w]) + T - 1) / T : 0;
+        if (n_items > 0x7FFFFFFFull) return done(PF_ERR_LIMIT);      // one workgroup per item
+        tile_off[w + 1] = (uint32_t)n_items;
+    }
+    if (n_items == 0) return done(PF_OK);
+
+    pf_pile_args a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.T = T; a.n_items = (uint32_t)n_items;
+    a.win_start = d.win_start; a.win_end = d.win_end; a.win_read_off = d.win_read_off;
+    a.read_hp = d.read_hp;
+    a.read_call_off = d.read_call_off; a.read_call_end = d.read_call_end;
+    a.call_pos = d.call_pos; a.call_cat = d.call_cat;
+    auto talloc = [&](void **p, size_t bytes) {
+        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
+        tmp.push_back(*p);
+        return PF_OK;
+    };
+    void *p_hp = nullptr, *p_to = nullptr, *p_ic = nullptr, *p_io = nullptr, *p_wo = nullptr, *p_st = nullptr;
+    if ((read_hp && R && talloc(&p_hp, R)) || talloc(&p_to, 4ull * (W + 1)) || talloc(&p_ic, 4ull * n_items) ||
+        talloc(&p_io, 8ull * (n_items + 1)) || talloc(&p_wo, 8ull * (W + 1)) || talloc(&p_st, 8))
+        return done(PF_ERR_NOMEM);
+    if (p_hp) {
+        if (hipMemcpyAsync(p_hp, read_hp, R, hipMemcpyHostToDevice, st) != hipSuccess) return done(PF_ERR_HIP);
+        a.read_hp = static_cast<const uint8_t *>(p_hp);
+    }
+    a.tile_off = static_cast<uint32_t *>(p_to);
+    a.item_cnt = static_cast<uint32_t *>(p_ic);
+    a.item_off = static_cast<uint64_t *>(p_io);
+    a.win_off = static_cast<uint64_t *>(p_wo);
+    a.status = static_cast<uint32_t *>(p_st);
+    const uint32_t lds = 12u * T;
+    if (lds > 65536u) {
+        const void *f[2] = {(const void *)pf_pile_count, (const void *)pf_pile_emit};
+        if (raise_lds_limit(ctx->device, 4, f, 2, lds)) return done(PF_ERR_HIP);
+    }
+    for (auto &e : ev)
+        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
+    uint64_t n_sites = 0;
+    uint32_t stt = 0;
+    if (hipMemcpyAsync(p_to, tile_off.data(), 4ull * (W + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemsetAsync(p_st, 0, 8, st) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess)
+        return done(PF_ERR_HIP);
+    hipLaunchKernelGGL(pf_pile_count, dim3(a.n_items), dim3(PF_PILE_THREADS), lds, st, a);
+    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    hipLaunchKernelGGL(pf_pile_scan, dim3(1), dim3(PF_PILE_SCAN_THREADS), 0, st, a);
+    if (hipGetLastError() != hipSuccess || hipEventRecord(ev[1], st) != hipSuccess ||
+        hipMemcpyAsync(&n_sites, a.item_off + a.n_items, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&stt, p_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return done(PF_ERR_HIP);
+    if (stt) {
+        fprintf(stderr, "[E::pomfret_amd] pileup: a count passed 65,535 (duplicate call entries)\n");
+        return done(PF_ERR_LIMIT);
+    }
+    float ms0 = 0.0f, ms1 = 0.0f;
+    if (n_sites) {
+        uint32_t *h_pos = (uint32_t *)malloc(4ull * n_sites), *h_cnt = (uint32_t *)malloc(24ull * n_sites);
+        res->pos = h_pos;
+        res->cnt = h_cnt;
+        void *p_op = nullptr, *p_oc = nullptr;
+        if (!h_pos || !h_cnt || talloc(&p_op, 4ull * n_sites) || talloc(&p_oc, 24ull * n_sites))
+            return done(PF_ERR_NOMEM);
+        a.out_pos = static_cast<uint32_t *>(p_op);
+        a.out_cnt = static_cast<uint32_t *>(p_oc);
+        if (hipEventRecord(ev[2], st) != hipSuccess) return done(PF_ERR_HIP);
+        hipLaunchKernelGGL(pf_pile_emit, dim3(a.n_items), dim3(PF_PILE_THREADS), lds, st, a);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[3], st) != hipSuccess ||
+            hipMemcpyAsync(h_pos, p_op, 4ull * n_sites, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(h_cnt, p_oc, 24ull * n_sites, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(h_win_off, p_wo, 8ull * (W + 1), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return done(PF_ERR_HIP);
+        (void)hipEventElapsedTime(&ms1, ev[2], ev[3]);
+    }
+    (void)hipEventElapsedTime(&ms0, ev[0], ev[1]);
+    (void)hipGetLastError();
+    res->n_sites = n_sites;
+    res->ms_kernels = ms0 + ms1;
+    return done(PF_OK);
 }
 
 extern "C" int pf_methphase_run(pf_ctx_t *ctx, pf_dbatch_t *b, pf_window_out_t *out) {

@@ -7,6 +7,7 @@
  *   pomfret-amd methphase -o out --vcf phased.vcf.gz [-c 60] [-u] [-t N] [--write-bam] [--gpus G] reads.bam
  *   pomfret-amd report    -o out --vcf phased.vcf.gz [-c C] [--chunk-size S --chunk-stride D] reads.bam
  *   pomfret-amd varhaptag -o out.bam in.vcf in.bam
+ *   pomfret-amd hapmeth   -o out [-r chrom[:beg-end]] [--chunk-size N] [-q mapq] [-L minlen] [--host-fetch] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
  * cliopt_haptag_t (cli.c:332-343); the -c arithmetic (cov/10, cov/4), the
@@ -24,6 +25,10 @@
  * pre-haplotag.  -U writes {prefix}.mp.input_haptag.tsv (4494-4517).  --dbg's
  * {prefix}.mp.dbg.read2tag (2223-2248) lists a khash in bucket order, which
  * no other implementation reproduces: it is not written (a warning says so).
+ * Added subcommand: hapmeth writes {prefix}.hapmeth.bed, the methylation of
+ * every CpG per haplotype of a haplotagged BAM (the HP tags of methphase
+ * --write-bam, varhaptag or any other haplotagger) with the allele-specific
+ * methylation p-value (pf_hapmeth_main; no reference counterpart).
  */
 #include <getopt.h>
 #include <stdio.h>
@@ -47,6 +52,9 @@ static void help_main(void) {
     fprintf(stderr, "             and exiting phase blocks, try to use methylation to\n");
     fprintf(stderr, "             phase the unphased regions (on the GPU).\n");
     fprintf(stderr, "  varhaptag  Haplotag reads from phased variants (on the GPU).\n");
+    fprintf(stderr, "  hapmeth    Given haplotagged reads with methylation calls in bam, write\n");
+    fprintf(stderr, "             the methylation of every CpG per haplotype and where the\n");
+    fprintf(stderr, "             two haplotypes differ (on the GPU).\n");
     fprintf(stderr, "  report     Given aligned reads in bam and a phased vcf, sample\n");
     fprintf(stderr, "             intervals within phase blocks, pretend they are phase gaps\n");
     fprintf(stderr, "             and report whether meth-phasing would generate correct \n");
@@ -260,6 +268,82 @@ static int varhaptag(int argc, char **argv) {
     return 0;
 }
 
+static void help_hapmeth(void) {
+    fprintf(stderr, "Usage: pomfret-amd hapmeth -o out_prefix [...] tagged.bam 2>log\n");
+    fprintf(stderr, "Writes {out_prefix}.hapmeth.bed: per CpG (0-based position of its C, strands combined) the meth and\n"
+                    "unmeth calls of haplotype 1, haplotype 2 and the other reads, and the two-sided Fisher p-value of\n"
+                    "haplotype 1 against haplotype 2 (allele-specific methylation).\n");
+    fprintf(stderr, "Options:\n");
+    fprintf(stderr, "  bam    [pos] Aligned, sorted, indexed reads with HP tags (methphase --write-bam, varhaptag, ...).\n");
+    fprintf(stderr, "  -o     [opt] Name prefix of the output file. [pomfret]\n");
+    fprintf(stderr, "  -r     [opt] Region chrom or chrom:beg-end (1-based, inclusive). [every contig]\n");
+    fprintf(stderr, "  --chunk-size [opt] Bases per window, the fetch unit. [100000]\n");
+    fprintf(stderr, "  -q,--mapq [opt] Minimum mapping quality. [10]\n");
+    fprintf(stderr, "  -L     [opt] Minimum read length. [0]  Reads shorter than 2 bases and reads whose de tag fails\n"
+                    "               the loader's divergence filter are dropped whatever -L says.\n");
+    fprintf(stderr, "  --lo, --hi [opt] ML below lo is unmethylated, from hi methylated, between them no call. [100, 156]\n");
+    fprintf(stderr, "  -t     [opt] Host threads of --host-fetch. [1]\n");
+    fprintf(stderr, "  --host-fetch [opt] Inflate and decode BAM records on the host instead of the GPU.\n");
+    fprintf(stderr, "  --gpus [opt] The GPU to use (the first of the list). [0]\n");
+    fprintf(stderr, "  --job-windows [opt] Windows per device job. [1024]\n");
+    fprintf(stderr, "  -v     [opt] Print the run's counts and the pileup kernels' time.\n");
+}
+
+/* hapmeth: one device, the jobs one after another (pf_hapmeth_main) */
+static int hapmeth(int argc, char **argv) {
+    pf_hapmeth_opts_t op;
+    memset(&op, 0, sizeof op);
+    op.out_prefix = "pomfret";
+    op.load.min_mapq = 10; op.load.min_len = 0; op.load.qual_lo = 100; op.load.qual_hi = 156;
+    op.threads = 1;
+    int o, csize = 100000, jobw = 0;
+    if (argc == 1) { help_hapmeth(); return 1; }
+    optind = 1;
+    while ((o = getopt_long(argc, argv, "vho:r:q:L:t:", longopts, NULL)) >= 0) {
+        switch (o) {
+        case 'h': case O_HELP: help_hapmeth(); return 1;
+        case 'v': op.verbose++; break;
+        case 'o': op.out_prefix = optarg; break;
+        case 'r': op.region = optarg; break;
+        case 'q': case O_MAPQ: op.load.min_mapq = atoi(optarg); break;
+        case 'L': op.load.min_len = atoi(optarg); break;
+        case 't': op.threads = atoi(optarg); break;
+        case O_LO: op.load.qual_lo = atoi(optarg); break;
+        case O_HI: op.load.qual_hi = atoi(optarg); break;
+        case O_CSIZE: csize = atoi(optarg); break;
+        case O_GPUS: op.device = atoi(optarg); break;
+        case O_JOBW: jobw = atoi(optarg); break;
+        case O_HFETCH: op.host_fetch = 1; break;
+        default:
+            fprintf(stderr, "[E::parse_cli_hapmeth] unknown or incomplete option \"%s\"\n", argv[optind - 1]);
+            return 1;
+        }
+    }
+    for (int i = optind; i < argc; i++) {
+        if (op.bam_path) { fprintf(stderr, "[E::parse_cli_hapmeth] multiple bam input is not supported.\n"); return 1; }
+        op.bam_path = argv[i];
+    }
+    if (!op.bam_path) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] missing bam file\n"); return 1; }
+    if (op.load.qual_lo < 0 || op.load.qual_lo > 127) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --lo (%d)\n", op.load.qual_lo); return 1; }
+    if (op.load.qual_hi > 255 || op.load.qual_hi <= 127) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --hi (%d)\n", op.load.qual_hi); return 1; }
+    if (csize <= 0) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] invalid chunk size\n"); return 1; }
+    if (!op.out_prefix[0]) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] no output prefix given\n"); return 1; }
+    if (op.load.min_mapq < 0) op.load.min_mapq = 0;
+    if (op.load.min_len < 0) op.load.min_len = 0;
+    if (op.threads < 1) op.threads = 1;
+    if (op.device < 0) op.device = 0;
+    op.chunk_size = (uint32_t)csize;
+    op.job_windows = jobw > 0 ? (uint32_t)jobw : 0;
+    pf_hapmeth_stats_t st;
+    const int rc = pf_hapmeth_main(&op, &st);
+    if (rc) {
+        fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
+        return 1;
+    }
+    fprintf(stderr, "[M::main] %llu sites written to %s.hapmeth.bed\n", (unsigned long long)st.n_sites, op.out_prefix);
+    return 0;
+}
+
 int main(int argc, char **argv) {
     fprintf(stderr, "[M::main] pomfret-amd (MI355X) ABI %d\n[M::main] CMD: ", pf_abi_version());
     for (int i = 0; i < argc; i++) fprintf(stderr, "%s ", argv[i]);
@@ -270,6 +354,7 @@ int main(int argc, char **argv) {
         return 1;
     }
     if (!strcmp(argv[1], "varhaptag")) return varhaptag(argc - 1, argv + 1);
+    if (!strcmp(argv[1], "hapmeth")) return hapmeth(argc - 1, argv + 1);
     const int report = !strcmp(argv[1], "report");
     if (!report && strcmp(argv[1], "methphase")) {
         fprintf(stderr, "[E::main] unknown subcommand: %s\n", argv[1]);

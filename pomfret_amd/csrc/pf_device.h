@@ -38,6 +38,11 @@
 #define PF_K12C_READS 64          /* reads per item of pf_k12_chunks (the heavy windows' methmer phase) */
 #define PF_K12C_WAVES 8           /* its waves per workgroup */
 #define PF_K12C_LDS 61440         /* its dynamic LDS: 14 B per site + PF_K12C_WAVES wave buffers (2 per CU) */
+#define PF_PILE_TILE 4096          /* positions per LDS tile of the pileup: 3 packed u32 each, 48 KB (3 workgroups per CU) */
+#define PF_PILE_TILE_MAX 8192      /* PF_PILE_TILE=<n> override: 96 KB */
+#define PF_PILE_THREADS 1024        /* 16 waves: a window's reads are searched 64 per wave at once */
+#define PF_PILE_WAVES (PF_PILE_THREADS / PF_WAVE)
+#define PF_PILE_SCAN_THREADS 1024
 #define PF_NONE 0xFFFFFFFFu
 
 /* status bits */
@@ -118,6 +123,28 @@ struct pf_dev_batch {
     const uint32_t *win_mask_rng;      /* [2W] window w sees mask_pos[rng[2w], rng[2w+1]); NULL: all of it */
     uint32_t *win_masked;              /* [W] qualifying positions the mask removed (the reference's n_filtered) */
     uint32_t mask_n;                   /* 0: no mask */
+};
+
+/* The per-haplotype pileup (pf_pileup.hip): one workgroup per item, an item
+ * being one tile of T positions of one window; window w owns the items
+ * [tile_off[w], tile_off[w+1]), tile j covering [win_start + j*T, +T) cut at
+ * win_end.  The count pass writes each item's sites to item_cnt, the scan
+ * turns them into item_off and win_off, the emit pass rebuilds each tile and
+ * writes its sites at item_off. */
+struct pf_pile_args {
+    uint32_t W, T, n_items;
+    const uint32_t *win_start, *win_end, *win_read_off;
+    const uint8_t *read_hp;                          /* the batch's tags or the caller's */
+    const uint64_t *read_call_off, *read_call_end;
+    const uint32_t *call_pos;
+    const uint8_t *call_cat;
+    const uint32_t *tile_off;                        /* [W+1] */
+    uint32_t *item_cnt;                              /* [n_items] */
+    uint64_t *item_off;                              /* [n_items+1] */
+    uint64_t *win_off;                               /* [W+1] */
+    uint32_t *out_pos;                               /* [n_sites] */
+    uint32_t *out_cnt;                               /* [n_sites*6] */
+    uint32_t *status;                                /* bit 0: a 16-bit counter wrapped */
 };
 
 #endif

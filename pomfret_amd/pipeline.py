@@ -33,7 +33,7 @@ import numpy as np
 
 from ._lib import (INTERVALS_GTF, INTERVALS_TSV, INTERVALS_VCF, PomfretError, _blocks_contigs, _check,  # noqa: F401
                    _gaps_contigs, _PfBlocks, _PfGaps, lib)
-from .abi import Config, LoadConfig, PfCfg, PfLoadCfg
+from .abi import Config, LoadConfig, PfCfg, PfHapmethOpts, PfHapmethStats, PfLoadCfg, PfPileup
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
 JOB_WINDOWS, JOB_HAPTAG = 0, 1
@@ -114,6 +114,7 @@ def _bind():
     L.pf_mask_load.argtypes = [C.c_char_p, C.c_char_p, u32, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.pf_mask_contig.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.pf_mask_free.argtypes = [vp]
+    L.pf_hapmeth_main.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethStats)]
     L.pf_tags_new.restype = vp
     L.pf_tags_free.argtypes = [vp]
     L.pf_tags_size.argtypes = [vp]
@@ -472,6 +473,44 @@ def report_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cov: i
         return _result(plan, MODE_REPORT)
     finally:
         plan.close()
+
+
+def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk_size: int = 100_000,
+                  lcfg: Optional[LoadConfig] = None, host_fetch: bool = False, threads: int = 1, device: int = 0,
+                  job_windows: int = 0) -> Dict:
+    """`pomfret-amd hapmeth` (pf_hapmeth_main): the per-haplotype CpG
+    methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
+    (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
+    the other reads, the two-sided Fisher p of haplotype 1 against 2).
+    region: chrom or chrom:beg-end (1-based inclusive), None: every contig.
+    chunk_size: bases per window, the fetch unit.  lcfg None: -q 10, -L 0,
+    ML bands 100 / 156.  Returns dict(path, n_windows, n_skipped (windows the
+    index holds no chunk for: not fetched), n_records, n_sites, ms_kernels)."""
+    L = _bind()
+    lc = lcfg or LoadConfig(min_len=0)
+    o = PfHapmethOpts(bam.encode(), out_prefix.encode(), region.encode() if region else None, int(chunk_size),
+                      int(job_windows), lc.to_c(), int(threads), int(bool(host_fetch)), int(device), 0)
+    st = PfHapmethStats()
+    _check(L.pf_hapmeth_main(C.byref(o), C.byref(st)), "pf_hapmeth_main")
+    return dict(path=out_prefix + ".hapmeth.bed", n_windows=int(st.n_windows), n_skipped=int(st.n_skipped),
+                n_records=int(st.n_records), n_sites=int(st.n_sites), ms_kernels=float(st.ms_kernels))
+
+
+def write_hapmeth(path: str, chrom: str, pile: Dict, header: bool = True, w0: int = 0, w1: Optional[int] = None):
+    """The sites of windows [w0, w1) of a pileup (DeviceBatch.pileup's dict:
+    win_off, pos, cnt) as hapmeth BED lines (pf_write_hapmeth, host only).
+    header: create the file with the column names first; else append."""
+    L = _bind()
+    win_off = np.ascontiguousarray(pile["win_off"], np.uint64)
+    pos = np.ascontiguousarray(pile["pos"], np.uint32)
+    cnt = np.ascontiguousarray(np.asarray(pile["cnt"], np.uint32).reshape(-1))
+    if cnt.size != 6 * pos.size or win_off.size < 1 or int(win_off[-1]) != pos.size:
+        raise PomfretError("pf_write_hapmeth: inconsistent pileup arrays")
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    p = PfPileup(win_off.size - 1, pos.size, win_off.ctypes.data_as(u64p), pos.ctypes.data_as(u32p),
+                 cnt.ctypes.data_as(u32p), 0.0)
+    _check(L.pf_write_hapmeth(path.encode(), chrom.encode(), C.byref(p), int(w0),
+                              win_off.size - 1 if w1 is None else int(w1), int(bool(header))), "pf_write_hapmeth")
 
 
 def methphase_files_dist(bam_path: str, vcf_path: str, out_prefix: Optional[str], cfg: Optional[Config],
