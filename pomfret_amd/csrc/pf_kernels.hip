@@ -1710,58 +1710,52 @@ struct K3Mem {
     uint32_t rcw;            // records per wave
 };
 
-#define K3_NOFF 13
-// P2 byte layout.  Returns the bytes needed with `rcw` records per wave;
-// slots (u16) are included only when with_slots, the per-read slot-list
-// offsets only when with_mo (the candidate cache reads them from HBM), and
-// aux_b bytes of T5 scratch (4R, or 0 when it lives in the cache region).
+// Where a greedy problem's arrays live.  Lists / Hbm: every table in LDS, the
+// slot lists beside them (u16) or read from the HBM key arena.  Cache: the
+// candidate slot-list cache (k3_greedy_slim CACHE) follows the tables; the
+// per-read slot-list offsets, methmer counts and first sites are read from
+// HBM where they are needed, and hp, flg, ord and the T5 scratch of k3_init
+// live in HBM (k3_side_mem).  CacheGcnt (path 6): Cache with the count table
+// in the problem's HBM scratch as well.
+enum class K3Place : uint32_t { Lists, Hbm, Cache, CacheGcnt };
+DEV bool k3_cached(K3Place p) { return p == K3Place::Cache || p == K3Place::CacheGcnt; }
+
+// byte offsets of the P2 regions; a region its placement leaves out is empty
+struct K3Layout {
+    K3Place place;
+    uint32_t rcw;            // records per wave (the general body; 0: the slim loop)
+    uint64_t sum, cnt, hp, flg, ord, untag, mn, mst, mo, sl16;
+    uint64_t tail;           // record rings / T5 scratch; a cached placement: tail == sl16 == need, the cache follows
+    uint64_t need;
+};
+
+// P2 byte layout of a placement with `rcw` records per wave.
 // No per-site divisor cache: a term's divisor is its site's hap total, and
 // its reciprocal is taken beside the dependent count load.
-DEV uint64_t k3_layout(uint32_t S, uint32_t ntot, uint32_t R, uint32_t dir, uint32_t summ,
-                       bool with_slots, uint32_t rcw, uint64_t off[K3_NOFF], bool c8 = false, bool with_mo = true,
-                       uint64_t aux_b = ~0ull, bool with_mnst = true, bool with_side = true, bool with_cnt = true) {
+DEV K3Layout k3_layout(uint32_t S, uint32_t ntot, uint32_t R, uint32_t dir, uint32_t summ, K3Place place,
+                       uint32_t rcw, bool c8 = false) {
     const uint32_t nwords = (R + 63) >> 6;
-    const uint64_t sd = with_side ? 1ull : 0ull;       // hp, flg, ord in LDS (else k3_side_mem)
-    off[0] = 0;                                        // sum   S*4
-    off[1] = align16(off[0] + 4ull * S);               // cnt   ntot*4 (in HBM when !with_cnt: path 6)
-    off[2] = align16(off[1] + (with_cnt ? (c8 ? 2ull : 4ull) * ntot : 0ull));   // hp    R (cnt: u8 pairs when c8)
-    off[3] = align16(off[2] + sd * R);                 // flg   R
-    off[4] = align16(off[3] + sd * R);                 // ord   R*2 (dir 1)
-    off[5] = align16(off[4] + (dir ? 2ull * sd * R : 0));   // untag nwords*8
-    const uint64_t mw = !with_mnst ? 0ull : S < 8192u ? 2ull : 4ull;   // (u16 when every index fits: see k3_mem)
-    off[6] = align16(off[5] + 8ull * nwords);          // mn    R*2|4  methmers per read
-    off[7] = align16(off[6] + mw * R);                 // mst   R*2|4  first site index
-    off[8] = align16(off[7] + mw * R);                 // mo    R*4  slot-list offset (optional)
-    off[9] = align16(off[8] + (with_mo ? 4ull * R : 0));   // sl16  summ*2 (optional)
-    off[10] = align16(off[9] + (with_slots ? 2ull * summ : 0));
-    off[11] = off[10];                                 // records / aux
+    const uint64_t sd = k3_cached(place) ? 0ull : 1ull;                           // hp, flg, ord
+    const uint64_t cw = place == K3Place::CacheGcnt ? 0ull : c8 ? 2ull : 4ull;    // a count pair (u8 pairs when c8)
+    const uint64_t mw = k3_cached(place) ? 0ull : S < 8192u ? 2ull : 4ull;   // (u16 when every index fits: see k3_mem)
+    K3Layout l;
+    l.place = place;
+    l.rcw = rcw;
+    l.sum = 0;                                         // sum   S*4
+    l.cnt = align16(l.sum + 4ull * S);                 // cnt   ntot*2|4
+    l.hp = align16(l.cnt + cw * ntot);                 // hp    R
+    l.flg = align16(l.hp + sd * R);                    // flg   R
+    l.ord = align16(l.flg + sd * R);                   // ord   R*2 (dir 1)
+    l.untag = align16(l.ord + (dir ? 2ull * sd * R : 0));   // untag nwords*8
+    l.mn = align16(l.untag + 8ull * nwords);           // mn    R*2|4  methmers per read
+    l.mst = align16(l.mn + mw * R);                    // mst   R*2|4  first site index
+    l.mo = align16(l.mst + mw * R);                    // mo    R*4  slot-list offset
+    l.sl16 = align16(l.mo + (k3_cached(place) ? 0ull : 4ull * R));   // sl16  summ*2 (Lists)
+    l.tail = align16(l.sl16 + (place == K3Place::Lists ? 2ull * summ : 0));
     const uint64_t rec = 12ull * PF_K3_WAVES * rcw;
-    const uint64_t aux = aux_b == ~0ull ? 4ull * R : aux_b;
-    off[12] = off[11] + (rec > aux ? rec : aux);
-    return off[12];
-}
-
-DEV void k3_mem(uint8_t *base, const uint64_t off[K3_NOFF], uint32_t rcw, bool with_slots,
-                const uint32_t *kb, K3Mem &m, bool with_mo = true, uint32_t S = 0xFFFFFFFFu, bool with_mnst = true) {
-    m.sum = reinterpret_cast<uint32_t *>(base + off[0]);
-    m.cnt = reinterpret_cast<uint32_t *>(base + off[1]);
-    m.hp = base + off[2];
-    m.flg = base + off[3];
-    m.ord = reinterpret_cast<uint16_t *>(base + off[4]);
-    m.untag = reinterpret_cast<uint64_t *>(base + off[5]);
-    m.mn = with_mnst ? base + off[6] : nullptr;
-    m.mst = with_mnst ? base + off[7] : nullptr;
-    m.gmn = m.gmst = nullptr;
-    m.m16 = S < 8192u;
-    m.mo = with_mo ? reinterpret_cast<uint32_t *>(base + off[8]) : nullptr;
-    m.gmo = nullptr;
-    m.kbase = 0;
-    m.sl16 = with_slots ? reinterpret_cast<uint16_t *>(base + off[9]) : nullptr;
-    m.kb = kb;
-    m.recv = reinterpret_cast<float2 *>(base + off[11]);
-    m.recc = reinterpret_cast<uint32_t *>(base + off[11] + 8ull * PF_K3_WAVES * rcw);
-    m.aux = reinterpret_cast<uint32_t *>(base + off[11]);
-    m.rcw = rcw;
+    const uint64_t aux = k3_cached(place) ? 0ull : 4ull * R;
+    l.need = l.tail + (rec > aux ? rec : aux);
+    return l;
 }
 
 // the per-read side arrays (hp, flg, ord, aux) of problem (r0, dir) in the
@@ -1774,6 +1768,42 @@ DEV void k3_side_mem(const pf_dev_batch &d, uint32_t r0, uint32_t dir, K3Mem &m)
     m.flg = d.k3_side + 2 * RB + dir * RB + r0;
     m.ord = reinterpret_cast<uint16_t *>(d.k3_side + 4 * RB) + r0;
     m.aux = reinterpret_cast<uint32_t *>(d.k3_side + ((6 * RB + 3) & ~3ull)) + dir * RB + r0;
+}
+
+// every field of m for problem (r0, dir) with layout l at `base`; kbase: the
+// problem's first key (d.mmr_off[2 * r0]); scr: its HBM scratch (CacheGcnt)
+DEV void k3_mem(const pf_dev_batch &d, uint32_t r0, uint32_t dir, uint64_t kbase, uint32_t S, uint8_t *base,
+                const K3Layout &l, K3Mem &m, uint8_t *scr = nullptr) {
+    const bool cached = k3_cached(l.place);
+    m.sum = reinterpret_cast<uint32_t *>(base + l.sum);
+    m.cnt = reinterpret_cast<uint32_t *>(l.place == K3Place::CacheGcnt ? scr : base + l.cnt);
+    m.untag = reinterpret_cast<uint64_t *>(base + l.untag);
+    m.m16 = S < 8192u;
+    m.kb = d.keys + kbase;
+    m.recv = reinterpret_cast<float2 *>(base + l.tail);
+    m.recc = reinterpret_cast<uint32_t *>(base + l.tail + 8ull * PF_K3_WAVES * l.rcw);
+    m.rcw = l.rcw;
+    m.sl16 = l.place == K3Place::Hbm ? nullptr : reinterpret_cast<uint16_t *>(base + l.sl16);
+    if (cached) {
+        k3_side_mem(d, r0, dir, m);
+        m.mn = m.mst = nullptr;
+        m.mo = nullptr;
+        m.gmo = d.mmr_off + 2ull * r0 + dir;
+        m.gmn = d.mmr_n + 2ull * r0 + dir;
+        m.gmst = d.mmr_start + 2ull * r0 + dir;
+        m.kbase = kbase;
+    } else {
+        m.hp = base + l.hp;
+        m.flg = base + l.flg;
+        m.ord = reinterpret_cast<uint16_t *>(base + l.ord);
+        m.aux = reinterpret_cast<uint32_t *>(base + l.tail);
+        m.mn = base + l.mn;
+        m.mst = base + l.mst;
+        m.mo = reinterpret_cast<uint32_t *>(base + l.mo);
+        m.gmo = nullptr;
+        m.gmn = m.gmst = nullptr;
+        m.kbase = 0;
+    }
 }
 
 DEV uint32_t k3_mn(const K3Mem &m, uint32_t i) {
@@ -3382,6 +3412,24 @@ DEV void k3_defer(const pf_dev_batch &d, uint32_t prob) {
     if (threadIdx.x == 0) d.k3_fb_list[atomicAdd(d.k3_fb_ctr, 1u)] = prob;
 }
 
+// Workgroup-uniform allocation of `bytes` (0: none) of the batch's HBM scratch,
+// 16 bytes aligned: its offset in ctl.scr.  False in every thread when the
+// scratch is exhausted (the host grows it and re-runs).  reuse: ctl.fail and
+// ctl.scr may still be read from an earlier allocation.
+DEV bool k3_scr_alloc(const pf_dev_batch &d, K3Ctl &ctl, uint64_t bytes, bool reuse) {
+    if (reuse) __syncthreads();
+    if (threadIdx.x == 0) {
+        ctl.fail = 0;
+        if (bytes) {
+            const unsigned long long o = atomicAdd(d.scr_ctr, (unsigned long long)align16(bytes));
+            if (o + bytes > d.scr_cap) { ctl.fail = 1; atomicOr(d.status, PF_ST_SCR_OVF); }
+            ctl.scr = o;
+        }
+    }
+    __syncthreads();
+    return !uni(ctl.fail);
+}
+
 // One greedy problem (window w, direction dir) on one workgroup.  FULL =
 // false is the main kernel's slim build: slot dictionary and lists in LDS,
 // n_cand <= 64 (register candidate list), < 8192 sites (exact-interval pick
@@ -3420,18 +3468,11 @@ DEV void k3_run(const pf_dev_batch &d, uint32_t prob, uint8_t *smem, K3Ctl &ctl,
         return;
     }
     if (tid == 0) {
-        ctl.fail = 0;
         ctl.summ = 0;
         ctl.nstrict = 0;
         ctl.mxlen = 0;
-        if (!p1_lds) {
-            const unsigned long long o = atomicAdd(d.scr_ctr, (unsigned long long)align16(need1));
-            if (o + need1 > d.scr_cap) { ctl.fail = 1; atomicOr(d.status, PF_ST_SCR_OVF); }
-            ctl.scr = o;
-        }
     }
-    __syncthreads();
-    if (uni(ctl.fail)) return;
+    if (!k3_scr_alloc(d, ctl, p1_lds ? 0ull : need1, false)) return;
     uint64_t *masks;
     uint32_t *mbase;
     if (!FULL || p1_lds) {
@@ -3462,7 +3503,6 @@ DEV void k3_run(const pf_dev_batch &d, uint32_t prob, uint8_t *smem, K3Ctl &ctl,
     // slim loop keeps no record rows (rcw = 0): either kernel runs it when the
     // problem fits this launch's LDS; the fallback kernel's general loop
     // takes the rest.
-    uint64_t off[K3_NOFF];
     const bool slots_ok = ntot < 0xFFFFu;
     // u8 count pairs when no site is covered by more than 255 reads' methmer
     // spans [st, st+n) (every count is bounded by that coverage): the deepest
@@ -3493,133 +3533,86 @@ DEV void k3_run(const pf_dev_batch &d, uint32_t prob, uint8_t *smem, K3Ctl &ctl,
         __syncthreads();
         c8 = uni(ctl.cmax) < 256u;
     }
-    const uint64_t slim_s = k3_layout(S, ntot, R, dir, summ_tot, true, 0, off, c8);
-    const uint64_t slim_n = k3_layout(S, ntot, R, dir, summ_tot, false, 0, off, c8);
+    auto lay = [&](K3Place p, uint32_t rcw, bool c8_) { return k3_layout(S, ntot, R, dir, summ_tot, p, rcw, c8_); };
+    const K3Layout l_lists = lay(K3Place::Lists, 0, c8), l_hbm = lay(K3Place::Hbm, 0, c8);
+    const K3Layout l_cache = lay(K3Place::Cache, 0, c8), l_gcnt = lay(K3Place::CacheGcnt, 0, c8);
     // the candidate slot-list cache (k3_greedy_slim CACHE) when the window's
     // lists do not fit: n_cand + 1 slots of the longest list, u16 entries
     const uint32_t CL = (uni(ctl.mxlen) + 1u) & ~1u;
     const uint32_t NCc = (uint32_t)d.win_par[w * 4 + 2];
     const bool cache_ok = slim_ok && slots_ok && NCc <= 63u && CL > 0 && CL <= 2u * NT && (d.k3_cache & 1u) != 0u;
     const bool lists_ok = slots_ok && d.k3_cache < 2u;         // (tests force the cache / the HBM lists)
-    // no per-read slot-list offsets (the cache copies from HBM), and the
-    // per-read side arrays and the T5 scratch of k3_init in HBM (k3_side_mem)
     const uint64_t cache_b = 2ull * (NCc + 1) * CL;
-    const uint64_t slim_cn = k3_layout(S, ntot, R, dir, summ_tot, false, 0, off, c8, false, 0, false, false);
-    const uint64_t slim_c = align16(slim_cn) + cache_b;
-    const bool slim_fit0 = slim_ok && ((lists_ok && slim_s <= lds) || (cache_ok && slim_c <= lds) || slim_n <= lds);
-    // path 6 (round 5): a candidate-cache problem past the budget (the main
-    // kernel's four-per-CU budget leaves the largest windows of a batch a few
-    // KB short) keeps its count table -- the bulk of its need -- in HBM
-    // scratch: it runs at once, heaviest first, instead of in the fallback
-    // kernel after the main one.  u8 count pairs only (c8); PF_K3_GCNT=force
-    // takes it for every such problem (tests)
-    const uint64_t cnt_b = align16(2ull * ntot);
-    const uint64_t slim_g =
-        align16(k3_layout(S, ntot, R, dir, summ_tot, false, 0, off, c8, false, 0, false, false, false)) + cache_b;
-    const bool gcnt = !FULL && cache_ok && c8 && slim_g <= lds && (!slim_fit0 || d.k3_gcnt != 0u);
-    const bool slim_fit = slim_fit0 || gcnt;
-    if (!FULL && !slim_fit) {
+    const uint64_t slim_c = align16(l_cache.need) + cache_b, slim_g = align16(l_gcnt.need) + cache_b;
+    // The problem's path, reported with its stats (pf_batch_k3_paths): the
+    // slim loop with 1 the slot lists in LDS, 2 the candidate cache, 3 the
+    // slot lists in HBM, in that order of preference; 6 (round 5): a
+    // candidate-cache problem past the budget (the main kernel's four-per-CU
+    // budget leaves the largest windows of a batch a few KB short) keeps its
+    // count table -- the bulk of its need -- in HBM scratch: it runs at once,
+    // heaviest first, instead of in the fallback kernel after the main one.
+    // u8 count pairs only (c8); PF_K3_GCNT=force takes it for every such
+    // problem (tests).  4 the general body (FULL); 0: deferred to it.
+    const uint32_t slim = !slim_ok ? 0u : (lists_ok && l_lists.need <= lds) ? 1u : (cache_ok && slim_c <= lds) ? 2u
+                        : l_hbm.need <= lds ? 3u : 0u;
+    const bool gcnt = !FULL && cache_ok && c8 && slim_g <= lds && (!slim || d.k3_gcnt != 0u);
+    const uint32_t path = gcnt ? 6u : slim ? slim : FULL ? 4u : 0u;
+    if (!path) {
         k3_defer(d, prob);           // keys still intact: the fallback rebuilds the dictionary
         return;
     }
-    if (gcnt) {
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned long long o = atomicAdd(d.scr_ctr, (unsigned long long)cnt_b);
-            ctl.fail = 0;
-            if (o + cnt_b > d.scr_cap) { ctl.fail = 1; atomicOr(d.status, PF_ST_SCR_OVF); }   // the host grows it, re-runs
-            ctl.scr = o;
-        }
-        __syncthreads();
-        if (uni(ctl.fail)) return;
-    }
+    if (path == 6u && !k3_scr_alloc(d, ctl, align16(2ull * ntot), true)) return;   // the count table
     if (!kd) k3_dict_rewrite<NT>(d, r0, R, S, dir, masks, mbase);
-    const uint32_t *kb = d.keys + kbase;
     if (tid == 0) {
-        // 1 slot lists in LDS, 2 the candidate cache, 3 slot lists in HBM (slim loop); 4 the general body;
-        // reported with the problem's stats (pf_batch_k3_paths)
-        ctl.path = !slim_fit ? 4u : gcnt ? 6u : (lists_ok && slim_s <= lds) ? 1u : (cache_ok && slim_c <= lds) ? 2u : 3u;
+        ctl.path = path;
 #ifdef PF_K3_PROFILE
-        ctl.need = (uint32_t)(cache_ok ? slim_c : ctl.path == 1 ? slim_s : slim_n);   // the cache layout's need (path 6: with its counts)
+        ctl.need = (uint32_t)(cache_ok ? slim_c : path == 1 ? l_lists.need : l_hbm.need);   // the cache layout's need (path 6: with its counts)
         ctl.cacheb = (uint32_t)cache_b;
 #endif
     }
-    if (slim_fit) {
-        K3Mem m;
-        uint32_t *qq = qb ? qb : cd.read;
+    K3Mem m;
+    uint32_t *qq = qb ? qb : cd.read;
+    switch (path) {
+    case 1:
+        k3_mem(d, r0, dir, kbase, S, smem, l_lists, m);
+        if (c8) k3_greedy_slim<true, NT, true, false, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq);
+        else k3_greedy_slim<true, NT, false, false, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq);
+        return;
+    case 2:
+        k3_mem(d, r0, dir, kbase, S, smem, l_cache, m);
+        if (c8) k3_greedy_slim<true, NT, true, true, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq, CL);
+        else k3_greedy_slim<true, NT, false, true, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq, CL);
+        return;
+    case 3:
+        k3_mem(d, r0, dir, kbase, S, smem, l_hbm, m);
+        if (c8) k3_greedy_slim<false, NT, true, false, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq);
+        else k3_greedy_slim<false, NT, false, false, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq);
+        return;
+    case 6:
         if constexpr (!FULL) {
-            if (gcnt) {
-                (void)k3_layout(S, ntot, R, dir, summ_tot, false, 0, off, c8, false, 0, false, false, false);
-                k3_mem(smem, off, 0, false, kb, m, false, S, false);
-                k3_side_mem(d, r0, dir, m);
-                m.cnt = reinterpret_cast<uint32_t *>(d.scr + ctl.scr);
-                m.gmo = d.mmr_off + 2ull * r0 + dir;
-                m.gmn = d.mmr_n + 2ull * r0 + dir;
-                m.gmst = d.mmr_start + 2ull * r0 + dir;
-                m.kbase = kbase;
-                m.sl16 = reinterpret_cast<uint16_t *>(smem + (slim_g - cache_b));
-                k3_greedy_slim<true, NT, true, true, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq, CL);
-                return;
-            }
-        }
-        if (lists_ok && slim_s <= lds) {
-            (void)k3_layout(S, ntot, R, dir, summ_tot, true, 0, off, c8);
-            k3_mem(smem, off, 0, true, kb, m, true, S);
-            if (c8) k3_greedy_slim<true, NT, true, false, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq);
-            else k3_greedy_slim<true, NT, false, false, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq);
-        } else if (cache_ok && slim_c <= lds) {
-            (void)k3_layout(S, ntot, R, dir, summ_tot, false, 0, off, c8, false, 0, false, false);
-            k3_mem(smem, off, 0, false, kb, m, false, S, false);
-            k3_side_mem(d, r0, dir, m);
-            m.gmo = d.mmr_off + 2ull * r0 + dir;
-            m.gmn = d.mmr_n + 2ull * r0 + dir;
-            m.gmst = d.mmr_start + 2ull * r0 + dir;
-            m.kbase = kbase;
-            m.sl16 = reinterpret_cast<uint16_t *>(smem + align16(slim_cn));
-            if (c8) k3_greedy_slim<true, NT, true, true, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq, CL);
-            else k3_greedy_slim<true, NT, false, true, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq, CL);
-        } else {
-            (void)k3_layout(S, ntot, R, dir, summ_tot, false, 0, off, c8);
-            k3_mem(smem, off, 0, false, kb, m, true, S);
-            if (c8) k3_greedy_slim<false, NT, true, false, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq);
-            else k3_greedy_slim<false, NT, false, false, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq);
+            k3_mem(d, r0, dir, kbase, S, smem, l_gcnt, m, d.scr + ctl.scr);
+            k3_greedy_slim<true, NT, true, true, CD>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan, qq, CL);
         }
         return;
     }
     if constexpr (FULL) {
+        // the general body: record rings of rcw_min records per wave, up to
+        // rcw_max in the LDS that the tables leave; else everything in HBM scratch
         const uint32_t rcw_min = 256, rcw_max = 1024;
-        const uint64_t need_s = k3_layout(S, ntot, R, dir, summ_tot, true, rcw_min, off);
-        const uint64_t need_n = k3_layout(S, ntot, R, dir, summ_tot, false, rcw_min, off);
-        if (slots_ok && need_s <= lds) {
-            (void)k3_layout(S, ntot, R, dir, summ_tot, true, rcw_min, off);
-            uint32_t rcw = (uint32_t)((lds - off[11]) / (12ull * PF_K3_WAVES));
-            rcw = rcw > rcw_max ? rcw_max : rcw;
-            (void)k3_layout(S, ntot, R, dir, summ_tot, true, rcw, off);
-            K3Mem m;
-            k3_mem(smem, off, rcw, true, kb, m, true, S);
+        auto grown = [&](const K3Layout &l) {
+            const uint32_t rcw = (uint32_t)((lds - l.tail) / (12ull * PF_K3_WAVES));
+            return lay(l.place, rcw > rcw_max ? rcw_max : rcw, false);
+        };
+        const K3Layout b_lists = lay(K3Place::Lists, rcw_min, false), b_hbm = lay(K3Place::Hbm, rcw_min, false);
+        if (slots_ok && b_lists.need <= lds) {
+            k3_mem(d, r0, dir, kbase, S, smem, grown(b_lists), m);
             k3_greedy_body<true, true>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan);
-        } else if (need_n <= lds) {
-            (void)k3_layout(S, ntot, R, dir, summ_tot, false, rcw_min, off);
-            uint32_t rcw = (uint32_t)((lds - off[11]) / (12ull * PF_K3_WAVES));
-            rcw = rcw > rcw_max ? rcw_max : rcw;
-            (void)k3_layout(S, ntot, R, dir, summ_tot, false, rcw, off);
-            K3Mem m;
-            k3_mem(smem, off, rcw, false, kb, m, true, S);
+        } else if (b_hbm.need <= lds) {
+            k3_mem(d, r0, dir, kbase, S, smem, grown(b_hbm), m);
             k3_greedy_body<false, true>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan);
         } else {
-            const uint32_t rcw = rcw_min;
-            const uint64_t need2 = align16(k3_layout(S, ntot, R, dir, summ_tot, false, rcw, off));
-            __syncthreads();
-            if (tid == 0) {
-                const unsigned long long o = atomicAdd(d.scr_ctr, (unsigned long long)need2);
-                ctl.fail = 0;
-                if (o + need2 > d.scr_cap) { ctl.fail = 1; atomicOr(d.status, PF_ST_SCR_OVF); }
-                ctl.scr = o;
-            }
-            __syncthreads();
-            if (uni(ctl.fail)) return;
-            K3Mem m;
-            k3_mem(d.scr + ctl.scr, off, rcw, false, kb, m, true, S);
+            if (!k3_scr_alloc(d, ctl, align16(b_hbm.need), true)) return;
+            k3_mem(d, r0, dir, kbase, S, d.scr + ctl.scr, b_hbm, m);
             k3_greedy_body<false, true>(d, w, dir, r0, S, R, m, ctl, cd, sh_scan);
         }
     }

@@ -118,6 +118,27 @@ def cases():
     return out
 
 
+def k3_budget_sweep():
+    """(tag, cfg, batch, env) points of the K3 path pin
+    (tests/golden/k3_paths_budget_sweep.json): two small gap-mix batches, the
+    main kernel's LDS budget from 8 KB to 48 KB under a 72 KB fallback budget,
+    and the 60x batch at 24 KB with path 6 forced.  The 72 KB fallback runs
+    every deferred problem in the slim loop; a 16 KB fallback budget (added:
+    the sweep above never reaches code 4) sends them to the general body."""
+    batches = [("c30", Config.from_coverage(30, given=False), synth(8, 30, 41, gap_mix=True)),
+               ("c60", Config.from_coverage(60, given=False), synth(6, 60, 48, gap_mix=True))]
+    pts = []
+    for tag, cfg, b in batches:
+        for lds in range(8192, 49152 + 1, 4096):
+            pts.append((f"{tag}/lds{lds}", cfg, b, {"PF_K3_LDS": str(lds), "PF_K3_LDS_FB": "73728"}))
+    tag, cfg, b = batches[1]
+    pts.append((f"{tag}/lds24576/gcnt", cfg, b, {"PF_K3_LDS": "24576", "PF_K3_LDS_FB": "73728",
+                                                 "PF_K3_CACHE": "force", "PF_K3_GCNT": "force"}))
+    for tag, cfg, b in batches:
+        pts.append((f"{tag}/lds8192/fb16384", cfg, b, {"PF_K3_LDS": "8192", "PF_K3_LDS_FB": "16384"}))
+    return pts
+
+
 def _batch_from_reads(s, e, reads):
     """One window [s, e] from [(start, end, hp, [(pos, cat), ...]), ...]."""
     off = np.cumsum([0] + [len(r[3]) for r in reads])

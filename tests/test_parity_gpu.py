@@ -174,6 +174,37 @@ def test_slot_list_sources(oracle_lib, gpu_ctx, monkeypatch, env):
         assert 3 in seen
 
 
+def test_k3_paths_budget_sweep(oracle_lib, gpu_ctx, monkeypatch):
+    """k3_run's path decision, pinned problem by problem: two small gap-mix
+    batches under every LDS budget of tests._cases.k3_budget_sweep take the
+    paths recorded in tests/golden/k3_paths_budget_sweep.json (every code 1,
+    2, 3, 4 and 6 among them; tests/golden/make_k3_paths_golden.py), with the
+    oracle's bits at every point.  The budgets are explicit, so the device's
+    LDS query plays no part."""
+    import json
+    import os
+    from tests._cases import k3_budget_sweep
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "k3_paths_budget_sweep.json")) as f:
+        golden = json.load(f)
+    sweep = k3_budget_sweep()
+    assert sorted(golden) == sorted(p[0] for p in sweep)
+    assert {1, 2, 3, 4, 6} <= {p for rows in golden.values() for row in rows for p in row}
+    refs = {}
+    for tag, cfg, batch, env in sweep:
+        for k in ("PF_K3_LDS", "PF_K3_LDS_FB", "PF_K3_CACHE", "PF_K3_GCNT"):
+            monkeypatch.delenv(k, raising=False)
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        if id(batch) not in refs:
+            refs[id(batch)] = oracle_lib.methphase(cfg, batch, n_threads=8)
+        db = gpu_ctx.upload(cfg, batch)
+        out = db.run()
+        paths = db.k3_paths().tolist()
+        db.free()
+        assert paths == golden[tag], (tag, paths, golden[tag])
+        _compare(refs[id(batch)], out, tag)
+
+
 @pytest.mark.parametrize("path", ["fold", "rows"])
 def test_greedy_pick_paths(oracle_lib, gpu_ctx, monkeypatch, path):
     """The greedy pick's alternatives give the same bits as the exact-interval
