@@ -361,6 +361,79 @@ typedef struct pf_pileup {
 int  pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, pf_pileup_t **out);
 void pf_pileup_free(pf_pileup_t *p);
 
+/* Allele-specific methylated regions of a pileup (pf_dmr.hip; no reference
+ * counterpart): a segmented scan over the sites of windows [w0, w1), all in
+ * integers.  With m1,u1,m2,u2 = cnt[0..3] of a site, n1 = m1+u1, n2 = m2+u2:
+ *   informative  n1 >= min_cov && n2 >= min_cov; every other site is
+ *                transparent (it neither joins nor breaks anything; the
+ *                "other" class cnt[4..5] is ignored);
+ *   sign         d = (m1*n2 - m2*n1) * 100, t = min_delta_pct * n1 * n2 in 64
+ *                bits: +1 if d >= t, else -1 if -d >= t, else 0;
+ *   join         two consecutive informative sites a < b are joined iff they
+ *                have the same non-zero sign, b - a <= max_gap and no break x
+ *                lies in a < x <= b (breaks: a sorted array given per call;
+ *                HP tags are comparable only inside one phase block);
+ *   run          a maximal chain of joined sites; a sign-0 site forms no run
+ *                and ends any run. */
+typedef struct pf_dmr_cfg {
+    uint32_t min_cov;          /* default 5                                      */
+    uint32_t min_delta_pct;    /* default 40; at most 100                        */
+    uint32_t max_gap;          /* default 500                                    */
+    uint32_t min_sites;        /* default 5                                      */
+} pf_dmr_cfg_t;
+
+#define PF_DMR_OPEN_LEFT  1u   /* the run's first member is the range's first informative site */
+#define PF_DMR_OPEN_RIGHT 2u   /* the run's last member is the range's last informative site   */
+typedef struct pf_dmr_run {
+    uint32_t start;            /* first member's position                        */
+    uint32_t end;              /* last member's position + 1                     */
+    uint32_t n_sites;          /* members                                        */
+    int32_t  sign;             /* +1: haplotype 1 more methylated, -1: less      */
+    uint64_t sum[4];           /* the members' m1, u1, m2, u2 summed             */
+    uint32_t open;             /* PF_DMR_OPEN_* bits                             */
+    uint32_t reserved;
+} pf_dmr_run_t;
+
+typedef struct pf_dmr {
+    uint64_t n_runs;
+    const pf_dmr_run_t *runs;  /* [n_runs] ascending                             */
+    uint64_t n_informative;    /* informative sites of the range                 */
+    float ms_kernels;          /* event-timed: the region kernels only           */
+    float ms_upload;           /* host clock: the range's pos, cnt and the breaks to the device */
+} pf_dmr_t;
+
+/* The runs of the sites of windows [w0, w1) of pile with n_sites >= min_sites
+ * or open != 0 (open runs come back unfiltered so that ranges can be stitched,
+ * pf_dmr_acc_*).  Positions must be strictly ascending over the whole range
+ * (disjoint consecutive windows; overlapping methphase windows are not):
+ * PF_ERR_ARG otherwise, and for unsorted breaks or min_delta_pct > 100.  A
+ * count above 65,535 returns PF_ERR_LIMIT.  Runs on ctx's stream; the result
+ * is exactly sized and owned by the library (pf_dmr_free), the same for any
+ * block size.  An empty range, no site and no informative site are valid,
+ * empty results.  PF_DMR_BLOCK=<n> in the environment (tests) sets the sites
+ * per workgroup, a power of two in [64, 1024]; the default is 1,024; any other
+ * value returns PF_ERR_ARG.  pf_dmr_regions_block takes the block as an
+ * argument instead (0: the environment's or the default). */
+int  pf_dmr_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w0, uint32_t w1, const pf_dmr_cfg_t *cfg,
+                    const uint32_t *breaks, uint32_t n_breaks, pf_dmr_t **out);
+int  pf_dmr_regions_block(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w0, uint32_t w1, const pf_dmr_cfg_t *cfg,
+                          const uint32_t *breaks, uint32_t n_breaks, uint32_t block, pf_dmr_t **out);
+void pf_dmr_free(pf_dmr_t *d);
+
+/* Stitching (host only): the results of consecutive ranges of one contig, in
+ * ascending position order, give the runs of the whole -- independent of how
+ * the contig was cut.  A part's open-left run joins the carried open-right run
+ * under the join rule above; a part with n_informative == 0 leaves the carry
+ * open; a part whose first informative site is in no open-left run closes it;
+ * min_sites is applied when a run closes.  pf_dmr_acc_flush closes the carry,
+ * returns every closed run so far (open = 0; pf_dmr_free) and leaves the
+ * accumulator empty for the next contig's parts under the same cfg and breaks. */
+typedef struct pf_dmr_acc pf_dmr_acc_t;
+pf_dmr_acc_t *pf_dmr_acc_new(const pf_dmr_cfg_t *cfg, const uint32_t *breaks, uint32_t n_breaks);
+int  pf_dmr_acc_add(pf_dmr_acc_t *acc, const pf_dmr_t *part);
+int  pf_dmr_acc_flush(pf_dmr_acc_t *acc, pf_dmr_t **final);
+void pf_dmr_acc_free(pf_dmr_acc_t *acc);
+
 /* -u pre-pass: hp_out[r] in {0, 1, 254} for every read of one contig. */
 int  pf_haptag_reads(pf_ctx_t *ctx, const pf_known_vars_t *known,
                      const pf_read_aln_batch_t *reads, uint8_t *hp_out);
@@ -1027,6 +1100,40 @@ typedef struct pf_hapmeth_stats {
  * fetch) with no read-back margin, pf_batch_pileup under the records' HP
  * tags, pf_write_hapmeth.  stats may be NULL. */
 int  pf_hapmeth_main(const pf_hapmeth_opts_t *o, pf_hapmeth_stats_t *stats);
+
+/* hapmeth --dmr: the allele-specific methylated regions (pf_dmr_regions,
+ * stitched by pf_dmr_acc_*) as BED lines, tab-separated:
+ *   chrom start end n_sites dir h1_meth h1_unmeth h2_meth h2_unmeth delta pooled_p
+ * dir "h1>h2" or "h1<h2"; the counts are the members' pooled sums; delta =
+ * h1_meth/(h1_meth+h1_unmeth) - h2_meth/(h2_meth+h2_unmeth) as %.4f; pooled_p
+ * the two-sided pf_fisher_exact of the pooled sums as %.6g.  pooled_p is a
+ * ranking score, not a calibrated p-value: one read contributes to many CpGs,
+ * so the pooled counts are not independent.  Lines with pooled_p > max_p are
+ * dropped (max_p 1 keeps everything).  header as in pf_write_hapmeth.  A
+ * pooled sum above INT32_MAX returns PF_ERR_LIMIT before anything is written. */
+int  pf_write_dmr(const char *path, const char *chrom, const pf_dmr_t *dmr, double max_p, int header);
+
+typedef struct pf_hapmeth_dmr {
+    pf_dmr_cfg_t cfg;
+    double max_p;              /* lines with pooled_p above it are dropped; 1 keeps all    */
+    const char *blocks_path;   /* NULL, or a phase-block GTF as methphase writes it
+                                  ({prefix}.mp.gtf; columns 4/5, 1-based): per contig each
+                                  block's 0-based start and its end are breaks            */
+} pf_hapmeth_dmr_t;
+
+typedef struct pf_hapmeth_dmr_stats {
+    uint64_t n_regions;        /* lines written to {out_prefix}.hapmeth.dmr.bed            */
+    uint64_t n_informative;    /* informative sites                                        */
+    double ms_kernels;         /* summed pf_dmr_t.ms_kernels                               */
+} pf_hapmeth_dmr_stats_t;
+
+/* pf_hapmeth_main, and with dmr != NULL also {out_prefix}.hapmeth.dmr.bed:
+ * after each job's pileup pf_dmr_regions over the job's windows, stitched per
+ * contig, flushed and appended at the contig's end; neither a job boundary nor
+ * a skipped window changes the file.  On failure both files are unlinked.
+ * dmr == NULL: exactly pf_hapmeth_main.  st and dst may be NULL. */
+int  pf_hapmeth_run(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, pf_hapmeth_stats_t *st,
+                    pf_hapmeth_dmr_stats_t *dst);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

@@ -12,8 +12,9 @@ import weakref
 
 import numpy as np
 
-from .abi import (AlnBatch, Config, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfKnownVars, PfLoadCfg, PfPileup,
-                  PfReadAlnBatch, PfWindowBatch, PfWindowOut, ReadAlnBatch, WindowBatch, WindowResult)
+from .abi import (DMR_RUN_DTYPE, AlnBatch, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
+                  PfKnownVars, PfLoadCfg, PfPileup, PfReadAlnBatch, PfWindowBatch, PfWindowOut, ReadAlnBatch,
+                  WindowBatch, WindowResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libpomfret_amd.so")
@@ -81,6 +82,17 @@ def lib():
                                       C.POINTER(C.POINTER(PfPileup))]
         L.pf_pileup_free.argtypes = [C.POINTER(PfPileup)]
         L.pf_write_hapmeth.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfPileup), C.c_uint32, C.c_uint32, C.c_int]
+        L.pf_dmr_regions.argtypes = [C.c_void_p, C.POINTER(PfPileup), C.c_uint32, C.c_uint32, C.POINTER(PfDmrCfg),
+                                     C.c_void_p, C.c_uint32, C.POINTER(C.POINTER(PfDmr))]
+        L.pf_dmr_regions_block.argtypes = [C.c_void_p, C.POINTER(PfPileup), C.c_uint32, C.c_uint32, C.POINTER(PfDmrCfg),
+                                           C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(PfDmr))]
+        L.pf_dmr_free.argtypes = [C.POINTER(PfDmr)]
+        L.pf_dmr_acc_new.argtypes = [C.POINTER(PfDmrCfg), C.c_void_p, C.c_uint32]
+        L.pf_dmr_acc_new.restype = C.c_void_p
+        L.pf_dmr_acc_add.argtypes = [C.c_void_p, C.POINTER(PfDmr)]
+        L.pf_dmr_acc_flush.argtypes = [C.c_void_p, C.POINTER(C.POINTER(PfDmr))]
+        L.pf_dmr_acc_free.argtypes = [C.c_void_p]
+        L.pf_write_dmr.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfDmr), C.c_double, C.c_int]
         if hasattr(L, "pf_haptag_reads"):
             L.pf_haptag_reads.argtypes = [C.c_void_p, C.POINTER(PfKnownVars),
                                           C.POINTER(PfReadAlnBatch), C.c_void_p]
@@ -91,6 +103,54 @@ def lib():
 def _check(rc: int, what: str):
     if rc != 0:
         raise PomfretError(f"{what}: {lib().pf_strerror(rc).decode()} ({rc})")
+
+
+def _pile_to_c(pile: dict):
+    """A pileup dict (DeviceBatch.pileup: win_off, pos, cnt) as a pf_pileup_t
+    over its arrays; returns (struct, the arrays it points into)."""
+    win_off = np.ascontiguousarray(pile["win_off"], np.uint64)
+    pos = np.ascontiguousarray(pile["pos"], np.uint32)
+    cnt = np.ascontiguousarray(np.asarray(pile["cnt"], np.uint32).reshape(-1))
+    if cnt.size != 6 * pos.size or win_off.size < 1 or int(win_off[-1]) != pos.size:
+        raise PomfretError("inconsistent pileup arrays")
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    p = PfPileup(win_off.size - 1, pos.size, win_off.ctypes.data_as(u64p), pos.ctypes.data_as(u32p),
+                 cnt.ctypes.data_as(u32p), 0.0)
+    return p, (win_off, pos, cnt)
+
+
+def _breaks(breaks):
+    """(array or None, pointer or None, n) of a sorted breaks list."""
+    if breaks is None or np.size(breaks) == 0:
+        return None, None, 0
+    b = np.ascontiguousarray(breaks, np.uint32).ravel()
+    return b, b.ctypes.data, b.size
+
+
+def _dmr_dict(d) -> dict:
+    """A pf_dmr_t as dict(start, end, n_sites, sign, sum [n, 4], open,
+    n_informative, ms, ms_upload): copies."""
+    n = int(d.n_runs)
+    if n:
+        rec = np.ctypeslib.as_array(C.cast(d.runs, C.POINTER(C.c_uint8)), (n * DMR_RUN_DTYPE.itemsize,)).copy()
+        rec = rec.view(DMR_RUN_DTYPE)
+    else:
+        rec = np.zeros(0, DMR_RUN_DTYPE)
+    return dict(start=rec["start"].copy(), end=rec["end"].copy(), n_sites=rec["n_sites"].copy(),
+                sign=rec["sign"].copy(), sum=rec["sum"].copy().reshape(n, 4), open=rec["open"].copy(),
+                n_informative=int(d.n_informative), ms=float(d.ms_kernels), ms_upload=float(d.ms_upload))
+
+
+def _dmr_to_c(part: dict):
+    """The inverse of _dmr_dict; returns (struct, the array it points into)."""
+    n = int(np.size(part["start"]))
+    rec = np.zeros(max(n, 1), DMR_RUN_DTYPE)
+    for k in ("start", "end", "n_sites", "sign", "open"):
+        rec[k][:n] = np.asarray(part[k]).ravel()
+    rec["sum"][:n] = np.asarray(part["sum"], np.uint64).reshape(n, 4)
+    from .abi import PfDmrRun
+    d = PfDmr(n, C.cast(rec.ctypes.data, C.POINTER(PfDmrRun)), int(part.get("n_informative", 0)), 0.0, 0.0)
+    return d, rec
 
 
 class _PfGaps(C.Structure):
@@ -351,6 +411,27 @@ class Context:
         n = C.c_uint64(0)
         _check(lib().pf_selftest(self.handle, C.byref(n)), "pf_selftest")
         return int(n.value)
+
+    def dmr_regions(self, pile: dict, cfg: DmrConfig = None, breaks=None, w0: int = 0, w1: int = None,
+                    block: int = 0) -> dict:
+        """The allele-specific runs of the sites of windows [w0, w1) of a
+        pileup dict (pf_dmr_regions; include/pomfret_amd.h has the rules):
+        dict(start, end, n_sites, sign, sum [n, 4] = pooled m1, u1, m2, u2,
+        open (bit 0 / 1: the run touches the range's first / last informative
+        site), n_informative, ms the region kernels' time, ms_upload).  Runs
+        below cfg.min_sites are returned only when open (pipeline.dmr_stitch).
+        breaks: sorted positions no run crosses.  block: sites per workgroup
+        (tests; 0: PF_DMR_BLOCK of the environment or the default)."""
+        p, keep = _pile_to_c(pile)
+        c = (cfg or DmrConfig()).to_c()
+        b, bp, nb = _breaks(breaks)
+        d = C.POINTER(PfDmr)()
+        _check(lib().pf_dmr_regions_block(self.handle, C.byref(p), int(w0), p.n_windows if w1 is None else int(w1),
+                                          C.byref(c), bp, nb, int(block), C.byref(d)), "pf_dmr_regions")
+        try:
+            return _dmr_dict(d.contents)
+        finally:
+            lib().pf_dmr_free(d)
 
     def haptag_reads(self, known: KnownVars, reads: ReadAlnBatch) -> np.ndarray:
         out = np.zeros(max(reads.n_reads, 1), np.uint8)

@@ -361,6 +361,54 @@ class PfHapmethStats(C.Structure):
                 ("n_sites", C.c_uint64), ("ms_kernels", C.c_double)]
 
 
+class PfDmrCfg(C.Structure):
+    """pf_dmr_cfg_t."""
+    _fields_ = [("min_cov", C.c_uint32), ("min_delta_pct", C.c_uint32), ("max_gap", C.c_uint32),
+                ("min_sites", C.c_uint32)]
+
+
+@dataclass
+class DmrConfig:
+    """Parameters of the allele-specific region call (pf_dmr_regions): a CpG
+    takes part with min_cov calls on each haplotype, carries a direction when
+    the haplotypes' methylation differs by min_delta_pct percent, and chains
+    to the next one of its direction within max_gap bases; a region needs
+    min_sites CpGs."""
+    min_cov: int = 5
+    min_delta_pct: int = 40
+    max_gap: int = 500
+    min_sites: int = 5
+
+    def to_c(self) -> PfDmrCfg:
+        return PfDmrCfg(self.min_cov, self.min_delta_pct, self.max_gap, self.min_sites)
+
+
+class PfDmrRun(C.Structure):
+    """pf_dmr_run_t."""
+    _fields_ = [("start", C.c_uint32), ("end", C.c_uint32), ("n_sites", C.c_uint32), ("sign", C.c_int32),
+                ("sum", C.c_uint64 * 4), ("open", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+DMR_RUN_DTYPE = np.dtype([("start", np.uint32), ("end", np.uint32), ("n_sites", np.uint32), ("sign", np.int32),
+                          ("sum", np.uint64, (4,)), ("open", np.uint32), ("reserved", np.uint32)])
+
+
+class PfDmr(C.Structure):
+    """pf_dmr_t: the runs of one range (pf_dmr_regions) or the stitched regions."""
+    _fields_ = [("n_runs", C.c_uint64), ("runs", C.POINTER(PfDmrRun)), ("n_informative", C.c_uint64),
+                ("ms_kernels", C.c_float), ("ms_upload", C.c_float)]
+
+
+class PfHapmethDmr(C.Structure):
+    """pf_hapmeth_dmr_t (pf_hapmeth_run)."""
+    _fields_ = [("cfg", PfDmrCfg), ("max_p", C.c_double), ("blocks_path", C.c_char_p)]
+
+
+class PfHapmethDmrStats(C.Structure):
+    """pf_hapmeth_dmr_stats_t."""
+    _fields_ = [("n_regions", C.c_uint64), ("n_informative", C.c_uint64), ("ms_kernels", C.c_double)]
+
+
 class PfAlnBatch(C.Structure):
     _fields_ = [("n_windows", C.c_uint32), ("n_recs", C.c_uint32)] + [
         (n, C.c_void_p) for n in (

@@ -7,7 +7,9 @@
  *   pomfret-amd methphase -o out --vcf phased.vcf.gz [-c 60] [-u] [-t N] [--write-bam] [--gpus G] reads.bam
  *   pomfret-amd report    -o out --vcf phased.vcf.gz [-c C] [--chunk-size S --chunk-stride D] reads.bam
  *   pomfret-amd varhaptag -o out.bam in.vcf in.bam
- *   pomfret-amd hapmeth   -o out [-r chrom[:beg-end]] [--chunk-size N] [-q mapq] [-L minlen] [--host-fetch] tagged.bam
+ *   pomfret-amd hapmeth   -o out [-r chrom[:beg-end]] [--chunk-size N] [-q mapq] [-L minlen] [--host-fetch]
+ *                         [--dmr [--dmr-min-cov N] [--dmr-delta PCT] [--dmr-gap N] [--dmr-min-sites N] [--dmr-max-p P]
+ *                         [--dmr-blocks blocks.gtf]] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
  * cliopt_haptag_t (cli.c:332-343); the -c arithmetic (cov/10, cov/4), the
@@ -90,7 +92,8 @@ static void help_methphase(const char *prefix) {
 }
 
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
-       O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF };
+       O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
+       O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -105,6 +108,10 @@ static const struct option longopts[] = {
     {"host-fetch", no_argument, 0, O_HFETCH},
     {"mask-bed", required_argument, 0, O_MBED},  {"mask-variants", no_argument, 0, O_MVAR},
     {"ref", required_argument, 0, O_REF},
+    {"dmr", no_argument, 0, O_DMR},              {"dmr-min-cov", required_argument, 0, O_DMR_COV},
+    {"dmr-delta", required_argument, 0, O_DMR_DELTA}, {"dmr-gap", required_argument, 0, O_DMR_GAP},
+    {"dmr-min-sites", required_argument, 0, O_DMR_SITES}, {"dmr-max-p", required_argument, 0, O_DMR_MAXP},
+    {"dmr-blocks", required_argument, 0, O_DMR_BLOCKS},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -287,6 +294,18 @@ static void help_hapmeth(void) {
     fprintf(stderr, "  --gpus [opt] The GPU to use (the first of the list). [0]\n");
     fprintf(stderr, "  --job-windows [opt] Windows per device job. [1024]\n");
     fprintf(stderr, "  -v     [opt] Print the run's counts and the pileup kernels' time.\n");
+    fprintf(stderr, "  --dmr  [opt] Also write {out_prefix}.hapmeth.dmr.bed: the regions where one haplotype is methylated\n"
+                    "               and the other is not (runs of CpGs of one direction), with the pooled counts, the\n"
+                    "               difference of the pooled methylation levels and pooled_p, the two-sided Fisher test\n"
+                    "               of the pooled counts.  pooled_p is a ranking score, not a calibrated p-value: one\n"
+                    "               read contributes to many CpGs, so the pooled counts are not independent.\n");
+    fprintf(stderr, "  --dmr-min-cov [opt] Calls per haplotype a CpG needs to take part. [5]\n");
+    fprintf(stderr, "  --dmr-delta [opt] Least difference of the two haplotypes' methylation at a CpG, in percent. [40]\n");
+    fprintf(stderr, "  --dmr-gap [opt] Largest distance between neighbouring CpGs of one region, in bases. [500]\n");
+    fprintf(stderr, "  --dmr-min-sites [opt] CpGs a region needs. [5]\n");
+    fprintf(stderr, "  --dmr-max-p [opt] Drop regions whose pooled_p (a ranking score, see --dmr) is above this. [1]\n");
+    fprintf(stderr, "  --dmr-blocks FILE [opt] Phase blocks as a GTF (methphase's {prefix}.mp.gtf): no region crosses a\n"
+                    "               block's start or end, since HP tags are comparable only inside one block.\n");
 }
 
 /* hapmeth: one device, the jobs one after another (pf_hapmeth_main) */
@@ -296,7 +315,13 @@ static int hapmeth(int argc, char **argv) {
     op.out_prefix = "pomfret";
     op.load.min_mapq = 10; op.load.min_len = 0; op.load.qual_lo = 100; op.load.qual_hi = 156;
     op.threads = 1;
-    int o, csize = 100000, jobw = 0;
+    pf_hapmeth_dmr_t dm;
+    memset(&dm, 0, sizeof dm);
+    dm.cfg.min_cov = 5; dm.cfg.min_delta_pct = 40; dm.cfg.max_gap = 500; dm.cfg.min_sites = 5;
+    dm.max_p = 1.0;
+    int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0;
+    long dcov = 5, ddelta = 40, dgap = 500, dsites = 5;
+    char *end;
     if (argc == 1) { help_hapmeth(); return 1; }
     optind = 1;
     while ((o = getopt_long(argc, argv, "vho:r:q:L:t:", longopts, NULL)) >= 0) {
@@ -314,6 +339,13 @@ static int hapmeth(int argc, char **argv) {
         case O_GPUS: op.device = atoi(optarg); break;
         case O_JOBW: jobw = atoi(optarg); break;
         case O_HFETCH: op.host_fetch = 1; break;
+        case O_DMR: dmr = 1; break;
+        case O_DMR_COV: dmr_opt = 1; dcov = strtol(optarg, &end, 10); if (*end || !*optarg) dcov = -1; break;
+        case O_DMR_DELTA: dmr_opt = 1; ddelta = strtol(optarg, &end, 10); if (*end || !*optarg) ddelta = -1; break;
+        case O_DMR_GAP: dmr_opt = 1; dgap = strtol(optarg, &end, 10); if (*end || !*optarg) dgap = -1; break;
+        case O_DMR_SITES: dmr_opt = 1; dsites = strtol(optarg, &end, 10); if (*end || !*optarg) dsites = -1; break;
+        case O_DMR_MAXP: dmr_opt = 1; dm.max_p = strtod(optarg, &end); if (*end || !*optarg) dm.max_p = -1.0; break;
+        case O_DMR_BLOCKS: dmr_opt = 1; dm.blocks_path = optarg; break;
         default:
             fprintf(stderr, "[E::parse_cli_hapmeth] unknown or incomplete option \"%s\"\n", argv[optind - 1]);
             return 1;
@@ -328,6 +360,14 @@ static int hapmeth(int argc, char **argv) {
     if (op.load.qual_hi > 255 || op.load.qual_hi <= 127) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --hi (%d)\n", op.load.qual_hi); return 1; }
     if (csize <= 0) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] invalid chunk size\n"); return 1; }
     if (!op.out_prefix[0]) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] no output prefix given\n"); return 1; }
+    if (dmr_opt && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-* options need --dmr\n"); return 1; }
+    if (dcov < 1 || dcov > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-min-cov (1 .. 65535)\n"); return 1; }
+    if (ddelta < 1 || ddelta > 100) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-delta (1 .. 100)\n"); return 1; }
+    if (dgap < 1 || dgap > 0x7FFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-gap\n"); return 1; }
+    if (dsites < 1 || dsites > 0x7FFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-min-sites\n"); return 1; }
+    if (!(dm.max_p >= 0.0 && dm.max_p <= 1.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-max-p (0 .. 1)\n"); return 1; }
+    dm.cfg.min_cov = (uint32_t)dcov; dm.cfg.min_delta_pct = (uint32_t)ddelta;
+    dm.cfg.max_gap = (uint32_t)dgap; dm.cfg.min_sites = (uint32_t)dsites;
     if (op.load.min_mapq < 0) op.load.min_mapq = 0;
     if (op.load.min_len < 0) op.load.min_len = 0;
     if (op.threads < 1) op.threads = 1;
@@ -335,12 +375,16 @@ static int hapmeth(int argc, char **argv) {
     op.chunk_size = (uint32_t)csize;
     op.job_windows = jobw > 0 ? (uint32_t)jobw : 0;
     pf_hapmeth_stats_t st;
-    const int rc = pf_hapmeth_main(&op, &st);
+    pf_hapmeth_dmr_stats_t dst;
+    const int rc = pf_hapmeth_run(&op, dmr ? &dm : NULL, &st, &dst);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;
     }
     fprintf(stderr, "[M::main] %llu sites written to %s.hapmeth.bed\n", (unsigned long long)st.n_sites, op.out_prefix);
+    if (dmr)
+        fprintf(stderr, "[M::main] %llu regions written to %s.hapmeth.dmr.bed\n", (unsigned long long)dst.n_regions,
+                op.out_prefix);
     return 0;
 }
 

@@ -43,6 +43,12 @@
 #define PF_PILE_THREADS 1024        /* 16 waves: a window's reads are searched 64 per wave at once */
 #define PF_PILE_WAVES (PF_PILE_THREADS / PF_WAVE)
 #define PF_PILE_SCAN_THREADS 1024
+#ifndef PF_DMR_BLOCK
+#define PF_DMR_BLOCK 1024           /* sites per workgroup of the region kernels, and the PF_DMR_BLOCK=<n> override's
+                                      upper bound (measured against 256 .. 4096: profiles/dmr/README.md) */
+#endif
+#define PF_DMR_THREADS 256          /* each thread folds PF_DMR_BLOCK / PF_DMR_THREADS consecutive sites */
+#define PF_DMR_WAVES (PF_DMR_THREADS / PF_WAVE)
 #define PF_NONE 0xFFFFFFFFu
 
 /* status bits */

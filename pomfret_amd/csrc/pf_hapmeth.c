@@ -14,7 +14,13 @@
  *                     margin (a read overlapping two windows is decoded in
  *                     both and counted in each inside that window's range, so
  *                     nothing counts twice), pileup under the records' HP
- *                     tags, write.
+ *                     tags, write;
+ *   pf_dmr_acc_*:     the stitching of pf_dmr_regions results of consecutive
+ *                     ranges of one contig (host only);
+ *   pf_write_dmr:     the stitched regions as BED lines (host only);
+ *   pf_hapmeth_run:   pf_hapmeth_main, and with --dmr the regions of every
+ *                     contig: each job's sites through pf_dmr_regions into the
+ *                     contig's accumulator, flushed and appended at its end.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -41,6 +47,158 @@ int pf_write_hapmeth(const char *path, const char *chrom, const pf_pileup_t *p, 
     const int bad = ferror(fp);
     if (fclose(fp) != 0 || bad) return -1;
     return PF_OK;
+}
+
+/* ---- allele-specific regions: stitching and the writer */
+struct pf_dmr_acc {
+    pf_dmr_cfg_t cfg;
+    uint32_t *brk;
+    uint32_t n_brk;
+    pf_dmr_run_t *runs;        /* closed and kept, ascending */
+    size_t n, m;
+    pf_dmr_run_t carry;        /* the run still open to the right */
+    int have;
+    uint32_t last_end;         /* parts must ascend */
+    uint64_t n_inf;
+};
+
+pf_dmr_acc_t *pf_dmr_acc_new(const pf_dmr_cfg_t *cfg, const uint32_t *breaks, uint32_t n_breaks) {
+    if (!cfg || (n_breaks && !breaks)) return NULL;
+    for (uint32_t i = 1; i < n_breaks; i++)
+        if (breaks[i] < breaks[i - 1]) return NULL;
+    pf_dmr_acc_t *a = (pf_dmr_acc_t *)calloc(1, sizeof *a);
+    if (!a) return NULL;
+    a->cfg = *cfg;
+    if (n_breaks) {
+        a->brk = (uint32_t *)malloc(4ull * n_breaks);
+        if (!a->brk) { free(a); return NULL; }
+        memcpy(a->brk, breaks, 4ull * n_breaks);
+        a->n_brk = n_breaks;
+    }
+    return a;
+}
+
+void pf_dmr_acc_free(pf_dmr_acc_t *a) {
+    if (!a) return;
+    free(a->brk);
+    free(a->runs);
+    free(a);
+}
+
+/* breaks <= p */
+static uint32_t acc_rank(const pf_dmr_acc_t *a, uint32_t p) {
+    uint32_t lo = 0, hi = a->n_brk;
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a->brk[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+/* a run closes: min_sites applies here */
+static int acc_close(pf_dmr_acc_t *a, const pf_dmr_run_t *r) {
+    if (r->n_sites < a->cfg.min_sites) return PF_OK;
+    if (a->n == a->m) {
+        const size_t nm = a->m ? a->m * 2 : 64;
+        pf_dmr_run_t *p = (pf_dmr_run_t *)realloc(a->runs, nm * sizeof *p);
+        if (!p) return PF_ERR_NOMEM;
+        a->runs = p;
+        a->m = nm;
+    }
+    a->runs[a->n] = *r;
+    a->runs[a->n].open = 0;
+    a->runs[a->n].reserved = 0;
+    a->n++;
+    return PF_OK;
+}
+
+int pf_dmr_acc_add(pf_dmr_acc_t *a, const pf_dmr_t *part) {
+    if (!a || !part || (part->n_runs && !part->runs)) return PF_ERR_ARG;
+    if (part->n_informative == 0) return part->n_runs ? PF_ERR_ARG : PF_OK;     /* the carry stays open */
+    for (uint64_t i = 0; i < part->n_runs; i++) {
+        const pf_dmr_run_t *r = part->runs + i;
+        const uint32_t lo = i ? part->runs[i - 1].end : a->last_end;
+        if (r->end <= r->start || r->start < lo || (r->sign != 1 && r->sign != -1) ||
+            ((r->open & PF_DMR_OPEN_LEFT) && i != 0) || ((r->open & PF_DMR_OPEN_RIGHT) && i + 1 != part->n_runs))
+            return PF_ERR_ARG;
+    }
+    a->n_inf += part->n_informative;
+    uint64_t i = 0;
+    int rc = PF_OK;
+    if (a->have) {
+        const pf_dmr_run_t *r0 = part->n_runs && (part->runs[0].open & PF_DMR_OPEN_LEFT) ? part->runs : NULL;
+        const uint32_t last = a->carry.end - 1u;             /* the carry's last member */
+        if (r0 && r0->sign == a->carry.sign && r0->start - last <= a->cfg.max_gap &&
+            acc_rank(a, last) == acc_rank(a, r0->start)) {
+            a->carry.end = r0->end;
+            a->carry.n_sites += r0->n_sites;
+            for (int k = 0; k < 4; k++) a->carry.sum[k] += r0->sum[k];
+            i = 1;
+            if (!(r0->open & PF_DMR_OPEN_RIGHT)) { rc = acc_close(a, &a->carry); a->have = 0; }
+        } else {
+            rc = acc_close(a, &a->carry);
+            a->have = 0;
+        }
+    }
+    for (; i < part->n_runs && !rc; i++) {
+        const pf_dmr_run_t *r = part->runs + i;
+        if (r->open & PF_DMR_OPEN_RIGHT) { a->carry = *r; a->have = 1; }
+        else rc = acc_close(a, r);
+    }
+    if (part->n_runs) a->last_end = part->runs[part->n_runs - 1].end;
+    return rc;
+}
+
+int pf_dmr_acc_flush(pf_dmr_acc_t *a, pf_dmr_t **final) {
+    if (!a || !final) return PF_ERR_ARG;
+    *final = NULL;
+    if (a->have) {
+        const int rc = acc_close(a, &a->carry);
+        if (rc) return rc;
+        a->have = 0;
+    }
+    pf_dmr_t *d = (pf_dmr_t *)calloc(1, sizeof *d);
+    if (!d) return PF_ERR_NOMEM;
+    d->n_runs = a->n;
+    d->runs = a->runs;                                       /* handed over: pf_dmr_free */
+    d->n_informative = a->n_inf;
+    a->runs = NULL;
+    a->n = a->m = 0;
+    a->n_inf = 0;
+    a->last_end = 0;
+    *final = d;
+    return PF_OK;
+}
+
+static int write_dmr(const char *path, const char *chrom, const pf_dmr_t *d, double max_p, int header, uint64_t *n_lines) {
+    if (n_lines) *n_lines = 0;
+    const uint64_t n = d ? d->n_runs : 0;
+    if (!path || (n && (!chrom || !d->runs))) return PF_ERR_ARG;
+    for (uint64_t i = 0; i < n; i++)
+        for (int k = 0; k < 4; k++)
+            if (d->runs[i].sum[k] > (uint64_t)INT32_MAX) return PF_ERR_LIMIT;
+    FILE *fp = fopen(path, header ? "w" : "a");
+    if (!fp) return -1;
+    if (header) fprintf(fp, "#chrom\tstart\tend\tn_sites\tdir\th1_meth\th1_unmeth\th2_meth\th2_unmeth\tdelta\tpooled_p\n");
+    for (uint64_t i = 0; i < n; i++) {
+        const pf_dmr_run_t *r = d->runs + i;
+        const uint64_t m1 = r->sum[0], u1 = r->sum[1], m2 = r->sum[2], u2 = r->sum[3];
+        double two = 1.0;
+        (void)pf_fisher_exact((int)m1, (int)u1, (int)m2, (int)u2, NULL, NULL, &two);
+        if (two > max_p) continue;
+        const double delta = (m1 + u1 ? (double)m1 / (double)(m1 + u1) : 0.0) - (m2 + u2 ? (double)m2 / (double)(m2 + u2) : 0.0);
+        fprintf(fp, "%s\t%u\t%u\t%u\t%s\t%llu\t%llu\t%llu\t%llu\t%.4f\t%.6g\n", chrom, r->start, r->end, r->n_sites,
+                r->sign > 0 ? "h1>h2" : "h1<h2", (unsigned long long)m1, (unsigned long long)u1, (unsigned long long)m2,
+                (unsigned long long)u2, delta, two);
+        if (n_lines) ++*n_lines;
+    }
+    const int bad = ferror(fp);
+    if (fclose(fp) != 0 || bad) return -1;
+    return PF_OK;
+}
+
+int pf_write_dmr(const char *path, const char *chrom, const pf_dmr_t *dmr, double max_p, int header) {
+    return write_dmr(path, chrom, dmr, max_p, header, NULL);
 }
 
 /* "chrom" or "chrom:beg-end" / "chrom:beg" (1-based inclusive, commas allowed)
@@ -85,6 +243,14 @@ typedef struct {
     pf_load_cfg_t lc;
     char *path;
     pf_hapmeth_stats_t st;
+    /* --dmr */
+    const pf_hapmeth_dmr_t *dmr;
+    char *dpath;
+    pf_gaps_t *blocks;         /* dmr->blocks_path's phase blocks */
+    uint32_t *brk;             /* the current contig's breaks */
+    uint32_t n_brk;
+    pf_dmr_acc_t *acc;         /* the current contig's accumulator */
+    pf_hapmeth_dmr_stats_t dst;
 } hm_t;
 
 /* one job: the windows ws/we[0, n) of chrom */
@@ -113,10 +279,62 @@ static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, co
         H->st.n_sites += pile->n_sites;
         H->st.ms_kernels += pile->ms_kernels;
     }
+    if (!rc && H->dmr) {
+        pf_dmr_t *part = NULL;
+        rc = pf_dmr_regions(H->ctx, pile, 0, n, &H->dmr->cfg, H->brk, H->n_brk, &part);
+        if (!rc) rc = pf_dmr_acc_add(H->acc, part);
+        if (!rc) H->dst.ms_kernels += part->ms_kernels;
+        pf_dmr_free(part);
+    }
     pf_pileup_free(pile);
     if (db) pf_batch_free(db);
     if (F) pf_bam_dev_fetch_free(F);
     if (recs) pf_bam_records_free(recs);
+    return rc;
+}
+
+static int cmp_u32(const void *a, const void *b) {
+    const uint32_t x = *(const uint32_t *)a, y = *(const uint32_t *)b;
+    return x < y ? -1 : x > y;
+}
+
+/* the breaks of chrom: each phase block's 0-based start and its end, sorted */
+static int hm_breaks(hm_t *H, const char *chrom) {
+    free(H->brk);
+    H->brk = NULL;
+    H->n_brk = 0;
+    const pf_gaps_t *g = H->blocks;
+    if (!g) return PF_OK;
+    uint32_t c = 0;
+    while (c < g->n_contigs && strcmp(g->names[c], chrom)) c++;
+    if (c == g->n_contigs) return PF_OK;
+    const uint64_t r0 = g->raw_off[c], nr = g->raw_off[c + 1] - r0;       /* nr gaps: nr + 1 blocks */
+    if (nr > 0x3FFFFFFFull) return PF_ERR_LIMIT;
+    H->brk = (uint32_t *)malloc(8ull * (nr + 1));
+    if (!H->brk) return PF_ERR_NOMEM;
+    for (uint64_t k = 0; k <= nr; k++) {
+        const uint32_t bs = k ? g->raw_end[r0 + k - 1] : g->abs_start[c]; /* 1-based */
+        const uint32_t be = k < nr ? g->raw_start[r0 + k] : g->abs_end[c];
+        H->brk[H->n_brk++] = bs ? bs - 1u : 0u;
+        H->brk[H->n_brk++] = be;
+    }
+    qsort(H->brk, H->n_brk, 4, cmp_u32);
+    return PF_OK;
+}
+
+/* the contig's regions are complete: close the carry, append */
+static int hm_flush(hm_t *H, const char *chrom) {
+    pf_dmr_t *fin = NULL;
+    uint64_t lines = 0;
+    int rc = pf_dmr_acc_flush(H->acc, &fin);
+    if (!rc) rc = write_dmr(H->dpath, chrom, fin, H->dmr->max_p, 0, &lines);
+    if (!rc) {
+        H->dst.n_regions += lines;
+        H->dst.n_informative += fin->n_informative;
+    }
+    pf_dmr_free(fin);
+    pf_dmr_acc_free(H->acc);
+    H->acc = NULL;
     return rc;
 }
 
@@ -125,6 +343,12 @@ static int hm_span(hm_t *H, int32_t tid, uint32_t s, uint32_t e, uint32_t chunk,
     const char *chrom = pf_bam_target_name(H->bam, tid);
     uint32_t n = 0;
     int rc = PF_OK;
+    if (H->dmr) {
+        rc = hm_breaks(H, chrom);
+        if (rc) return rc;
+        H->acc = pf_dmr_acc_new(&H->dmr->cfg, H->brk, H->n_brk);
+        if (!H->acc) return PF_ERR_NOMEM;
+    }
     for (uint64_t a = s; a < e && !rc; a += chunk) {
         const uint64_t b = a + chunk < e ? a + chunk : e;
         H->st.n_windows++;
@@ -137,15 +361,24 @@ static int hm_span(hm_t *H, int32_t tid, uint32_t s, uint32_t e, uint32_t chunk,
         if (++n == jw) { rc = hm_job(H, chrom, n, ws, we); n = 0; }
     }
     if (!rc && n) rc = hm_job(H, chrom, n, ws, we);
+    if (!rc && H->dmr) rc = hm_flush(H, chrom);
     return rc;
 }
 
 int pf_hapmeth_main(const pf_hapmeth_opts_t *o, pf_hapmeth_stats_t *stats) {
+    return pf_hapmeth_run(o, NULL, stats, NULL);
+}
+
+int pf_hapmeth_run(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, pf_hapmeth_stats_t *stats,
+                   pf_hapmeth_dmr_stats_t *dstats) {
     if (stats) memset(stats, 0, sizeof *stats);
+    if (dstats) memset(dstats, 0, sizeof *dstats);
     if (!o || !o->bam_path || !o->out_prefix || !o->out_prefix[0]) return PF_ERR_ARG;
+    if (dmr && (dmr->cfg.min_delta_pct > 100u || !(dmr->max_p >= 0.0))) return PF_ERR_ARG;
     hm_t H;
     memset(&H, 0, sizeof H);
     H.o = o;
+    H.dmr = dmr;
     H.lc = o->load;
     /* the batch's phasing parameters are not used by the pileup: the reference's defaults */
     H.cfg.k = 3; H.cfg.k_span = 5000; H.cfg.cov_for_selection = 6; H.cfg.n_cand = 15; H.cfg.hard_cov = 15;
@@ -165,38 +398,60 @@ int pf_hapmeth_main(const pf_hapmeth_opts_t *o, pf_hapmeth_stats_t *stats) {
         tid1 = tid0 + 1;
     }
     uint32_t *ws = NULL, *we = NULL;
-    int made = 0;
+    int made = 0, dmade = 0;
+    if (!rc && dmr && dmr->blocks_path) {
+        rc = pf_interval_gaps(dmr->blocks_path, PF_INTERVALS_GTF, 0, &H.blocks);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot read the phase blocks of %s\n", dmr->blocks_path);
+    }
     if (!rc) {
         rc = pf_ctx_create(o->device, &H.ctx);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] no usable GPU (device %d): %s\n", o->device, pf_strerror(rc));
     }
     if (!rc) {
-        const size_t l = strlen(o->out_prefix) + 16;
+        const size_t l = strlen(o->out_prefix) + 24;
         H.path = (char *)malloc(l);
+        H.dpath = (char *)malloc(l);
         ws = (uint32_t *)malloc(4ull * jw);
         we = (uint32_t *)malloc(4ull * jw);
-        if (!H.path || !ws || !we) rc = PF_ERR_NOMEM;
-        else snprintf(H.path, l, "%s.hapmeth.bed", o->out_prefix);
+        if (!H.path || !H.dpath || !ws || !we) rc = PF_ERR_NOMEM;
+        else {
+            snprintf(H.path, l, "%s.hapmeth.bed", o->out_prefix);
+            snprintf(H.dpath, l, "%s.hapmeth.dmr.bed", o->out_prefix);
+        }
     }
     if (!rc) {
         rc = pf_write_hapmeth(H.path, NULL, NULL, 0, 0, 1);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.path);
         else made = 1;
     }
+    if (!rc && dmr) {
+        rc = write_dmr(H.dpath, NULL, NULL, 1.0, 1, NULL);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.dpath);
+        else dmade = 1;
+    }
     for (int32_t t = tid0; t < tid1 && !rc; t++) {
         if (!o->region) { s = 0; e = pf_bam_target_len(H.bam, t); }
         rc = hm_span(&H, t, s, e, chunk, jw, ws, we);
     }
     if (rc && made) (void)unlink(H.path);              /* no truncated output behind a failure */
+    if (rc && dmade) (void)unlink(H.dpath);
     if (!rc && o->verbose)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu windows (%llu without reads in the index, skipped), %llu records, "
                 "%llu sites, pileup kernels %.3f ms\n", (unsigned long long)H.st.n_windows,
                 (unsigned long long)H.st.n_skipped, (unsigned long long)H.st.n_records,
                 (unsigned long long)H.st.n_sites, H.st.ms_kernels);
+    if (!rc && o->verbose && dmr)
+        fprintf(stderr, "[M::pf_hapmeth_main] %llu informative sites, %llu regions, region kernels %.3f ms\n",
+                (unsigned long long)H.dst.n_informative, (unsigned long long)H.dst.n_regions, H.dst.ms_kernels);
     if (stats) *stats = H.st;
+    if (dstats) *dstats = H.dst;
     free(ws);
     free(we);
     free(H.path);
+    free(H.dpath);
+    free(H.brk);
+    pf_dmr_acc_free(H.acc);
+    pf_gaps_free(H.blocks);
     if (H.ctx) pf_ctx_destroy(H.ctx);
     pf_bam_close(H.bam);
     return rc;

@@ -32,8 +32,9 @@ from typing import Callable, Dict, List, Optional
 import numpy as np
 
 from ._lib import (INTERVALS_GTF, INTERVALS_TSV, INTERVALS_VCF, PomfretError, _blocks_contigs, _check,  # noqa: F401
-                   _gaps_contigs, _PfBlocks, _PfGaps, lib)
-from .abi import Config, LoadConfig, PfCfg, PfHapmethOpts, PfHapmethStats, PfLoadCfg, PfPileup
+                   _breaks, _dmr_dict, _dmr_to_c, _gaps_contigs, _PfBlocks, _PfGaps, lib)
+from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfHapmethDmrStats, PfHapmethOpts,
+                  PfHapmethStats, PfLoadCfg, PfPileup)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
 JOB_WINDOWS, JOB_HAPTAG = 0, 1
@@ -115,6 +116,8 @@ def _bind():
     L.pf_mask_contig.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(C.c_uint64)]
     L.pf_mask_free.argtypes = [vp]
     L.pf_hapmeth_main.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethStats)]
+    L.pf_hapmeth_run.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethStats),
+                                 C.POINTER(PfHapmethDmrStats)]
     L.pf_tags_new.restype = vp
     L.pf_tags_free.argtypes = [vp]
     L.pf_tags_size.argtypes = [vp]
@@ -477,23 +480,74 @@ def report_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cov: i
 
 def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk_size: int = 100_000,
                   lcfg: Optional[LoadConfig] = None, host_fetch: bool = False, threads: int = 1, device: int = 0,
-                  job_windows: int = 0) -> Dict:
-    """`pomfret-amd hapmeth` (pf_hapmeth_main): the per-haplotype CpG
+                  job_windows: int = 0, dmr: Optional[DmrConfig] = None, dmr_max_p: float = 1.0,
+                  dmr_blocks: Optional[str] = None) -> Dict:
+    """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
     the other reads, the two-sided Fisher p of haplotype 1 against 2).
     region: chrom or chrom:beg-end (1-based inclusive), None: every contig.
     chunk_size: bases per window, the fetch unit.  lcfg None: -q 10, -L 0,
     ML bands 100 / 156.  Returns dict(path, n_windows, n_skipped (windows the
-    index holds no chunk for: not fetched), n_records, n_sites, ms_kernels)."""
+    index holds no chunk for: not fetched), n_records, n_sites, ms_kernels).
+    dmr: a DmrConfig also writes out_prefix + .hapmeth.dmr.bed, the regions
+    where the haplotypes differ (`--dmr`; dmr_max_p drops regions whose
+    pooled_p -- a ranking score, not a calibrated p-value -- is above it;
+    dmr_blocks: a phase-block GTF no region crosses a block edge of), and adds
+    dmr_path, n_regions, n_informative and dmr_ms_kernels to the dict."""
     L = _bind()
     lc = lcfg or LoadConfig(min_len=0)
     o = PfHapmethOpts(bam.encode(), out_prefix.encode(), region.encode() if region else None, int(chunk_size),
                       int(job_windows), lc.to_c(), int(threads), int(bool(host_fetch)), int(device), 0)
     st = PfHapmethStats()
-    _check(L.pf_hapmeth_main(C.byref(o), C.byref(st)), "pf_hapmeth_main")
-    return dict(path=out_prefix + ".hapmeth.bed", n_windows=int(st.n_windows), n_skipped=int(st.n_skipped),
-                n_records=int(st.n_records), n_sites=int(st.n_sites), ms_kernels=float(st.ms_kernels))
+    if dmr is None:
+        _check(L.pf_hapmeth_main(C.byref(o), C.byref(st)), "pf_hapmeth_main")
+    else:
+        d = PfHapmethDmr(dmr.to_c(), float(dmr_max_p), dmr_blocks.encode() if dmr_blocks else None)
+        dst = PfHapmethDmrStats()
+        _check(L.pf_hapmeth_run(C.byref(o), C.byref(d), C.byref(st), C.byref(dst)), "pf_hapmeth_run")
+    res = dict(path=out_prefix + ".hapmeth.bed", n_windows=int(st.n_windows), n_skipped=int(st.n_skipped),
+               n_records=int(st.n_records), n_sites=int(st.n_sites), ms_kernels=float(st.ms_kernels))
+    if dmr is not None:
+        res.update(dmr_path=out_prefix + ".hapmeth.dmr.bed", n_regions=int(dst.n_regions),
+                   n_informative=int(dst.n_informative), dmr_ms_kernels=float(dst.ms_kernels))
+    return res
+
+
+def dmr_stitch(parts, cfg: Optional[DmrConfig] = None, breaks=None) -> Dict:
+    """The regions of one contig from the Context.dmr_regions results of its
+    consecutive ranges, in ascending order (pf_dmr_acc_*, host only): the same
+    whatever the cut.  Returns the dict of Context.dmr_regions (open all 0,
+    every run at least cfg.min_sites long)."""
+    L = _bind()
+    c = (cfg or DmrConfig()).to_c()
+    b, bp, nb = _breaks(breaks)
+    acc = L.pf_dmr_acc_new(C.byref(c), bp, nb)
+    if not acc:
+        raise PomfretError("pf_dmr_acc_new: bad arguments (breaks must be sorted)")
+    try:
+        for part in parts:
+            d, keep = _dmr_to_c(part)
+            _check(L.pf_dmr_acc_add(acc, C.byref(d)), "pf_dmr_acc_add")
+        fin = C.POINTER(PfDmr)()
+        _check(L.pf_dmr_acc_flush(acc, C.byref(fin)), "pf_dmr_acc_flush")
+        try:
+            return _dmr_dict(fin.contents)
+        finally:
+            L.pf_dmr_free(fin)
+    finally:
+        L.pf_dmr_acc_free(acc)
+
+
+def write_dmr(path: str, chrom: str, dmr: Dict, max_p: float = 1.0, header: bool = True):
+    """Regions (dmr_stitch's dict) as hapmeth --dmr BED lines (pf_write_dmr,
+    host only): chrom, start, end, n_sites, dir, the pooled counts, delta and
+    pooled_p (a ranking score, not a calibrated p-value); regions with
+    pooled_p > max_p are dropped.  header: create the file with the column
+    names first; else append."""
+    L = _bind()
+    d, keep = _dmr_to_c(dmr)
+    _check(L.pf_write_dmr(path.encode(), chrom.encode(), C.byref(d), float(max_p), int(bool(header))), "pf_write_dmr")
 
 
 def write_hapmeth(path: str, chrom: str, pile: Dict, header: bool = True, w0: int = 0, w1: Optional[int] = None):
