@@ -434,6 +434,61 @@ int  pf_dmr_acc_add(pf_dmr_acc_t *acc, const pf_dmr_t *part);
 int  pf_dmr_acc_flush(pf_dmr_acc_t *acc, pf_dmr_t **final);
 void pf_dmr_acc_free(pf_dmr_acc_t *acc);
 
+/* Read-label permutation test of windows (pf_perm.hip; no reference
+ * counterpart): for each window [ws, we) of a batch, how often a random
+ * relabelling of its reads separates the two pooled methylation fractions at
+ * least as far as the reads' own tags do.  The read is the exchangeable unit,
+ * so the p-value (hits + 1) / (n_perm + 1) holds under the correlation of one
+ * read's calls, which the pooled Fisher test of pf_write_dmr ignores.  All in
+ * integers; windows may overlap, every window is tested on its own.
+ *   participating  the window's reads with tag 0 or 1 and at least one call
+ *                  entry with ws <= pos < we and cat 0 or 1, in the batch's
+ *                  read order, numbered i = 0 .. n-1;
+ *   counts         m_i / u_i the read's meth / unmeth entries in range (a
+ *                  duplicate entry counts twice, cat 2 nowhere); n1 the
+ *                  participating reads tagged 0, M = sum m_i, N = sum (m_i + u_i);
+ *   statistic      for a labelling L with M0, N0 the sums over the reads
+ *                  labelled 0: A(L) = |M0*N - M*N0|, D(L) = N0*(N - N0); A/D is
+ *                  the absolute difference of the two pooled fractions.  A0,
+ *                  D0 are those of the true tags;
+ *   keys           uint32 arithmetic with wrap-around;
+ *                  mix(x): x ^= x>>16; x *= 0x7feb352d; x ^= x>>15;
+ *                          x *= 0x846ca68b; x ^= x>>16;
+ *                  base = mix(seed ^ mix(ws ^ mix(we))): the salt is the
+ *                  window's coordinates, not its index, so a region's result
+ *                  does not depend on the batch it lands in;
+ *                  key(b, i) = mix(mix(base + b) ^ i);
+ *   permutation b  (0 <= b < n_perm) rank(i) = the number of j with
+ *                  (key(b,j), j) < (key(b,i), i) lexicographically; read i is
+ *                  labelled 0 iff rank(i) < n1; b is a hit iff D_b > 0 and
+ *                  A_b*D0 >= A0*D_b, compared as 128-bit values;
+ *   status         0 tested; 1 nothing to test (n1 == 0, n1 == n or D0 == 0),
+ *                  hits 0; 2 n > PF_PERM_MAX_READS, hits 0 (no error). */
+#define PF_PERM_MAX_READS 4096u
+#define PF_PERM_MAX_PERM  1000000u
+typedef struct pf_perm {
+    uint32_t n_windows;
+    uint32_t n_perm;
+    uint32_t seed;
+    const uint32_t *n_reads;   /* [n_windows*2] participating reads tagged 0, tagged 1 */
+    const uint64_t *sum;       /* [n_windows*4] their m1, u1, m2, u2 in range    */
+    const uint32_t *hits;      /* [n_windows]                                    */
+    const uint32_t *status;    /* [n_windows] 0, 1, 2 as above                   */
+    float ms_kernels;          /* event-timed: the kernels only                  */
+} pf_perm_t;
+/* Batches and tags as in pf_batch_pileup: calls-level and record-level batches
+ * (the latter run their load stage first); read_hp NULL uses the batch's own
+ * tags, else [n_hp] tags replace them for this call only; PF_ERR_ARG while a
+ * launched run is unfinished; the batch is left as it was.  n_perm outside
+ * [1, PF_PERM_MAX_PERM] returns PF_ERR_ARG, N >= 2^31 in any window
+ * PF_ERR_LIMIT.  The result is owned by the library (pf_perm_free) and depends
+ * on neither launch geometry nor atomic order.  PF_PERM_THREADS=<64|256|1024>
+ * in the environment (tests) sets the workgroup size; the default is 256; any
+ * other value returns PF_ERR_ARG. */
+int  pf_batch_permtest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t n_perm,
+                       uint32_t seed, pf_perm_t **out);
+void pf_perm_free(pf_perm_t *p);
+
 /* -u pre-pass: hp_out[r] in {0, 1, 254} for every read of one contig. */
 int  pf_haptag_reads(pf_ctx_t *ctx, const pf_known_vars_t *known,
                      const pf_read_aln_batch_t *reads, uint8_t *hp_out);
@@ -1134,6 +1189,45 @@ typedef struct pf_hapmeth_dmr_stats {
  * dmr == NULL: exactly pf_hapmeth_main.  st and dst may be NULL. */
 int  pf_hapmeth_run(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, pf_hapmeth_stats_t *st,
                     pf_hapmeth_dmr_stats_t *dst);
+
+/* hapmeth --dmr --dmr-perm: pf_write_dmr's eleven columns unchanged, followed
+ * by reads_h1 reads_h2 perm_p.  Window k of perm (pf_batch_permtest) is run k
+ * of dmr: reads_h1 / reads_h2 its participating reads tagged 0 / 1, perm_p =
+ * (hits + 1) / (n_perm + 1) as %.6g, or "." when the window's status is not 0.
+ * Unlike pooled_p, perm_p is a p-value: the reads' labels are permuted, so the
+ * correlation of one read's calls is part of the null distribution; its
+ * smallest value is 1 / (n_perm + 1).  max_p, header and the INT32_MAX limit
+ * as in pf_write_dmr.  PF_ERR_ARG when perm is NULL or holds fewer windows
+ * than dmr has runs. */
+int  pf_write_dmr_perm(const char *path, const char *chrom, const pf_dmr_t *dmr, const pf_perm_t *perm, double max_p,
+                       int header);
+
+typedef struct pf_hapmeth_perm {
+    uint32_t n_perm;           /* permutations per region, 1 .. PF_PERM_MAX_PERM           */
+    uint32_t seed;             /* the CLI's default is 1                                   */
+} pf_hapmeth_perm_t;
+
+typedef struct pf_hapmeth_perm_stats {
+    uint64_t n_tested;         /* lines written with a numeric perm_p                      */
+    uint64_t n_untested;       /* lines written with "."                                   */
+    uint64_t n_records;        /* records fetched by the second pass                       */
+    double ms_kernels;         /* summed pf_perm_t.ms_kernels                              */
+} pf_hapmeth_perm_stats_t;
+
+/* pf_hapmeth_run, and with perm != NULL a second pass at each contig's end,
+ * where its regions are final: the regions that pass dmr->max_p become the
+ * windows [start, end) of jobs of job_windows windows, each fetched like a job
+ * of the first pass (the device fetch or the host fetch, no read-back margin,
+ * the same loader configuration) and tested by pf_batch_permtest under the
+ * records' HP tags; every read overlapping a region is one whole read of that
+ * region's window, so the result depends on neither chunk_size, job_windows
+ * nor the fetch kind.  The region file is then written by pf_write_dmr_perm.
+ * perm == NULL: exactly pf_hapmeth_run (pst is zeroed).  perm without dmr, or
+ * n_perm outside [1, PF_PERM_MAX_PERM], returns PF_ERR_ARG.  A failing fetch
+ * of the second pass (PF_ERR_LIMIT included) fails the run and unlinks both
+ * files.  st, dst and pst may be NULL. */
+int  pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
+                         pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst, pf_hapmeth_perm_stats_t *pst);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

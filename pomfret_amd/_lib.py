@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from .abi import (DMR_RUN_DTYPE, AlnBatch, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
-                  PfKnownVars, PfLoadCfg, PfPileup, PfReadAlnBatch, PfWindowBatch, PfWindowOut, ReadAlnBatch,
+                  PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfReadAlnBatch, PfWindowBatch, PfWindowOut, ReadAlnBatch,
                   WindowBatch, WindowResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -93,6 +93,10 @@ def lib():
         L.pf_dmr_acc_flush.argtypes = [C.c_void_p, C.POINTER(C.POINTER(PfDmr))]
         L.pf_dmr_acc_free.argtypes = [C.c_void_p]
         L.pf_write_dmr.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfDmr), C.c_double, C.c_int]
+        L.pf_batch_permtest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                        C.POINTER(C.POINTER(PfPerm))]
+        L.pf_perm_free.argtypes = [C.POINTER(PfPerm)]
+        L.pf_write_dmr_perm.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfDmr), C.POINTER(PfPerm), C.c_double, C.c_int]
         if hasattr(L, "pf_haptag_reads"):
             L.pf_haptag_reads.argtypes = [C.c_void_p, C.POINTER(PfKnownVars),
                                           C.POINTER(PfReadAlnBatch), C.c_void_p]
@@ -583,6 +587,37 @@ class DeviceBatch:
             return dict(win_off=win_off, pos=pos, cnt=cnt.reshape(n, 3, 2), ms=float(r.ms_kernels))
         finally:
             lib().pf_pileup_free(p)
+
+    def permtest(self, n_perm: int, seed: int = 1, read_hp=None) -> dict:
+        """Read-label permutation test of every window of the batch
+        (pf_batch_permtest; include/pomfret_amd.h has the definition):
+        dict(n_reads [W, 2] the participating reads tagged 0 / 1, sum [W, 4]
+        their m1, u1, m2, u2 inside the window, hits [W] the permutations at
+        least as extreme as the true labels, status [W] (0 tested, 1 nothing
+        to test, 2 more than 4,096 participating reads), n_perm, seed, ms the
+        kernel's time).  p = (hits + 1) / (n_perm + 1) where status is 0.
+        read_hp as in pileup."""
+        hp_ptr, n_hp = None, 0
+        if read_hp is not None:
+            hp = np.zeros(np.size(read_hp) + 1, np.uint8)
+            hp[:-1] = np.asarray(read_hp, np.uint8).ravel()
+            hp_ptr, n_hp = hp.ctypes.data, hp.size - 1
+        if not 0 <= int(n_perm) <= 0xFFFFFFFF or not 0 <= int(seed) <= 0xFFFFFFFF:
+            raise PomfretError("pf_batch_permtest: n_perm and seed are 32-bit unsigned")
+        p = C.POINTER(PfPerm)()
+        _check(lib().pf_batch_permtest(self.ctx.handle, self.handle, hp_ptr, n_hp, int(n_perm), int(seed), C.byref(p)),
+               "pf_batch_permtest")
+        try:
+            r = p.contents
+            W = int(r.n_windows)
+
+            def arr(ptr, n, dt):
+                return np.ctypeslib.as_array(ptr, (n,)).copy() if W else np.zeros(0, dt)
+            return dict(n_reads=arr(r.n_reads, 2 * W, np.uint32).reshape(W, 2), sum=arr(r.sum, 4 * W, np.uint64).reshape(W, 4),
+                        hits=arr(r.hits, W, np.uint32), status=arr(r.status, W, np.uint32), n_perm=int(r.n_perm),
+                        seed=int(r.seed), ms=float(r.ms_kernels))
+        finally:
+            lib().pf_perm_free(p)
 
     def stats(self) -> np.ndarray:
         """Per-(window, dir) counters of the last run: [W, 2, 8] (see pf_batch_stats)."""

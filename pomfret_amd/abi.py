@@ -409,6 +409,24 @@ class PfHapmethDmrStats(C.Structure):
     _fields_ = [("n_regions", C.c_uint64), ("n_informative", C.c_uint64), ("ms_kernels", C.c_double)]
 
 
+class PfPerm(C.Structure):
+    """pf_perm_t: the permutation test of a batch's windows (pf_batch_permtest)."""
+    _fields_ = [("n_windows", C.c_uint32), ("n_perm", C.c_uint32), ("seed", C.c_uint32),
+                ("n_reads", C.POINTER(C.c_uint32)), ("sum", C.POINTER(C.c_uint64)), ("hits", C.POINTER(C.c_uint32)),
+                ("status", C.POINTER(C.c_uint32)), ("ms_kernels", C.c_float)]
+
+
+class PfHapmethPerm(C.Structure):
+    """pf_hapmeth_perm_t (pf_hapmeth_run_perm)."""
+    _fields_ = [("n_perm", C.c_uint32), ("seed", C.c_uint32)]
+
+
+class PfHapmethPermStats(C.Structure):
+    """pf_hapmeth_perm_stats_t."""
+    _fields_ = [("n_tested", C.c_uint64), ("n_untested", C.c_uint64), ("n_records", C.c_uint64),
+                ("ms_kernels", C.c_double)]
+
+
 class PfAlnBatch(C.Structure):
     _fields_ = [("n_windows", C.c_uint32), ("n_recs", C.c_uint32)] + [
         (n, C.c_void_p) for n in (

@@ -1659,6 +1659,24 @@ extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *rea
     return done(PF_OK);
 }
 
+// ---- the batch's reads and calls for a consumer in another file (pf_perm.hip):
+// pf_batch_pileup's checks and load stage, then the device view with W, R and N
+// as they stand after the load.  Not part of the public header.
+extern "C" int pf_batch_calls_view(pf_ctx_t *ctx, pf_dbatch_t *b, pf_dev_batch *view) {
+    if (!ctx || !b || !view || b->ctx != ctx) return PF_ERR_ARG;
+    if (b->n_launch != b->n_finish) return PF_ERR_ARG;       // a run is in flight
+    HIPCHK(hipSetDevice(ctx->device));
+    if (b->has_aln) {
+        const int rc = run_debug(b, 0);
+        if (rc) return rc;
+    }
+    *view = b->d;
+    view->W = b->W;
+    view->R = b->R;
+    view->N = b->N;
+    return PF_OK;
+}
+
 extern "C" int pf_methphase_run(pf_ctx_t *ctx, pf_dbatch_t *b, pf_window_out_t *out) {
     int rc = pf_methphase_launch(ctx, b);
     if (rc) return rc;

@@ -9,7 +9,7 @@
  *   pomfret-amd varhaptag -o out.bam in.vcf in.bam
  *   pomfret-amd hapmeth   -o out [-r chrom[:beg-end]] [--chunk-size N] [-q mapq] [-L minlen] [--host-fetch]
  *                         [--dmr [--dmr-min-cov N] [--dmr-delta PCT] [--dmr-gap N] [--dmr-min-sites N] [--dmr-max-p P]
- *                         [--dmr-blocks blocks.gtf]] tagged.bam
+ *                         [--dmr-blocks blocks.gtf] [--dmr-perm N [--dmr-seed S]]] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
  * cliopt_haptag_t (cli.c:332-343); the -c arithmetic (cov/10, cov/4), the
@@ -93,7 +93,7 @@ static void help_methphase(const char *prefix) {
 
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
        O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
-       O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS };
+       O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -112,6 +112,7 @@ static const struct option longopts[] = {
     {"dmr-delta", required_argument, 0, O_DMR_DELTA}, {"dmr-gap", required_argument, 0, O_DMR_GAP},
     {"dmr-min-sites", required_argument, 0, O_DMR_SITES}, {"dmr-max-p", required_argument, 0, O_DMR_MAXP},
     {"dmr-blocks", required_argument, 0, O_DMR_BLOCKS},
+    {"dmr-perm", required_argument, 0, O_DMR_PERM}, {"dmr-seed", required_argument, 0, O_DMR_SEED},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -306,6 +307,11 @@ static void help_hapmeth(void) {
     fprintf(stderr, "  --dmr-max-p [opt] Drop regions whose pooled_p (a ranking score, see --dmr) is above this. [1]\n");
     fprintf(stderr, "  --dmr-blocks FILE [opt] Phase blocks as a GTF (methphase's {prefix}.mp.gtf): no region crosses a\n"
                     "               block's start or end, since HP tags are comparable only inside one block.\n");
+    fprintf(stderr, "  --dmr-perm N [opt] Test every region with N permutations of its reads' haplotype labels and add\n"
+                    "               the columns reads_h1, reads_h2 and perm_p = (hits + 1) / (N + 1): a p-value that\n"
+                    "               holds although one read contributes to many CpGs (\".\" where a region has reads of\n"
+                    "               one haplotype only, or more than 4096).  N in 1 .. 1000000. [0: off]\n");
+    fprintf(stderr, "  --dmr-seed S [opt] Seed of the permutations. [1]\n");
 }
 
 /* hapmeth: one device, the jobs one after another (pf_hapmeth_main) */
@@ -319,8 +325,10 @@ static int hapmeth(int argc, char **argv) {
     memset(&dm, 0, sizeof dm);
     dm.cfg.min_cov = 5; dm.cfg.min_delta_pct = 40; dm.cfg.max_gap = 500; dm.cfg.min_sites = 5;
     dm.max_p = 1.0;
+    pf_hapmeth_perm_t pm;
+    pm.n_perm = 0; pm.seed = 1;
     int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0;
-    long dcov = 5, ddelta = 40, dgap = 500, dsites = 5;
+    long dcov = 5, ddelta = 40, dgap = 500, dsites = 5, dperm = 0, dseed = 1;
     char *end;
     if (argc == 1) { help_hapmeth(); return 1; }
     optind = 1;
@@ -346,6 +354,8 @@ static int hapmeth(int argc, char **argv) {
         case O_DMR_SITES: dmr_opt = 1; dsites = strtol(optarg, &end, 10); if (*end || !*optarg) dsites = -1; break;
         case O_DMR_MAXP: dmr_opt = 1; dm.max_p = strtod(optarg, &end); if (*end || !*optarg) dm.max_p = -1.0; break;
         case O_DMR_BLOCKS: dmr_opt = 1; dm.blocks_path = optarg; break;
+        case O_DMR_PERM: dmr_opt = 1; dperm = strtol(optarg, &end, 10); if (*end || !*optarg) dperm = -1; break;
+        case O_DMR_SEED: dmr_opt = 1; dseed = strtol(optarg, &end, 10); if (*end || !*optarg) dseed = -1; break;
         default:
             fprintf(stderr, "[E::parse_cli_hapmeth] unknown or incomplete option \"%s\"\n", argv[optind - 1]);
             return 1;
@@ -366,6 +376,9 @@ static int hapmeth(int argc, char **argv) {
     if (dgap < 1 || dgap > 0x7FFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-gap\n"); return 1; }
     if (dsites < 1 || dsites > 0x7FFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-min-sites\n"); return 1; }
     if (!(dm.max_p >= 0.0 && dm.max_p <= 1.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-max-p (0 .. 1)\n"); return 1; }
+    if (dperm < 0 || dperm > 1000000) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-perm (0 .. 1000000)\n"); return 1; }
+    if (dseed < 0 || dseed > 0xFFFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-seed (0 .. 4294967295)\n"); return 1; }
+    pm.n_perm = (uint32_t)dperm; pm.seed = (uint32_t)dseed;
     dm.cfg.min_cov = (uint32_t)dcov; dm.cfg.min_delta_pct = (uint32_t)ddelta;
     dm.cfg.max_gap = (uint32_t)dgap; dm.cfg.min_sites = (uint32_t)dsites;
     if (op.load.min_mapq < 0) op.load.min_mapq = 0;
@@ -376,7 +389,8 @@ static int hapmeth(int argc, char **argv) {
     op.job_windows = jobw > 0 ? (uint32_t)jobw : 0;
     pf_hapmeth_stats_t st;
     pf_hapmeth_dmr_stats_t dst;
-    const int rc = pf_hapmeth_run(&op, dmr ? &dm : NULL, &st, &dst);
+    pf_hapmeth_perm_stats_t pst;
+    const int rc = pf_hapmeth_run_perm(&op, dmr ? &dm : NULL, pm.n_perm ? &pm : NULL, &st, &dst, &pst);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;
@@ -385,6 +399,8 @@ static int hapmeth(int argc, char **argv) {
     if (dmr)
         fprintf(stderr, "[M::main] %llu regions written to %s.hapmeth.dmr.bed\n", (unsigned long long)dst.n_regions,
                 op.out_prefix);
+    if (pm.n_perm)
+        fprintf(stderr, "[M::main] %llu of them with a permutation p-value\n", (unsigned long long)pst.n_tested);
     return 0;
 }
 

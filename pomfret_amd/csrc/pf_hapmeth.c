@@ -20,7 +20,12 @@
  *   pf_write_dmr:     the stitched regions as BED lines (host only);
  *   pf_hapmeth_run:   pf_hapmeth_main, and with --dmr the regions of every
  *                     contig: each job's sites through pf_dmr_regions into the
- *                     contig's accumulator, flushed and appended at its end.
+ *                     contig's accumulator, flushed and appended at its end;
+ *   pf_hapmeth_run_perm: pf_hapmeth_run, and with --dmr-perm a second pass at
+ *                     each contig's end: its regions become the windows of
+ *                     jobs fetched like the first pass's and tested by
+ *                     pf_batch_permtest, and pf_write_dmr_perm's three columns
+ *                     follow pf_write_dmr's.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -170,16 +175,23 @@ int pf_dmr_acc_flush(pf_dmr_acc_t *a, pf_dmr_t **final) {
     return PF_OK;
 }
 
-static int write_dmr(const char *path, const char *chrom, const pf_dmr_t *d, double max_p, int header, uint64_t *n_lines) {
+/* perm NULL: pf_write_dmr's eleven columns; else window k of perm is run k and
+ * three columns follow.  n_lines: lines written; n_dot: of those, with "." */
+static int write_dmr(const char *path, const char *chrom, const pf_dmr_t *d, const pf_perm_t *perm, double max_p,
+                     int header, uint64_t *n_lines, uint64_t *n_dot) {
     if (n_lines) *n_lines = 0;
+    if (n_dot) *n_dot = 0;
     const uint64_t n = d ? d->n_runs : 0;
     if (!path || (n && (!chrom || !d->runs))) return PF_ERR_ARG;
+    if (perm && n && (perm->n_windows < n || !perm->n_reads || !perm->hits || !perm->status)) return PF_ERR_ARG;
     for (uint64_t i = 0; i < n; i++)
         for (int k = 0; k < 4; k++)
             if (d->runs[i].sum[k] > (uint64_t)INT32_MAX) return PF_ERR_LIMIT;
     FILE *fp = fopen(path, header ? "w" : "a");
     if (!fp) return -1;
-    if (header) fprintf(fp, "#chrom\tstart\tend\tn_sites\tdir\th1_meth\th1_unmeth\th2_meth\th2_unmeth\tdelta\tpooled_p\n");
+    if (header)
+        fprintf(fp, "#chrom\tstart\tend\tn_sites\tdir\th1_meth\th1_unmeth\th2_meth\th2_unmeth\tdelta\tpooled_p%s\n",
+                perm ? "\treads_h1\treads_h2\tperm_p" : "");
     for (uint64_t i = 0; i < n; i++) {
         const pf_dmr_run_t *r = d->runs + i;
         const uint64_t m1 = r->sum[0], u1 = r->sum[1], m2 = r->sum[2], u2 = r->sum[3];
@@ -187,9 +199,19 @@ static int write_dmr(const char *path, const char *chrom, const pf_dmr_t *d, dou
         (void)pf_fisher_exact((int)m1, (int)u1, (int)m2, (int)u2, NULL, NULL, &two);
         if (two > max_p) continue;
         const double delta = (m1 + u1 ? (double)m1 / (double)(m1 + u1) : 0.0) - (m2 + u2 ? (double)m2 / (double)(m2 + u2) : 0.0);
-        fprintf(fp, "%s\t%u\t%u\t%u\t%s\t%llu\t%llu\t%llu\t%llu\t%.4f\t%.6g\n", chrom, r->start, r->end, r->n_sites,
+        fprintf(fp, "%s\t%u\t%u\t%u\t%s\t%llu\t%llu\t%llu\t%llu\t%.4f\t%.6g", chrom, r->start, r->end, r->n_sites,
                 r->sign > 0 ? "h1>h2" : "h1<h2", (unsigned long long)m1, (unsigned long long)u1, (unsigned long long)m2,
                 (unsigned long long)u2, delta, two);
+        if (perm) {
+            fprintf(fp, "\t%u\t%u\t", perm->n_reads[2 * i], perm->n_reads[2 * i + 1]);
+            if (perm->status[i] == 0)
+                fprintf(fp, "%.6g", ((double)perm->hits[i] + 1.0) / ((double)perm->n_perm + 1.0));
+            else {
+                fputc('.', fp);
+                if (n_dot) ++*n_dot;
+            }
+        }
+        fputc('\n', fp);
         if (n_lines) ++*n_lines;
     }
     const int bad = ferror(fp);
@@ -198,7 +220,13 @@ static int write_dmr(const char *path, const char *chrom, const pf_dmr_t *d, dou
 }
 
 int pf_write_dmr(const char *path, const char *chrom, const pf_dmr_t *dmr, double max_p, int header) {
-    return write_dmr(path, chrom, dmr, max_p, header, NULL);
+    return write_dmr(path, chrom, dmr, NULL, max_p, header, NULL, NULL);
+}
+
+int pf_write_dmr_perm(const char *path, const char *chrom, const pf_dmr_t *dmr, const pf_perm_t *perm, double max_p,
+                      int header) {
+    if (!perm) return PF_ERR_ARG;
+    return write_dmr(path, chrom, dmr, perm, max_p, header, NULL, NULL);
 }
 
 /* "chrom" or "chrom:beg-end" / "chrom:beg" (1-based inclusive, commas allowed)
@@ -251,7 +279,29 @@ typedef struct {
     uint32_t n_brk;
     pf_dmr_acc_t *acc;         /* the current contig's accumulator */
     pf_hapmeth_dmr_stats_t dst;
+    /* --dmr-perm */
+    const pf_hapmeth_perm_t *perm;
+    uint32_t jw;               /* windows per job */
+    pf_hapmeth_perm_stats_t pst;
 } hm_t;
+
+/* the fetch of one job, the same in both passes: the records of the windows
+ * ws/we[0, n) of chrom as a record-level batch, no read-back margin */
+static int hm_fetch(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, const uint32_t *we, pf_dbatch_t **db,
+                    pf_bam_dev_fetch_t **F, pf_bam_records_t **recs, uint64_t *n_records) {
+    int rc;
+    if (H->o->host_fetch) {
+        rc = pf_bam_fetch_windows(H->bam, chrom, n, ws, we, 0, H->o->threads > 0 ? H->o->threads : 1, recs);
+        if (!rc) {
+            *n_records += (*recs)->aln.n_recs;
+            rc = pf_batch_upload_aln(H->ctx, &H->cfg, &H->lc, &(*recs)->aln, db);
+        }
+    } else {
+        rc = pf_batch_upload_bam(H->ctx, &H->cfg, &H->lc, H->bam, chrom, n, ws, we, 0, 0, db, F);
+        if (!rc) *n_records += (*F)->n_recs;
+    }
+    return rc;
+}
 
 /* one job: the windows ws/we[0, n) of chrom */
 static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, const uint32_t *we) {
@@ -259,17 +309,7 @@ static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, co
     pf_bam_dev_fetch_t *F = NULL;
     pf_bam_records_t *recs = NULL;
     pf_pileup_t *pile = NULL;
-    int rc;
-    if (H->o->host_fetch) {
-        rc = pf_bam_fetch_windows(H->bam, chrom, n, ws, we, 0, H->o->threads > 0 ? H->o->threads : 1, &recs);
-        if (!rc) {
-            H->st.n_records += recs->aln.n_recs;
-            rc = pf_batch_upload_aln(H->ctx, &H->cfg, &H->lc, &recs->aln, &db);
-        }
-    } else {
-        rc = pf_batch_upload_bam(H->ctx, &H->cfg, &H->lc, H->bam, chrom, n, ws, we, 0, 0, &db, &F);
-        if (!rc) H->st.n_records += F->n_recs;
-    }
+    int rc = hm_fetch(H, chrom, n, ws, we, &db, &F, &recs, &H->st.n_records);
     if (rc == PF_ERR_LIMIT)
         fprintf(stderr, "[E::pf_hapmeth_main] %s:%u-%u: a window exceeds a device limit (65,535 records per window); "
                 "try a smaller --chunk-size\n", chrom, ws[0] + 1, we[n - 1]);
@@ -322,16 +362,83 @@ static int hm_breaks(hm_t *H, const char *chrom) {
     return PF_OK;
 }
 
-/* the contig's regions are complete: close the carry, append */
+/* --dmr-perm's second pass over a contig's final regions: the regions that
+ * pass max_p are the windows [start, end) of jobs of at most jw windows, each
+ * fetched as in the first pass and tested under the records' HP tags; run k's
+ * result lands in window k of *out (malloc'ed arrays: pf_perm_free) */
+static int hm_perm(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t **out) {
+    *out = NULL;
+    const uint64_t n = fin->n_runs;
+    if (n > 0xFFFFFFFFull) return PF_ERR_LIMIT;
+    pf_perm_t *P = (pf_perm_t *)calloc(1, sizeof *P);
+    if (!P) return PF_ERR_NOMEM;
+    uint32_t *nr = (uint32_t *)calloc(2 * n + 1, 4), *hits = (uint32_t *)calloc(n + 1, 4), *stat = (uint32_t *)calloc(n + 1, 4);
+    uint64_t *sum = (uint64_t *)calloc(4 * n + 1, 8);
+    uint32_t *ws = (uint32_t *)malloc(4ull * H->jw), *we = (uint32_t *)malloc(4ull * H->jw);
+    uint64_t *idx = (uint64_t *)malloc(8ull * H->jw);
+    P->n_windows = (uint32_t)n; P->n_perm = H->perm->n_perm; P->seed = H->perm->seed;
+    P->n_reads = nr; P->sum = sum; P->hits = hits; P->status = stat;
+    int rc = (nr && hits && stat && sum && ws && we && idx) ? PF_OK : PF_ERR_NOMEM;
+    uint32_t k = 0;
+    for (uint64_t i = 0; i <= n && !rc; i++) {
+        if (i < n) {
+            const pf_dmr_run_t *r = fin->runs + i;
+            double two = 1.0;
+            if ((r->sum[0] | r->sum[1] | r->sum[2] | r->sum[3]) > (uint64_t)INT32_MAX) rc = PF_ERR_LIMIT;   /* as the writer */
+            else (void)pf_fisher_exact((int)r->sum[0], (int)r->sum[1], (int)r->sum[2], (int)r->sum[3], NULL, NULL, &two);
+            if (rc || two > H->dmr->max_p) continue;         /* no line: nothing to test */
+            ws[k] = r->start; we[k] = r->end; idx[k] = i;
+            k++;
+        }
+        if (k == 0 || (k < H->jw && i < n)) continue;
+        pf_dbatch_t *db = NULL;
+        pf_bam_dev_fetch_t *F = NULL;
+        pf_bam_records_t *recs = NULL;
+        pf_perm_t *part = NULL;
+        rc = hm_fetch(H, chrom, k, ws, we, &db, &F, &recs, &H->pst.n_records);
+        if (rc == PF_ERR_LIMIT)
+            fprintf(stderr, "[E::pf_hapmeth_main] %s:%u-%u: a region exceeds a device limit (65,535 records per window)\n",
+                    chrom, ws[0] + 1, we[k - 1]);
+        if (!rc) rc = pf_batch_permtest(H->ctx, db, NULL, 0, H->perm->n_perm, H->perm->seed, &part);
+        if (!rc && part->n_windows != k) rc = PF_ERR_INTERNAL;
+        for (uint32_t j = 0; j < k && !rc; j++) {
+            nr[2 * idx[j]] = part->n_reads[2 * j];
+            nr[2 * idx[j] + 1] = part->n_reads[2 * j + 1];
+            for (int q = 0; q < 4; q++) sum[4 * idx[j] + q] = part->sum[4 * j + q];
+            hits[idx[j]] = part->hits[j];
+            stat[idx[j]] = part->status[j];
+        }
+        if (!rc) H->pst.ms_kernels += part->ms_kernels;
+        pf_perm_free(part);
+        if (db) pf_batch_free(db);
+        if (F) pf_bam_dev_fetch_free(F);
+        if (recs) pf_bam_records_free(recs);
+        k = 0;
+    }
+    free(ws);
+    free(we);
+    free(idx);
+    if (rc) pf_perm_free(P); else *out = P;
+    return rc;
+}
+
+/* the contig's regions are complete: close the carry, (test,) append */
 static int hm_flush(hm_t *H, const char *chrom) {
     pf_dmr_t *fin = NULL;
-    uint64_t lines = 0;
+    pf_perm_t *P = NULL;
+    uint64_t lines = 0, dots = 0;
     int rc = pf_dmr_acc_flush(H->acc, &fin);
-    if (!rc) rc = write_dmr(H->dpath, chrom, fin, H->dmr->max_p, 0, &lines);
+    if (!rc && H->perm) rc = hm_perm(H, chrom, fin, &P);
+    if (!rc) rc = write_dmr(H->dpath, chrom, fin, P, H->dmr->max_p, 0, &lines, &dots);
     if (!rc) {
         H->dst.n_regions += lines;
         H->dst.n_informative += fin->n_informative;
+        if (P) {
+            H->pst.n_tested += lines - dots;
+            H->pst.n_untested += dots;
+        }
     }
+    pf_perm_free(P);
     pf_dmr_free(fin);
     pf_dmr_acc_free(H->acc);
     H->acc = NULL;
@@ -366,24 +473,33 @@ static int hm_span(hm_t *H, int32_t tid, uint32_t s, uint32_t e, uint32_t chunk,
 }
 
 int pf_hapmeth_main(const pf_hapmeth_opts_t *o, pf_hapmeth_stats_t *stats) {
-    return pf_hapmeth_run(o, NULL, stats, NULL);
+    return pf_hapmeth_run_perm(o, NULL, NULL, stats, NULL, NULL);
 }
 
 int pf_hapmeth_run(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, pf_hapmeth_stats_t *stats,
                    pf_hapmeth_dmr_stats_t *dstats) {
+    return pf_hapmeth_run_perm(o, dmr, NULL, stats, dstats, NULL);
+}
+
+int pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
+                        pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats, pf_hapmeth_perm_stats_t *pstats) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (dstats) memset(dstats, 0, sizeof *dstats);
+    if (pstats) memset(pstats, 0, sizeof *pstats);
     if (!o || !o->bam_path || !o->out_prefix || !o->out_prefix[0]) return PF_ERR_ARG;
     if (dmr && (dmr->cfg.min_delta_pct > 100u || !(dmr->max_p >= 0.0))) return PF_ERR_ARG;
+    if (perm && (!dmr || perm->n_perm < 1u || perm->n_perm > PF_PERM_MAX_PERM)) return PF_ERR_ARG;
     hm_t H;
     memset(&H, 0, sizeof H);
     H.o = o;
     H.dmr = dmr;
+    H.perm = perm;
     H.lc = o->load;
     /* the batch's phasing parameters are not used by the pileup: the reference's defaults */
     H.cfg.k = 3; H.cfg.k_span = 5000; H.cfg.cov_for_selection = 6; H.cfg.n_cand = 15; H.cfg.hard_cov = 15;
     const uint32_t chunk = o->chunk_size ? o->chunk_size : 100000u;
     const uint32_t jw = o->job_windows ? o->job_windows : 1024u;
+    H.jw = jw;
     int rc = pf_bam_open(o->bam_path, NULL, &H.bam);
     if (rc) {
         fprintf(stderr, "[E::pf_hapmeth_main] cannot open %s or its index\n", o->bam_path);
@@ -425,7 +541,9 @@ int pf_hapmeth_run(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, pf_h
         else made = 1;
     }
     if (!rc && dmr) {
-        rc = write_dmr(H.dpath, NULL, NULL, 1.0, 1, NULL);
+        pf_perm_t none;                                  /* with --dmr-perm the header names its columns */
+        memset(&none, 0, sizeof none);
+        rc = write_dmr(H.dpath, NULL, NULL, perm ? &none : NULL, 1.0, 1, NULL, NULL);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.dpath);
         else dmade = 1;
     }
@@ -443,8 +561,14 @@ int pf_hapmeth_run(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, pf_h
     if (!rc && o->verbose && dmr)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu informative sites, %llu regions, region kernels %.3f ms\n",
                 (unsigned long long)H.dst.n_informative, (unsigned long long)H.dst.n_regions, H.dst.ms_kernels);
+    if (!rc && o->verbose && perm)
+        fprintf(stderr, "[M::pf_hapmeth_main] %llu regions tested (%u permutations, seed %u), %llu without a test, "
+                "%llu records fetched again, permutation kernels %.3f ms\n", (unsigned long long)H.pst.n_tested,
+                perm->n_perm, perm->seed, (unsigned long long)H.pst.n_untested, (unsigned long long)H.pst.n_records,
+                H.pst.ms_kernels);
     if (stats) *stats = H.st;
     if (dstats) *dstats = H.dst;
+    if (pstats) *pstats = H.pst;
     free(ws);
     free(we);
     free(H.path);

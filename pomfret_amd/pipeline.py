@@ -34,7 +34,7 @@ import numpy as np
 from ._lib import (INTERVALS_GTF, INTERVALS_TSV, INTERVALS_VCF, PomfretError, _blocks_contigs, _check,  # noqa: F401
                    _breaks, _dmr_dict, _dmr_to_c, _gaps_contigs, _PfBlocks, _PfGaps, lib)
 from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfHapmethDmrStats, PfHapmethOpts,
-                  PfHapmethStats, PfLoadCfg, PfPileup)
+                  PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
 JOB_WINDOWS, JOB_HAPTAG = 0, 1
@@ -118,6 +118,9 @@ def _bind():
     L.pf_hapmeth_main.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethStats)]
     L.pf_hapmeth_run.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethStats),
                                  C.POINTER(PfHapmethDmrStats)]
+    L.pf_hapmeth_run_perm.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethPerm),
+                                      C.POINTER(PfHapmethStats), C.POINTER(PfHapmethDmrStats),
+                                      C.POINTER(PfHapmethPermStats)]
     L.pf_tags_new.restype = vp
     L.pf_tags_free.argtypes = [vp]
     L.pf_tags_size.argtypes = [vp]
@@ -481,7 +484,7 @@ def report_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cov: i
 def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk_size: int = 100_000,
                   lcfg: Optional[LoadConfig] = None, host_fetch: bool = False, threads: int = 1, device: int = 0,
                   job_windows: int = 0, dmr: Optional[DmrConfig] = None, dmr_max_p: float = 1.0,
-                  dmr_blocks: Optional[str] = None) -> Dict:
+                  dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1) -> Dict:
     """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
@@ -494,8 +497,17 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     where the haplotypes differ (`--dmr`; dmr_max_p drops regions whose
     pooled_p -- a ranking score, not a calibrated p-value -- is above it;
     dmr_blocks: a phase-block GTF no region crosses a block edge of), and adds
-    dmr_path, n_regions, n_informative and dmr_ms_kernels to the dict."""
+    dmr_path, n_regions, n_informative and dmr_ms_kernels to the dict.
+    dmr_perm: permutations of the reads' haplotype labels per region
+    (`--dmr-perm`, 1 .. 1,000,000; 0: off; needs dmr): the region file gains
+    the columns reads_h1, reads_h2 and perm_p = (hits + 1) / (dmr_perm + 1), a
+    p-value that holds under the correlation of one read's calls, and the dict
+    n_tested (lines with a numeric perm_p), n_untested (lines with "."),
+    perm_records (records the second pass fetched) and perm_ms_kernels;
+    dmr_seed seeds the permutations."""
     L = _bind()
+    if dmr_perm and dmr is None:
+        raise PomfretError("hapmeth_files: dmr_perm needs dmr")
     lc = lcfg or LoadConfig(min_len=0)
     o = PfHapmethOpts(bam.encode(), out_prefix.encode(), region.encode() if region else None, int(chunk_size),
                       int(job_windows), lc.to_c(), int(threads), int(bool(host_fetch)), int(device), 0)
@@ -505,12 +517,18 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     else:
         d = PfHapmethDmr(dmr.to_c(), float(dmr_max_p), dmr_blocks.encode() if dmr_blocks else None)
         dst = PfHapmethDmrStats()
-        _check(L.pf_hapmeth_run(C.byref(o), C.byref(d), C.byref(st), C.byref(dst)), "pf_hapmeth_run")
+        pm = PfHapmethPerm(int(dmr_perm), int(dmr_seed))
+        pst = PfHapmethPermStats()
+        _check(L.pf_hapmeth_run_perm(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(st),
+                                     C.byref(dst), C.byref(pst)), "pf_hapmeth_run_perm")
     res = dict(path=out_prefix + ".hapmeth.bed", n_windows=int(st.n_windows), n_skipped=int(st.n_skipped),
                n_records=int(st.n_records), n_sites=int(st.n_sites), ms_kernels=float(st.ms_kernels))
     if dmr is not None:
         res.update(dmr_path=out_prefix + ".hapmeth.dmr.bed", n_regions=int(dst.n_regions),
                    n_informative=int(dst.n_informative), dmr_ms_kernels=float(dst.ms_kernels))
+        if dmr_perm:
+            res.update(n_tested=int(pst.n_tested), n_untested=int(pst.n_untested), perm_records=int(pst.n_records),
+                       perm_ms_kernels=float(pst.ms_kernels))
     return res
 
 
@@ -548,6 +566,32 @@ def write_dmr(path: str, chrom: str, dmr: Dict, max_p: float = 1.0, header: bool
     L = _bind()
     d, keep = _dmr_to_c(dmr)
     _check(L.pf_write_dmr(path.encode(), chrom.encode(), C.byref(d), float(max_p), int(bool(header))), "pf_write_dmr")
+
+
+def write_dmr_perm(path: str, chrom: str, dmr: Dict, perm: Dict, max_p: float = 1.0, header: bool = True):
+    """write_dmr's lines followed by reads_h1, reads_h2 and perm_p
+    (pf_write_dmr_perm, host only).  perm: DeviceBatch.permtest's dict of a
+    batch whose window k is region k of dmr (n_reads, hits, status, n_perm);
+    perm_p = (hits + 1) / (n_perm + 1), "." where status is not 0."""
+    L = _bind()
+    d, keep = _dmr_to_c(dmr)
+    if perm is None:
+        _check(L.pf_write_dmr_perm(path.encode(), chrom.encode(), C.byref(d), None, float(max_p), int(bool(header))),
+               "pf_write_dmr_perm")
+        return
+    W = int(np.size(perm["hits"]))
+    nr = np.zeros(2 * W + 1, np.uint32)
+    hits, stat, sm = np.zeros(W + 1, np.uint32), np.zeros(W + 1, np.uint32), np.zeros(4 * W + 1, np.uint64)
+    nr[:2 * W] = np.asarray(perm["n_reads"], np.uint32).ravel()
+    hits[:W] = np.asarray(perm["hits"], np.uint32).ravel()
+    stat[:W] = np.asarray(perm["status"], np.uint32).ravel()
+    if "sum" in perm:
+        sm[:4 * W] = np.asarray(perm["sum"], np.uint64).ravel()
+    u64p, u32p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)
+    p = PfPerm(W, int(perm["n_perm"]), int(perm.get("seed", 0)), nr.ctypes.data_as(u32p), sm.ctypes.data_as(u64p),
+               hits.ctypes.data_as(u32p), stat.ctypes.data_as(u32p), 0.0)
+    _check(L.pf_write_dmr_perm(path.encode(), chrom.encode(), C.byref(d), C.byref(p), float(max_p), int(bool(header))),
+           "pf_write_dmr_perm")
 
 
 def write_hapmeth(path: str, chrom: str, pile: Dict, header: bool = True, w0: int = 0, w1: Optional[int] = None):
