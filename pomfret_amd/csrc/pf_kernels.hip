@@ -397,12 +397,17 @@ struct K2Calls {
 // (the hash is passed by value: a pointer to a local struct would put it on
 // the scratch stack, and every reload's vmcnt wait would drain the next
 // read's prefetched calls)
-DEV void k2_calls_sites(K2Calls &cl, const uint32_t *sp, uint32_t S, const K2SiteHash hs, bool use_hash) {
+DEV void k2_calls_sites(K2Calls &cl, uint32_t nc, const uint32_t *sp, uint32_t S, const K2SiteHash hs,
+                        bool use_hash) {
+    // the sites' range once per read; slots beyond the read's nc calls hold
+    // no call (nc is wave-uniform: a scalar branch)
+    const uint32_t sfirst = S ? sp[0] : 1u, slast = S ? sp[S - 1] : 0u;
 #pragma unroll
     for (int u = 0; u < K2_CR; u++) {
         const uint32_t p = cl.pos[u];
         uint32_t si = PF_NONE;
-        if (cl.cat[u] < 3u && S > 0 && p >= sp[0] && p <= sp[S - 1]) {
+        if (64u * u >= nc) { cl.site[u] = si; continue; }
+        if (cl.cat[u] < 3u && p >= sfirst && p <= slast) {
             if (use_hash) si = k2_site_of(hs, p);
             else {
                 uint32_t lo = 0, hi = S;
@@ -639,6 +644,303 @@ __global__ __launch_bounds__(PF_K2_WAVES * 64) void pf_k2_methmers(pf_dev_batch 
     }
 }
 
+// ------------------------------------------------------------------------
+// Both directions of one read in one pass (k12_methmers, calls in registers)
+// ------------------------------------------------------------------------
+#ifndef PF_K12_PAIR
+#define PF_K12_PAIR 1                     // k12_methmers: k2_pair (1) or two k2_core calls per read (0)
+#endif
+#ifndef PF_K12_PACK
+#define PF_K12_PACK 1                     // k2_pair's keys: two LDS words of 2-bit characters per key (1; K12 2.98 ms) or a byte loop (0; 3.06 ms)
+#endif
+
+// Lower bounds of kA and kB in a0[0, n) and in a1[0, n), both non-decreasing
+// and in one LDS block: lanes 0-15 / 16-31 search a0 for kA / kB, lanes 32-47
+// / 48-63 a1, narrowing 16-fold per round (wave_lb2's loop, four keys in one).
+DEV void wave_lb4(const uint32_t *a0, const uint32_t *a1, uint32_t n, uint32_t kA, uint32_t kB, uint32_t lane,
+                  uint32_t &lbA0, uint32_t &lbB0, uint32_t &lbA1, uint32_t &lbB1) {
+    const uint32_t g = lane >> 4, j = lane & 15;
+    // an offset from a0, not a choice of pointers: the loads stay LDS loads
+    const uint32_t *a = a0 + ((g & 2u) ? (a1 - a0) : 0);
+    const uint32_t key = (g & 1u) ? kB : kA;
+    uint32_t lo = 0, hi = n;
+    for (;;) {
+        const uint32_t len = hi - lo;
+        const uint32_t step = (len + 15) >> 4;
+        const uint32_t p = lo + j * step;
+        const bool lt = len > 0 && p < hi && a[p] < key;
+        const uint64_t bal = __ballot(lt);
+        const uint32_t c = (uint32_t)__popc((uint32_t)(bal >> (16 * g)) & 0xFFFFu);
+        if (len > 0) {
+            if (c == 0) hi = lo;
+            else {
+                const uint32_t pn = lo + c * step;
+                lo = lo + (c - 1) * step + 1;
+                hi = pn < hi ? pn : hi;
+            }
+        }
+        if (__ballot(hi > lo) == 0) break;
+    }
+    lbA0 = rdl(lo, 0);
+    lbB0 = rdl(lo, 16);
+    lbA1 = rdl(lo, 32);
+    lbB1 = rdl(lo, 48);
+}
+
+// Characters cb[0, n) (values 0-2) packed 2 bits each into pk[0, ceil(n/16)),
+// character 16w + i in bits 31-2i, 30-2i of word w: a key's bit order, so the
+// key of characters [e, e + L) is a shift of the word pair at e >> 4.  cb is
+// read in whole words up to the next multiple of 16 (the wave buffer is 4-byte
+// aligned and longer); what lies beyond n is masked to 2 bits and never used.
+DEV void k2_pack_chars(const uint8_t *cb, uint32_t n, uint32_t lane, uint32_t *pk) {
+    const uint32_t *c4 = reinterpret_cast<const uint32_t *>(cb);
+    for (uint32_t w = lane; 16 * w < n; w += 64) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            // bytes b0..b3 -> b0 << 6 | b1 << 4 | b2 << 2 | b3: the product's
+            // other terms fall below bit 24 or beyond bit 31
+            const uint32_t t = c4[4 * w + q] & 0x03030303u;
+            v = v << 8 | (t * 0x40100401u) >> 24;
+        }
+        pk[w] = v;
+    }
+}
+DEV uint64_t k2_key_window(const uint32_t *pk, uint32_t e) {
+    const uint32_t w = e >> 4;
+    return (uint64_t)pk[w] << 32 | pk[w + 1];
+}
+// the key of the L characters from e (1 <= L <= 16), win = k2_key_window(pk, e)
+DEV uint32_t k2_key_of(uint64_t win, uint32_t e, uint32_t L) {
+    return L ? (uint32_t)((win << (2 * (e & 15u))) >> ((64 - 2 * L) & 63u)) : 0u;
+}
+DEV uint32_t k2_key_bytes(const uint8_t *cb, uint32_t e, uint32_t L) {
+    uint32_t key = 0;
+    for (uint32_t t = 0; t < L; t++) key = key << 2 | cb[e + t];
+    return key;
+}
+
+// What two k2_core calls (direction 0, copy-out, direction 1) do for a read
+// whose calls sit in registers, in fewer dependent LDS round trips:
+//  - the four lower bounds (F and L in sp and in st1) in one search;
+//  - the characters once, over the union [ulo, uhi) of the two real-index
+//    ranges; direction 0 reads them at xl - ulo, direction 1 at q1 - ulo;
+//  - direction 0 without an entry list: its starts are site_pos itself,
+//    strictly ascending, so every index of [xl, xr) is an entry, entry e is
+//    site xl + e, a run of equal starts has length one and the duplicated
+//    start fix-up cannot fire;
+//  - direction 1 with k2_core's entry pass (its starts repeat, the i > 1 quirk
+//    lives there), each lane's run of equal starts walked once: the first
+//    index, the count and up to 8 lengths stay in registers (a longer run is
+//    walked a second time);
+//  - keys from packed characters (PF_K12_PACK).
+// Direction 0's keys are staged in kst and copied out before direction 1
+// stages its own, whose count is returned in pend_n, exactly as the two calls
+// do: no store moves against the prefetched loads.  Returns false, having
+// written nothing, where the read takes the two calls instead: only one
+// direction has sites in range, a range exceeds the buffers, or the union
+// exceeds k12_capw.
+DEV bool k2_pair(const pf_dev_batch &d, uint32_t r, uint32_t lane, uint32_t S, const uint32_t *sp,
+                 const uint32_t *st1, const uint32_t *q1s, const uint8_t *l0s, const uint8_t *l1s, uint8_t *wb,
+                 const K2Read &rd, const K2Calls &cl, uint64_t k0, uint64_t k1, unsigned long long *k2acc,
+                 uint32_t &pend_n) {
+    uint8_t *chars = wb, *crank = wb + PF_K12_CAPW;
+    uint16_t *irank = reinterpret_cast<uint16_t *>(wb + 2 * PF_K12_CAPW);
+    uint32_t *kst = reinterpret_cast<uint32_t *>(wb + 4 * PF_K12_CAPW);
+    // packed characters: direction 0's in the crank share it does not use,
+    // direction 1's over the characters its entry pass has consumed
+    uint32_t *pk0 = reinterpret_cast<uint32_t *>(crank), *pk1 = reinterpret_cast<uint32_t *>(chars);
+    (void)pk0; (void)pk1;
+    pend_n = 0;
+    uint32_t xl0 = 0, xr0 = 0, xl1 = 0, xr1 = 0;
+    if (S > 0 && rd.c1 > rd.c0) {
+        const uint32_t F = rd.F, L = rd.L;
+        const uint32_t sf0 = sp[0], sl0 = sp[S - 1], sf1 = st1[0], sl1 = st1[S - 1];
+        const bool in0 = !(F > sl0 || L < sf0), in1 = !(F > sl1 || L < sf1);
+        if (in0 || in1) {
+            uint32_t lbF0, lbL0, lbF1, lbL1;
+            wave_lb4(sp, st1, S, F, L, lane, lbF0, lbL0, lbF1, lbL1);
+            if (in0) {
+                xl0 = F < sf0 ? 0 : (sp[lbF0] == F ? lbF0 : (lbF0 ? lbF0 - 1 : 0));
+                xr0 = L > sl0 ? S : lbL0;
+            }
+            if (in1) {
+                xl1 = F < sf1 ? 0 : (st1[lbF1] == F ? lbF1 : (lbF1 ? lbF1 - 1 : 0));
+                xr1 = L > sl1 ? S : lbL1;
+            }
+        }
+    }
+    const bool ne0 = xl0 < xr0, ne1 = xl1 < xr1;
+    if (ne0 != ne1) return false;
+    if (!ne0) {
+        if (lane == 0) {
+            d.mmr_n[2 * r] = 0; d.mmr_start[2 * r] = 0;
+            d.mmr_n[2 * r + 1] = 0; d.mmr_start[2 * r + 1] = 0;
+        }
+        return true;
+    }
+    const uint32_t ql1 = q1s[xl1], qh1 = q1s[xr1 - 1] + 1;
+    const uint32_t ulo = xl0 < ql1 ? xl0 : ql1, uhi = xr0 > qh1 ? xr0 : qh1;
+    if (xr0 - xl0 > PF_K12_CAPW || xr1 - xl1 > PF_K12_CAPW || uhi - ulo > d.k12_capw) return false;
+    K2_STAMP(0);
+    k2_chars_reg(cl, ulo, uhi, lane, chars);
+    const uint32_t cap = rd.cap, maxcall = rd.maxcall;
+    // ---- direction 0
+    {
+        const uint32_t E = xr0 - xl0, off = xl0 - ulo;
+        const uint32_t usable = E - (sp[xr0 - 1] > maxcall ? 1u : 0u);
+#if PF_K12_PACK
+        k2_pack_chars(chars, uhi - ulo, lane, pk0);
+        wave_sync();
+#endif
+        K2_STAMP(1);
+        const uint64_t room = d.keys_cap > k0 ? d.keys_cap - k0 : 0;
+        uint32_t total = 0, start_i = PF_NONE;
+        for (uint32_t e0 = 0; e0 < E; e0 += 64) {
+            const uint32_t e = e0 + lane;
+            bool emit = false;
+            uint32_t key = 0;
+            if (e < E) {
+                const uint32_t Lj = l0s[xl0 + e];
+#if PF_K12_PACK
+                const uint64_t win = k2_key_window(pk0, off + e);
+#endif
+                emit = e + Lj <= usable;
+#if PF_K12_PACK
+                key = k2_key_of(win, off + e, Lj);
+#else
+                if (emit) key = k2_key_bytes(chars, off + e, Lj);
+#endif
+            }
+            const uint64_t m = __ballot(emit);
+            if (start_i == PF_NONE && m) start_i = xl0 + e0 + (uint32_t)__ffsll((unsigned long long)m) - 1;
+            if (emit) {
+                const uint32_t pos = total + (uint32_t)__popcll(m & lanemask_lt(lane));
+                if (pos < cap && pos < room) kst[pos] = key;
+            }
+            total += (uint32_t)__popcll(m);
+        }
+        if (total > cap && lane == 0) atomicOr(d.status, PF_ST_KEYS_OVF);
+        uint32_t n0 = total < cap ? total : cap;
+        n0 = n0 < room ? n0 : (uint32_t)room;
+        K2_STAMP(3);
+        if (lane == 0) {
+            d.mmr_n[2 * r] = total;
+            d.mmr_start[2 * r] = total ? start_i : 0;
+        }
+        k2_flush(d, kst, k0, n0, lane);
+        K2_STAMP(5);
+    }
+    // ---- direction 1
+    {
+        const uint32_t qlo = ulo;
+        uint32_t E = 0;
+        for (uint32_t i0 = xl1; i0 < xr1; i0 += 64) {
+            const uint32_t i = i0 + lane;
+            bool ent = false;
+            if (i < xr1) ent = !(i > 1 && st1[i] == st1[i - 1]);
+            const uint64_t m = __ballot(ent);
+            if (ent) {
+                const uint32_t rk = E + (uint32_t)__popcll(m & lanemask_lt(lane));
+                crank[rk] = chars[q1s[i] - qlo];
+                irank[rk] = (uint16_t)i;
+            }
+            E += (uint32_t)__popcll(m);
+        }
+        wave_sync();
+        uint32_t total = 0, start_i = PF_NONE, n1 = 0;
+        if (E > 0) {
+            const uint32_t usable = E - (st1[irank[E - 1]] > maxcall ? 1u : 0u);
+            // duplicated start at indices 0 and 1: entry 0 is followed by another
+            // site entry, so its character is '-'.  Entries 0 and 1 are indices 0
+            // and 1 exactly when xl1 == 0 and xr1 >= 2 (index 1 is always an entry).
+            const bool dup01 = xl1 == 0 && xr1 >= 2 && st1[1] == st1[0];
+#if PF_K12_PACK
+            k2_pack_chars(crank, E, lane, pk1);
+            if (dup01 && lane == 0) pk1[0] = (pk1[0] & 0x3FFFFFFFu) | 0x80000000u;   // lane 0 packed word 0 itself
+            wave_sync();
+#else
+            if (dup01 && lane == 0) crank[0] = 2;
+            wave_sync();
+#endif
+            K2_STAMP(2);
+            const uint64_t room = d.keys_cap > k1 ? d.keys_cap - k1 : 0;
+            for (uint32_t e0 = 0; e0 < E; e0 += 64) {
+                const uint32_t e = e0 + lane;
+                uint32_t ne = 0, fj = PF_NONE, i = 0, P = 0;
+                uint64_t lp = 0;                              // the run's first 8 emitted lengths
+#if PF_K12_PACK
+                uint64_t win = 0;
+#endif
+                if (e < E) {
+                    i = irank[e];
+#if PF_K12_PACK
+                    win = k2_key_window(pk1, e);
+#endif
+                    P = st1[i];
+                    uint32_t j = i;
+                    bool more;
+                    do {
+                        const uint32_t Lj = l1s[j];
+                        more = j + 1 < S && st1[j + 1] == P;
+                        if (e + Lj <= usable) {
+                            if (fj == PF_NONE) fj = j;
+                            if (ne < 8) lp |= (uint64_t)Lj << (8 * ne);
+                            ne++;
+                        }
+                        j++;
+                    } while (more);
+                }
+                const uint32_t incl = wave_incl_scan_dpp(ne);
+                const uint32_t tot = rdl(incl, 63);
+                if (start_i == PF_NONE && tot > 0) {
+                    const uint64_t m = __ballot(ne > 0);
+                    const uint32_t src = (uint32_t)__ffsll((unsigned long long)m) - 1;
+                    start_i = rdl(fj, src);
+                }
+                if (ne) {
+                    uint32_t pos = total + incl - ne;
+                    if (ne <= 8) {
+                        for (uint32_t t = 0; t < ne; t++, pos++) {
+                            const uint32_t Lj = (uint32_t)(lp >> (8 * t)) & 255u;
+#if PF_K12_PACK
+                            const uint32_t key = k2_key_of(win, e, Lj);
+#else
+                            const uint32_t key = k2_key_bytes(crank, e, Lj);
+#endif
+                            if (pos < cap && pos < room) kst[pos] = key;
+                        }
+                    } else {
+                        for (uint32_t j = i; j < S && st1[j] == P; j++) {
+                            const uint32_t Lj = l1s[j];
+                            if (e + Lj <= usable) {
+#if PF_K12_PACK
+                                const uint32_t key = k2_key_of(win, e, Lj);
+#else
+                                const uint32_t key = k2_key_bytes(crank, e, Lj);
+#endif
+                                if (pos < cap && pos < room) kst[pos] = key;
+                                pos++;
+                            }
+                        }
+                    }
+                }
+                total += tot;
+            }
+            if (total > cap && lane == 0) atomicOr(d.status, PF_ST_KEYS_OVF);
+            n1 = total < cap ? total : cap;
+            n1 = n1 < room ? n1 : (uint32_t)room;
+            K2_STAMP(3);
+        }
+        if (lane == 0) {
+            d.mmr_n[2 * r + 1] = total;
+            d.mmr_start[2 * r + 1] = total ? start_i : 0;
+        }
+        pend_n = n1;
+    }
+    return true;
+}
+
 // The methmer phase of one window over its reads i0, i0 + NW, ... < i1 (wave
 // wid of NW): one wavefront per read, both directions, the window's site
 // arrays in LDS (sp, st1, q1s, l0s, l1s; hsd when use_hash), the wave's
@@ -695,7 +997,7 @@ DEV void k12_methmers(const pf_dev_batch &d, uint32_t r0, uint32_t i0, uint32_t 
                         if ((uint32_t)u == ul) mc = rdl(cl.pos[u], ll);
                 }
                 rd.maxcall = mc;
-                k2_calls_sites(cl, sp, S, hsd, use_hash);
+                k2_calls_sites(cl, uni((uint32_t)nc), sp, S, hsd, use_hash);
             }
             K2_STAMP(4);
             k2_flush(d, kst, pend_off, pend_n, lane);
@@ -710,12 +1012,19 @@ DEV void k12_methmers(const pf_dev_batch &d, uint32_t r0, uint32_t i0, uint32_t 
             } else {
                 const uint64_t k0 = d.mmr_off[2ull * r], k1 = d.mmr_off[2ull * r + 1];
                 if (regs) {
-                    const uint32_t n0 = k2_core(d, r, 0, lane, S, sp, sp, l0s, q1s, chars, crank, irank, PF_K12_CAPW,
-                                                rd, &cl, k0, k2acc, kst);
-                    k2_flush(d, kst, k0, n0, lane);
-                    K2_STAMP(5);
-                    pend_n = k2_core(d, r, 1, lane, S, sp, st1, l1s, q1s, chars, crank, irank, PF_K12_CAPW, rd,
-                                     &cl, k1, k2acc, kst);
+#if PF_K12_PAIR
+                    const bool paired = k2_pair(d, r, lane, S, sp, st1, q1s, l0s, l1s, wb, rd, cl, k0, k1, k2acc, pend_n);
+#else
+                    const bool paired = false;
+#endif
+                    if (!paired) {
+                        const uint32_t n0 = k2_core(d, r, 0, lane, S, sp, sp, l0s, q1s, chars, crank, irank,
+                                                    PF_K12_CAPW, rd, &cl, k0, k2acc, kst);
+                        k2_flush(d, kst, k0, n0, lane);
+                        K2_STAMP(5);
+                        pend_n = k2_core(d, r, 1, lane, S, sp, st1, l1s, q1s, chars, crank, irank, PF_K12_CAPW, rd,
+                                         &cl, k1, k2acc, kst);
+                    }
                     pend_off = k1;
                     K2_STAMP(5);
                 } else {
@@ -1405,10 +1714,12 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
 // No position hash (the heavy windows' calls span beyond K12's bitmap): the
 // calls' site indices come from binary searches in LDS, as K12's dense-path
 // windows do.
-__global__ __launch_bounds__(PF_K12C_WAVES * 64) void pf_k12_chunks(pf_dev_batch d) {
+// 4 waves per SIMD (128 VGPRs): without the bound the allocator spreads the
+// methmer phase over ~150 registers and the kernel drops to 3 waves.
+__global__ __launch_bounds__(PF_K12C_WAVES * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void pf_k12_chunks(pf_dev_batch d) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ uint32_t s_item, s_rctr;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wid = uni(tid >> 6);   // the wave buffer's address in SGPRs
     const uint32_t n = *d.k12c_ctr;
     for (;;) {
         if (tid == 0) s_item = atomicAdd(d.k12c_next, 1u);
