@@ -489,6 +489,81 @@ int  pf_batch_permtest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, u
                        uint32_t seed, pf_perm_t **out);
 void pf_perm_free(pf_perm_t *p);
 
+/* Tags for untagged reads from a window's allele-specific methylation
+ * (pf_assign.hip; no reference counterpart): inside a window [ws, we) where
+ * the two haplotypes' methylation differs, an untagged read's own calls say
+ * which haplotype it came from.  The tagged reads give the per-site model, the
+ * untagged read is never part of it.  All in integers; windows may overlap,
+ * every window is scored on its own.  Out of scope: writing a retagged BAM;
+ * merging one read's scores across regions or phase blocks (one row per
+ * (window, read), the consumer decides); leave-one-out scoring of reads that
+ * carry a tag; filtering regions by perm_p; more than one device.
+ *   model        for every position p of the window m1,u1,m2,u2 are the meth /
+ *                unmeth entries of the window's reads tagged 0 and 1, exactly
+ *                pf_batch_pileup's cnt[0..3]; n1 = m1+u1, n2 = m2+u2; p is
+ *                informative iff n1 >= min_cov && n2 >= min_cov (pf_dmr_cfg_t's
+ *                rule).  Tags other than 0 / 1 never enter the model;
+ *   L(x), x >= 1 a Q16 fixed-point log2 defined by this algorithm, not by libm
+ *                (pf_ilog2_q16): e = floor(log2 x); y = (uint64)x << (31 - e);
+ *                f = 0; 16 times: y = (y*y) >> 31, f <<= 1, and if y >= 2^32
+ *                then y >>= 1, f |= 1; L = (e << 16) | f.  Never above
+ *                floor(65536*log2 x) and at most 1 below it;
+ *   weights      of an informative site, Laplace-smoothed log-odds, int32:
+ *                wM = L(m1+1) - L(n1+2) - L(m2+1) + L(n2+2) for a meth entry,
+ *                wU = L(u1+1) - L(n1+2) - L(u2+1) + L(n2+2) for an unmeth one
+ *                (counts reach 65,535, so arguments reach 131,072);
+ *   candidates   the window's reads whose tag is exactly 254 (untagged), in
+ *                the batch's read order; tags 0, 1 and HP >= 3 never;
+ *   score        S (int64) the sum of wM / wU over the candidate's call entries
+ *                with ws <= pos < we, cat 0 / 1, at an informative position;
+ *                n_used the number of those entries.  A duplicate entry counts
+ *                each time; cat 2 and non-informative positions count nowhere;
+ *                an informative site whose weights are both 0 still counts in
+ *                n_used;
+ *   decision     new tag 0 iff n_used >= min_calls && S >= min_llr_q16 && S > 0;
+ *                new tag 1 iff n_used >= min_calls && -S >= min_llr_q16 && S < 0;
+ *                else the candidate stays 254. */
+typedef struct pf_assign_cfg {
+    uint32_t min_cov;          /* calls per haplotype a site needs (the --dmr one)   */
+    uint32_t min_calls;        /* informative entries a candidate needs              */
+    int64_t  min_llr_q16;      /* least |S|, Q16 bits: 3 bits (odds of 8:1) = 196608 */
+} pf_assign_cfg_t;
+
+typedef struct pf_assign {
+    uint32_t n_windows;
+    uint32_t n_reads;
+    const uint32_t *win_read_off;  /* [n_windows+1] the batch's reads per window        */
+    const uint32_t *n_used;    /* [n_reads] 0 for non-candidates                     */
+    const int64_t  *llr;       /* [n_reads] S, Q16; 0 for non-candidates             */
+    const uint8_t  *hp;        /* [n_reads] the new tag for candidates, the input tag
+                                  for every other read: read_hp for pf_batch_pileup  */
+    const uint32_t *win_n;     /* [n_windows*3] candidates with n_used >= 1, assigned
+                                  0, assigned 1                                      */
+    float ms_kernels;          /* event-timed: the assign kernels only (the site
+                                  table's pileup kernels are not part of it)         */
+} pf_assign_t;
+/* Batches and tags as in pf_batch_permtest: calls-level and record-level
+ * batches (the latter run their load stage first); read_hp NULL uses the
+ * batch's own tags, else [n_hp] tags replace them for this call only (n_hp
+ * equal to the batch's reads, PF_ERR_ARG otherwise); PF_ERR_ARG while a
+ * launched run is unfinished; the batch is left as it was; no window is a
+ * valid empty result.  A batch read belongs to exactly one window, so the
+ * per-read arrays are dense.  The site table is pf_batch_pileup's, kept on the
+ * device (its limits apply: a count past 65,535 returns PF_ERR_LIMIT).  The
+ * result is owned by the library (pf_assign_free) and depends on neither
+ * launch geometry nor atomic order: every sum is an integer sum.  min_llr_q16
+ * below 1 acts as 1 (S > 0 / S < 0 is required anyway).  PF_ASSIGN_TILE=<n> in
+ * the environment (tests) sets the sites per LDS tile, a power of two in
+ * [64, 4096]; the default is 4,096; any other value returns PF_ERR_ARG. */
+int  pf_batch_assign(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, const pf_assign_cfg_t *cfg,
+                     pf_assign_t **out);
+void pf_assign_free(pf_assign_t *a);
+/* L(x) as defined above, on the host (the kernels compute the same); 0 for x == 0. */
+uint32_t pf_ilog2_q16(uint32_t x);
+/* The two weights of a site with the counts m1, u1, m2, u2 (host; the kernels
+ * compute the same): w[0] = wM, w[1] = wU. */
+void pf_assign_site_weights(uint32_t m1, uint32_t u1, uint32_t m2, uint32_t u2, int32_t w[2]);
+
 /* -u pre-pass: hp_out[r] in {0, 1, 254} for every read of one contig. */
 int  pf_haptag_reads(pf_ctx_t *ctx, const pf_known_vars_t *known,
                      const pf_read_aln_batch_t *reads, uint8_t *hp_out);
@@ -1228,6 +1303,49 @@ typedef struct pf_hapmeth_perm_stats {
  * files.  st, dst and pst may be NULL. */
 int  pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
                          pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst, pf_hapmeth_perm_stats_t *pst);
+
+/* hapmeth --dmr --assign: the scored candidates of a pf_batch_assign result
+ * as lines of {out_prefix}.hapmeth.assign.tsv, tab-separated (host only):
+ *   qname chrom start end n_calls llr hp
+ * one line per (window, read of it with n_used >= 1), windows in order and the
+ * batch's read order inside a window; start / end the window's, n_calls the
+ * read's n_used, llr = S / 65536.0 as %.4f (bits; positive: haplotype 1), hp
+ * "1", "2" or "." (not assigned).  win_start / win_end: [a->n_windows];
+ * rec_of_read: [a->n_reads] each read's record (pf_batch_read_recs), NULL for
+ * the identity; qname_off / qname: the records' names as the fetch holds them
+ * (pf_bam_records_t, pf_bam_dev_fetch_t).  header as in pf_write_hapmeth (then
+ * a may be NULL).  n_lines, when given, receives the lines written. */
+int  pf_write_assign(const char *path, const char *chrom, const pf_assign_t *a, const uint32_t *win_start,
+                     const uint32_t *win_end, const uint32_t *rec_of_read, const uint64_t *qname_off, const char *qname,
+                     int header, uint64_t *n_lines);
+
+typedef struct pf_hapmeth_assign {
+    int64_t  min_llr_q16;      /* pf_assign_cfg_t's; the CLI's default is 3 bits           */
+    uint32_t min_calls;        /* pf_assign_cfg_t's; the CLI's default is 2                */
+    uint32_t reserved;
+} pf_hapmeth_assign_t;
+
+typedef struct pf_hapmeth_assign_stats {
+    uint64_t n_lines;          /* lines written to {out_prefix}.hapmeth.assign.tsv         */
+    uint64_t n_h1, n_h2;       /* of those, assigned to haplotype 1 / 2                    */
+    uint64_t n_records;        /* records fetched by the second pass                       */
+    double ms_kernels;         /* summed pf_assign_t.ms_kernels                            */
+} pf_hapmeth_assign_stats_t;
+
+/* pf_hapmeth_run_perm, and with assign != NULL {out_prefix}.hapmeth.assign.tsv:
+ * the second pass at each contig's end (the regions that pass dmr->max_p as the
+ * windows of jobs of job_windows windows, each fetched once) serves both:
+ * pf_batch_permtest when perm is given and pf_batch_assign when assign is, on
+ * the same batch, under the records' HP tags; with assign alone the pass still
+ * runs.  min_cov is dmr->cfg.min_cov, so the sites used are the region's own
+ * members.  Neither file of the other features changes with assign.  assign ==
+ * NULL: exactly pf_hapmeth_run_perm (ast is zeroed).  The pass's one fetch is
+ * counted in pst.n_records when perm is given and in ast.n_records when assign
+ * is.  assign without dmr returns PF_ERR_ARG.  On failure every file is unlinked.
+ * st, dst, pst and ast may be NULL. */
+int  pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
+                           const pf_hapmeth_assign_t *assign, pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst,
+                           pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

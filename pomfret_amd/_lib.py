@@ -12,7 +12,7 @@ import weakref
 
 import numpy as np
 
-from .abi import (DMR_RUN_DTYPE, AlnBatch, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
+from .abi import (DMR_RUN_DTYPE, AlnBatch, AssignConfig, PfAssign, PfAssignCfg, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
                   PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfReadAlnBatch, PfWindowBatch, PfWindowOut, ReadAlnBatch,
                   WindowBatch, WindowResult)
 
@@ -97,6 +97,15 @@ def lib():
                                         C.POINTER(C.POINTER(PfPerm))]
         L.pf_perm_free.argtypes = [C.POINTER(PfPerm)]
         L.pf_write_dmr_perm.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfDmr), C.POINTER(PfPerm), C.c_double, C.c_int]
+        L.pf_batch_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PfAssignCfg),
+                                      C.POINTER(C.POINTER(PfAssign))]
+        L.pf_assign_free.argtypes = [C.POINTER(PfAssign)]
+        L.pf_ilog2_q16.argtypes = [C.c_uint32]
+        L.pf_ilog2_q16.restype = C.c_uint32
+        L.pf_assign_site_weights.argtypes = [C.c_uint32] * 4 + [C.POINTER(C.c_int32)]
+        L.pf_assign_site_weights.restype = None
+        L.pf_write_assign.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfAssign), C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
         if hasattr(L, "pf_haptag_reads"):
             L.pf_haptag_reads.argtypes = [C.c_void_p, C.POINTER(PfKnownVars),
                                           C.POINTER(PfReadAlnBatch), C.c_void_p]
@@ -618,6 +627,36 @@ class DeviceBatch:
                         seed=int(r.seed), ms=float(r.ms_kernels))
         finally:
             lib().pf_perm_free(p)
+
+    def assign(self, cfg: AssignConfig = None, read_hp=None) -> dict:
+        """Tags for the batch's untagged reads from each window's
+        allele-specific methylation (pf_batch_assign; include/pomfret_amd.h
+        has the definition): dict(win_read_off [W+1], n_used [R] the read's
+        call entries at informative sites (0 for a read that is no
+        candidate), llr [R] the score S in Q16 bits (int64; positive:
+        haplotype 1), hp [R] the new tag of a candidate and the input tag of
+        every other read -- pileup's read_hp --, win_n [W, 3] the candidates
+        with n_used >= 1, assigned 0, assigned 1, ms the assign kernels'
+        time).  read_hp as in pileup."""
+        hp_ptr, n_hp = None, 0
+        if read_hp is not None:
+            hp = np.zeros(np.size(read_hp) + 1, np.uint8)
+            hp[:-1] = np.asarray(read_hp, np.uint8).ravel()
+            hp_ptr, n_hp = hp.ctypes.data, hp.size - 1
+        c = (cfg or AssignConfig()).to_c()
+        p = C.POINTER(PfAssign)()
+        _check(lib().pf_batch_assign(self.ctx.handle, self.handle, hp_ptr, n_hp, C.byref(c), C.byref(p)), "pf_batch_assign")
+        try:
+            r = p.contents
+            W, R = int(r.n_windows), int(r.n_reads)
+
+            def arr(ptr, n, dt):
+                return np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dt)
+            return dict(win_read_off=arr(r.win_read_off, W + 1, np.uint32), n_used=arr(r.n_used, R, np.uint32),
+                        llr=arr(r.llr, R, np.int64), hp=arr(r.hp, R, np.uint8),
+                        win_n=arr(r.win_n, 3 * W, np.uint32).reshape(W, 3), ms=float(r.ms_kernels))
+        finally:
+            lib().pf_assign_free(p)
 
     def stats(self) -> np.ndarray:
         """Per-(window, dir) counters of the last run: [W, 2, 8] (see pf_batch_stats)."""

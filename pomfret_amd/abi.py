@@ -427,6 +427,49 @@ class PfHapmethPermStats(C.Structure):
                 ("ms_kernels", C.c_double)]
 
 
+class PfAssignCfg(C.Structure):
+    """pf_assign_cfg_t."""
+    _fields_ = [("min_cov", C.c_uint32), ("min_calls", C.c_uint32), ("min_llr_q16", C.c_int64)]
+
+
+@dataclass
+class AssignConfig:
+    """Parameters of the tag assignment (pf_batch_assign): a CpG enters the
+    model with min_cov calls on each haplotype (hapmeth_files takes the
+    DmrConfig's instead), an untagged read gets a tag with at least min_calls
+    calls at such CpGs and log2 odds of at least min_llr bits (Q16 inside:
+    round(min_llr * 65536)).  The two defaults -- odds of 8:1, two calls --
+    are choices, not measured optima."""
+    min_cov: int = 5
+    min_calls: int = 2
+    min_llr: float = 3.0
+
+    @property
+    def min_llr_q16(self) -> int:
+        return int(round(self.min_llr * 65536))
+
+    def to_c(self) -> PfAssignCfg:
+        return PfAssignCfg(self.min_cov, self.min_calls, self.min_llr_q16)
+
+
+class PfAssign(C.Structure):
+    """pf_assign_t: the scores and new tags of a batch's untagged reads (pf_batch_assign)."""
+    _fields_ = [("n_windows", C.c_uint32), ("n_reads", C.c_uint32), ("win_read_off", C.POINTER(C.c_uint32)),
+                ("n_used", C.POINTER(C.c_uint32)), ("llr", C.POINTER(C.c_int64)), ("hp", C.POINTER(C.c_uint8)),
+                ("win_n", C.POINTER(C.c_uint32)), ("ms_kernels", C.c_float)]
+
+
+class PfHapmethAssign(C.Structure):
+    """pf_hapmeth_assign_t (pf_hapmeth_run_assign)."""
+    _fields_ = [("min_llr_q16", C.c_int64), ("min_calls", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PfHapmethAssignStats(C.Structure):
+    """pf_hapmeth_assign_stats_t."""
+    _fields_ = [("n_lines", C.c_uint64), ("n_h1", C.c_uint64), ("n_h2", C.c_uint64), ("n_records", C.c_uint64),
+                ("ms_kernels", C.c_double)]
+
+
 class PfAlnBatch(C.Structure):
     _fields_ = [("n_windows", C.c_uint32), ("n_recs", C.c_uint32)] + [
         (n, C.c_void_p) for n in (

@@ -1532,16 +1532,22 @@ static uint32_t pile_tile() {
     return (uint32_t)n;
 }
 
-extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *read_hp, uint32_t n_hp,
-                               pf_pileup_t **out) {
-    if (!ctx || !b || !out || b->ctx != ctx) return PF_ERR_ARG;
-    *out = nullptr;
+// dev == NULL: pf_batch_pileup.  Else the site CSR stays in HBM for a consumer
+// in another file (pf_assign.hip): *dev takes over win_off, pos and cnt
+// (pf_pile_dev_free), nothing but the site count is copied back, *out is not
+// touched, and the load stage is not run again: the consumer has just run it
+// (pf_batch_calls_view).
+static int pile_run(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *read_hp, uint32_t n_hp, pf_pileup_t **out,
+                    pf_pile_dev *dev) {
+    if (!ctx || !b || (!out && !dev) || b->ctx != ctx) return PF_ERR_ARG;
+    if (out) *out = nullptr;
+    if (dev) memset(dev, 0, sizeof *dev);
     if (b->n_launch != b->n_finish) return PF_ERR_ARG;       // a run is in flight
     const uint32_t T = pile_tile();
     if (!T) return PF_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     // record level: K0, scan and pack size the batch and leave its reads and calls
-    if (b->has_aln) {
+    if (b->has_aln && !dev) {
         const int rc = run_debug(b, 0);
         if (rc) return rc;
     }
@@ -1558,7 +1564,7 @@ extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *rea
         (void)hipStreamSynchronize(st);
         for (void *p : tmp) (void)hipFree(p);
         for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (rc) {
+        if (rc || dev) {
             if (res) { res->win_off = h_win_off; pf_pileup_free(res); } else free(h_win_off);
         } else
             *out = res;
@@ -1567,6 +1573,7 @@ extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *rea
     if (!res || !h_win_off) return done(PF_ERR_NOMEM);
     res->n_windows = W;
     res->win_off = h_win_off;
+    if (dev) dev->W = W;
     if (W == 0) return done(PF_OK);
 
     // items: the tiles of every window
@@ -1633,7 +1640,26 @@ extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *rea
         return done(PF_ERR_LIMIT);
     }
     float ms0 = 0.0f, ms1 = 0.0f;
-    if (n_sites) {
+    if (n_sites && dev) {
+        void *p_op = nullptr, *p_oc = nullptr;
+        if (talloc(&p_op, 4ull * n_sites) || talloc(&p_oc, 24ull * n_sites)) return done(PF_ERR_NOMEM);
+        a.out_pos = static_cast<uint32_t *>(p_op);
+        a.out_cnt = static_cast<uint32_t *>(p_oc);
+        if (hipEventRecord(ev[2], st) != hipSuccess) return done(PF_ERR_HIP);
+        hipLaunchKernelGGL(pf_pile_emit, dim3(a.n_items), dim3(PF_PILE_THREADS), lds, st, a);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[3], st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return done(PF_ERR_HIP);
+        (void)hipEventElapsedTime(&ms1, ev[2], ev[3]);
+        // the three arrays outlive this call
+        for (void *keep : {p_wo, p_op, p_oc})
+            for (size_t i = 0; i < tmp.size(); i++)
+                if (tmp[i] == keep) { tmp.erase(tmp.begin() + (long)i); break; }
+        dev->n_sites = n_sites;
+        dev->win_off = static_cast<uint64_t *>(p_wo);
+        dev->pos = a.out_pos;
+        dev->cnt = a.out_cnt;
+    } else if (n_sites) {
         uint32_t *h_pos = (uint32_t *)malloc(4ull * n_sites), *h_cnt = (uint32_t *)malloc(24ull * n_sites);
         res->pos = h_pos;
         res->cnt = h_cnt;
@@ -1656,10 +1682,33 @@ extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *rea
     (void)hipGetLastError();
     res->n_sites = n_sites;
     res->ms_kernels = ms0 + ms1;
+    if (dev) dev->ms_kernels = ms0 + ms1;
     return done(PF_OK);
 }
 
-// ---- the batch's reads and calls for a consumer in another file (pf_perm.hip):
+extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *read_hp, uint32_t n_hp,
+                               pf_pileup_t **out) {
+    if (!out) return PF_ERR_ARG;
+    return pile_run(ctx, b, read_hp, n_hp, out, nullptr);
+}
+
+// ---- the same pileup with its site CSR left in HBM (pf_assign.hip), to be
+// called right after pf_batch_calls_view, whose load stage it relies on.  Not
+// part of the public header.  No site: n_sites 0 and NULL arrays.
+extern "C" int pf_batch_pileup_dev(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *read_hp, uint32_t n_hp, pf_pile_dev *dev) {
+    if (!dev) return PF_ERR_ARG;
+    return pile_run(ctx, b, read_hp, n_hp, nullptr, dev);
+}
+
+extern "C" void pf_pile_dev_free(pf_pile_dev *dev) {
+    if (!dev) return;
+    (void)hipFree(dev->win_off);
+    (void)hipFree(dev->pos);
+    (void)hipFree(dev->cnt);
+    memset(dev, 0, sizeof *dev);
+}
+
+// ---- the batch's reads and calls for a consumer in another file (pf_perm.hip, pf_assign.hip):
 // pf_batch_pileup's checks and load stage, then the device view with W, R and N
 // as they stand after the load.  Not part of the public header.
 extern "C" int pf_batch_calls_view(pf_ctx_t *ctx, pf_dbatch_t *b, pf_dev_batch *view) {

@@ -9,7 +9,8 @@
  *   pomfret-amd varhaptag -o out.bam in.vcf in.bam
  *   pomfret-amd hapmeth   -o out [-r chrom[:beg-end]] [--chunk-size N] [-q mapq] [-L minlen] [--host-fetch]
  *                         [--dmr [--dmr-min-cov N] [--dmr-delta PCT] [--dmr-gap N] [--dmr-min-sites N] [--dmr-max-p P]
- *                         [--dmr-blocks blocks.gtf] [--dmr-perm N [--dmr-seed S]]] tagged.bam
+ *                         [--dmr-blocks blocks.gtf] [--dmr-perm N [--dmr-seed S]]
+ *                         [--assign [--assign-min-llr BITS] [--assign-min-calls N]]] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
  * cliopt_haptag_t (cli.c:332-343); the -c arithmetic (cov/10, cov/4), the
@@ -33,6 +34,7 @@
  * methylation p-value (pf_hapmeth_main; no reference counterpart).
  */
 #include <getopt.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -93,7 +95,8 @@ static void help_methphase(const char *prefix) {
 
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
        O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
-       O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED };
+       O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED,
+       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -113,6 +116,8 @@ static const struct option longopts[] = {
     {"dmr-min-sites", required_argument, 0, O_DMR_SITES}, {"dmr-max-p", required_argument, 0, O_DMR_MAXP},
     {"dmr-blocks", required_argument, 0, O_DMR_BLOCKS},
     {"dmr-perm", required_argument, 0, O_DMR_PERM}, {"dmr-seed", required_argument, 0, O_DMR_SEED},
+    {"assign", no_argument, 0, O_ASSIGN},        {"assign-min-llr", required_argument, 0, O_ASSIGN_LLR},
+    {"assign-min-calls", required_argument, 0, O_ASSIGN_CALLS},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -312,6 +317,14 @@ static void help_hapmeth(void) {
                     "               holds although one read contributes to many CpGs (\".\" where a region has reads of\n"
                     "               one haplotype only, or more than 4096).  N in 1 .. 1000000. [0: off]\n");
     fprintf(stderr, "  --dmr-seed S [opt] Seed of the permutations. [1]\n");
+    fprintf(stderr, "  --assign [opt] Needs --dmr.  Also write {out_prefix}.hapmeth.assign.tsv: every untagged read with a call\n"
+                    "               at a member CpG of a region (those that pass --dmr-max-p), scored against the region's\n"
+                    "               tagged reads: qname, chrom, start, end (the region), n_calls (the read's calls used),\n"
+                    "               llr (log2 odds of haplotype 1 against 2, Laplace-smoothed per CpG) and hp: 1, 2 or \".\"\n"
+                    "               (not assigned).  One line per region and read; no BAM is rewritten.\n");
+    fprintf(stderr, "  --assign-min-llr BITS [opt] Least |llr| for a tag, a decimal in (0, 64].  The default asks for\n"
+                    "               odds of 8:1; it is a choice, not a measured optimum. [3]\n");
+    fprintf(stderr, "  --assign-min-calls N [opt] Least n_calls for a tag, 1 .. 65535; a choice as well. [2]\n");
 }
 
 /* hapmeth: one device, the jobs one after another (pf_hapmeth_main) */
@@ -327,8 +340,11 @@ static int hapmeth(int argc, char **argv) {
     dm.max_p = 1.0;
     pf_hapmeth_perm_t pm;
     pm.n_perm = 0; pm.seed = 1;
-    int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0;
-    long dcov = 5, ddelta = 40, dgap = 500, dsites = 5, dperm = 0, dseed = 1;
+    pf_hapmeth_assign_t am;
+    memset(&am, 0, sizeof am);
+    int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0;
+    long dcov = 5, ddelta = 40, dgap = 500, dsites = 5, dperm = 0, dseed = 1, acalls = 2;
+    double allr = 3.0;
     char *end;
     if (argc == 1) { help_hapmeth(); return 1; }
     optind = 1;
@@ -356,6 +372,9 @@ static int hapmeth(int argc, char **argv) {
         case O_DMR_BLOCKS: dmr_opt = 1; dm.blocks_path = optarg; break;
         case O_DMR_PERM: dmr_opt = 1; dperm = strtol(optarg, &end, 10); if (*end || !*optarg) dperm = -1; break;
         case O_DMR_SEED: dmr_opt = 1; dseed = strtol(optarg, &end, 10); if (*end || !*optarg) dseed = -1; break;
+        case O_ASSIGN: assign = 1; break;
+        case O_ASSIGN_LLR: assign_opt = 1; allr = strtod(optarg, &end); if (*end || !*optarg) allr = -1.0; break;
+        case O_ASSIGN_CALLS: assign_opt = 1; acalls = strtol(optarg, &end, 10); if (*end || !*optarg) acalls = -1; break;
         default:
             fprintf(stderr, "[E::parse_cli_hapmeth] unknown or incomplete option \"%s\"\n", argv[optind - 1]);
             return 1;
@@ -378,6 +397,11 @@ static int hapmeth(int argc, char **argv) {
     if (!(dm.max_p >= 0.0 && dm.max_p <= 1.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-max-p (0 .. 1)\n"); return 1; }
     if (dperm < 0 || dperm > 1000000) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-perm (0 .. 1000000)\n"); return 1; }
     if (dseed < 0 || dseed > 0xFFFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-seed (0 .. 4294967295)\n"); return 1; }
+    if (assign_opt && !assign) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign-* options need --assign\n"); return 1; }
+    if (assign && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign needs --dmr\n"); return 1; }
+    if (!(allr > 0.0 && allr <= 64.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --assign-min-llr (above 0, at most 64)\n"); return 1; }
+    if (acalls < 1 || acalls > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --assign-min-calls (1 .. 65535)\n"); return 1; }
+    am.min_llr_q16 = (int64_t)llround(allr * 65536.0); am.min_calls = (uint32_t)acalls;
     pm.n_perm = (uint32_t)dperm; pm.seed = (uint32_t)dseed;
     dm.cfg.min_cov = (uint32_t)dcov; dm.cfg.min_delta_pct = (uint32_t)ddelta;
     dm.cfg.max_gap = (uint32_t)dgap; dm.cfg.min_sites = (uint32_t)dsites;
@@ -390,7 +414,9 @@ static int hapmeth(int argc, char **argv) {
     pf_hapmeth_stats_t st;
     pf_hapmeth_dmr_stats_t dst;
     pf_hapmeth_perm_stats_t pst;
-    const int rc = pf_hapmeth_run_perm(&op, dmr ? &dm : NULL, pm.n_perm ? &pm : NULL, &st, &dst, &pst);
+    pf_hapmeth_assign_stats_t ast;
+    const int rc = pf_hapmeth_run_assign(&op, dmr ? &dm : NULL, pm.n_perm ? &pm : NULL, assign ? &am : NULL, &st, &dst, &pst,
+                                         &ast);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;
@@ -401,6 +427,9 @@ static int hapmeth(int argc, char **argv) {
                 op.out_prefix);
     if (pm.n_perm)
         fprintf(stderr, "[M::main] %llu of them with a permutation p-value\n", (unsigned long long)pst.n_tested);
+    if (assign)
+        fprintf(stderr, "[M::main] %llu scored reads written to %s.hapmeth.assign.tsv, %llu of them with a tag\n",
+                (unsigned long long)ast.n_lines, op.out_prefix, (unsigned long long)(ast.n_h1 + ast.n_h2));
     return 0;
 }
 

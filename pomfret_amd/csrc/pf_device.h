@@ -52,6 +52,11 @@
 #define PF_PERM_THREADS 256         /* the permutation test's workgroup (PF_PERM_THREADS=<64|256|1024> overrides it) */
 #define PF_PERM_THREADS_MAX 1024
 #define PF_PERM_READS 4096          /* participating reads per window held in LDS (PF_PERM_MAX_READS): 8 B each */
+#define PF_ASSIGN_TILE 4096         /* sites per LDS tile of pf_assign_score: position and two weights, 12 B each, 48 KB
+                                      (PF_ASSIGN_TILE=<n> overrides it downwards) */
+#define PF_ASSIGN_THREADS 256       /* its workgroup: each wave takes 64 of the window's reads at a time (1,024 measured:
+                                      profiles/assign/README.md) */
+#define PF_ASSIGN_WAVES (PF_ASSIGN_THREADS / PF_WAVE)
 #define PF_NONE 0xFFFFFFFFu
 
 /* status bits */
@@ -154,6 +159,17 @@ struct pf_pile_args {
     uint32_t *out_pos;                               /* [n_sites] */
     uint32_t *out_cnt;                               /* [n_sites*6] */
     uint32_t *status;                                /* bit 0: a 16-bit counter wrapped */
+};
+
+/* pf_batch_pileup's site CSR left in HBM (pf_batch_pileup_dev, pf_api.hip) for
+ * a consumer in another file (pf_assign.hip); pf_pile_dev_free releases it */
+struct pf_pile_dev {
+    uint32_t W;
+    uint64_t n_sites;                                /* 0: the three arrays are NULL */
+    uint64_t *win_off;                               /* [W+1] */
+    uint32_t *pos;                                   /* [n_sites] ascending inside a window */
+    uint32_t *cnt;                                   /* [n_sites*6] */
+    float ms_kernels;                                /* the pileup kernels */
 };
 
 #endif

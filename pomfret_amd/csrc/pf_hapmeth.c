@@ -25,7 +25,13 @@
  *                     each contig's end: its regions become the windows of
  *                     jobs fetched like the first pass's and tested by
  *                     pf_batch_permtest, and pf_write_dmr_perm's three columns
- *                     follow pf_write_dmr's.
+ *                     follow pf_write_dmr's;
+ *   pf_write_assign:  the scored untagged reads of a pf_batch_assign result as
+ *                     lines of {prefix}.hapmeth.assign.tsv (host only);
+ *   pf_hapmeth_run_assign: pf_hapmeth_run_perm, and with --assign the same
+ *                     second pass (each job fetched once, for the test and the
+ *                     assignment alike) scores every region's untagged reads
+ *                     against the region's tagged ones (pf_batch_assign).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -229,6 +235,33 @@ int pf_write_dmr_perm(const char *path, const char *chrom, const pf_dmr_t *dmr, 
     return write_dmr(path, chrom, dmr, perm, max_p, header, NULL, NULL);
 }
 
+int pf_write_assign(const char *path, const char *chrom, const pf_assign_t *a, const uint32_t *win_start,
+                    const uint32_t *win_end, const uint32_t *rec_of_read, const uint64_t *qname_off, const char *qname,
+                    int header, uint64_t *n_lines) {
+    if (n_lines) *n_lines = 0;
+    const uint32_t W = a ? a->n_windows : 0;
+    if (!path) return PF_ERR_ARG;
+    if (W && (!chrom || !win_start || !win_end || !a->win_read_off || a->win_read_off[W] > a->n_reads)) return PF_ERR_ARG;
+    if (W && a->win_read_off[W] && (!a->n_used || !a->llr || !a->hp || !qname_off || !qname)) return PF_ERR_ARG;
+    for (uint32_t w = 0; w < W; w++)
+        if (a->win_read_off[w] > a->win_read_off[w + 1]) return PF_ERR_ARG;
+    FILE *fp = fopen(path, header ? "w" : "a");
+    if (!fp) return -1;
+    if (header) fprintf(fp, "#qname\tchrom\tstart\tend\tn_calls\tllr\thp\n");
+    for (uint32_t w = 0; w < W; w++)
+        for (uint32_t r = a->win_read_off[w]; r < a->win_read_off[w + 1]; r++) {
+            if (a->n_used[r] < 1u) continue;
+            const uint32_t rec = rec_of_read ? rec_of_read[r] : r;
+            fprintf(fp, "%.*s\t%s\t%u\t%u\t%u\t%.4f\t%s\n", (int)(qname_off[rec + 1] - qname_off[rec]), qname + qname_off[rec],
+                    chrom, win_start[w], win_end[w], a->n_used[r], (double)a->llr[r] / 65536.0,
+                    a->hp[r] == 0 ? "1" : a->hp[r] == 1 ? "2" : ".");
+            if (n_lines) ++*n_lines;
+        }
+    const int bad = ferror(fp);
+    if (fclose(fp) != 0 || bad) return -1;
+    return PF_OK;
+}
+
 /* "chrom" or "chrom:beg-end" / "chrom:beg" (1-based inclusive, commas allowed)
  * -> tid and the 0-based [*s, *e); a name that holds ':' itself is tried whole
  * first */
@@ -283,6 +316,10 @@ typedef struct {
     const pf_hapmeth_perm_t *perm;
     uint32_t jw;               /* windows per job */
     pf_hapmeth_perm_stats_t pst;
+    /* --assign */
+    const pf_hapmeth_assign_t *assign;
+    char *apath;
+    pf_hapmeth_assign_stats_t ast;
 } hm_t;
 
 /* the fetch of one job, the same in both passes: the records of the windows
@@ -362,23 +399,32 @@ static int hm_breaks(hm_t *H, const char *chrom) {
     return PF_OK;
 }
 
-/* --dmr-perm's second pass over a contig's final regions: the regions that
- * pass max_p are the windows [start, end) of jobs of at most jw windows, each
- * fetched as in the first pass and tested under the records' HP tags; run k's
- * result lands in window k of *out (malloc'ed arrays: pf_perm_free) */
-static int hm_perm(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t **out) {
+/* the second pass over a contig's final regions, for --dmr-perm and --assign:
+ * the regions that pass max_p are the windows [start, end) of jobs of at most
+ * jw windows, each fetched once as in the first pass; on that batch, under the
+ * records' HP tags, pf_batch_permtest (run k's result lands in window k of
+ * *out; malloc'ed arrays: pf_perm_free) and / or pf_batch_assign, whose lines
+ * are appended to the assign file job by job (region order) */
+static int hm_second(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t **out) {
     *out = NULL;
     const uint64_t n = fin->n_runs;
     if (n > 0xFFFFFFFFull) return PF_ERR_LIMIT;
-    pf_perm_t *P = (pf_perm_t *)calloc(1, sizeof *P);
-    if (!P) return PF_ERR_NOMEM;
-    uint32_t *nr = (uint32_t *)calloc(2 * n + 1, 4), *hits = (uint32_t *)calloc(n + 1, 4), *stat = (uint32_t *)calloc(n + 1, 4);
-    uint64_t *sum = (uint64_t *)calloc(4 * n + 1, 8);
+    pf_perm_t *P = NULL;
+    uint32_t *nr = NULL, *hits = NULL, *stat = NULL;
+    uint64_t *sum = NULL;
+    int rc = PF_OK;
+    if (H->perm) {
+        P = (pf_perm_t *)calloc(1, sizeof *P);
+        if (!P) return PF_ERR_NOMEM;
+        nr = (uint32_t *)calloc(2 * n + 1, 4); hits = (uint32_t *)calloc(n + 1, 4); stat = (uint32_t *)calloc(n + 1, 4);
+        sum = (uint64_t *)calloc(4 * n + 1, 8);
+        P->n_windows = (uint32_t)n; P->n_perm = H->perm->n_perm; P->seed = H->perm->seed;
+        P->n_reads = nr; P->sum = sum; P->hits = hits; P->status = stat;
+        if (!nr || !hits || !stat || !sum) rc = PF_ERR_NOMEM;
+    }
     uint32_t *ws = (uint32_t *)malloc(4ull * H->jw), *we = (uint32_t *)malloc(4ull * H->jw);
     uint64_t *idx = (uint64_t *)malloc(8ull * H->jw);
-    P->n_windows = (uint32_t)n; P->n_perm = H->perm->n_perm; P->seed = H->perm->seed;
-    P->n_reads = nr; P->sum = sum; P->hits = hits; P->status = stat;
-    int rc = (nr && hits && stat && sum && ws && we && idx) ? PF_OK : PF_ERR_NOMEM;
+    if (!ws || !we || !idx) rc = PF_ERR_NOMEM;
     uint32_t k = 0;
     for (uint64_t i = 0; i <= n && !rc; i++) {
         if (i < n) {
@@ -395,20 +441,51 @@ static int hm_perm(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t **
         pf_bam_dev_fetch_t *F = NULL;
         pf_bam_records_t *recs = NULL;
         pf_perm_t *part = NULL;
-        rc = hm_fetch(H, chrom, k, ws, we, &db, &F, &recs, &H->pst.n_records);
+        pf_assign_t *as = NULL;
+        uint64_t fetched = 0;
+        rc = hm_fetch(H, chrom, k, ws, we, &db, &F, &recs, &fetched);
+        if (H->perm) H->pst.n_records += fetched;
+        if (H->assign) H->ast.n_records += fetched;
         if (rc == PF_ERR_LIMIT)
             fprintf(stderr, "[E::pf_hapmeth_main] %s:%u-%u: a region exceeds a device limit (65,535 records per window)\n",
                     chrom, ws[0] + 1, we[k - 1]);
-        if (!rc) rc = pf_batch_permtest(H->ctx, db, NULL, 0, H->perm->n_perm, H->perm->seed, &part);
-        if (!rc && part->n_windows != k) rc = PF_ERR_INTERNAL;
-        for (uint32_t j = 0; j < k && !rc; j++) {
-            nr[2 * idx[j]] = part->n_reads[2 * j];
-            nr[2 * idx[j] + 1] = part->n_reads[2 * j + 1];
-            for (int q = 0; q < 4; q++) sum[4 * idx[j] + q] = part->sum[4 * j + q];
-            hits[idx[j]] = part->hits[j];
-            stat[idx[j]] = part->status[j];
+        if (!rc && H->perm) {
+            rc = pf_batch_permtest(H->ctx, db, NULL, 0, H->perm->n_perm, H->perm->seed, &part);
+            if (!rc && part->n_windows != k) rc = PF_ERR_INTERNAL;
+            for (uint32_t j = 0; j < k && !rc; j++) {
+                nr[2 * idx[j]] = part->n_reads[2 * j];
+                nr[2 * idx[j] + 1] = part->n_reads[2 * j + 1];
+                for (int q = 0; q < 4; q++) sum[4 * idx[j] + q] = part->sum[4 * j + q];
+                hits[idx[j]] = part->hits[j];
+                stat[idx[j]] = part->status[j];
+            }
+            if (!rc) H->pst.ms_kernels += part->ms_kernels;
         }
-        if (!rc) H->pst.ms_kernels += part->ms_kernels;
+        if (!rc && H->assign) {
+            pf_assign_cfg_t ac;
+            ac.min_cov = H->dmr->cfg.min_cov; ac.min_calls = H->assign->min_calls; ac.min_llr_q16 = H->assign->min_llr_q16;
+            rc = pf_batch_assign(H->ctx, db, NULL, 0, &ac, &as);
+            if (!rc && as->n_windows != k) rc = PF_ERR_INTERNAL;
+            uint32_t *rec_of = NULL;
+            if (!rc) {
+                rec_of = (uint32_t *)malloc(4ull * as->n_reads + 4);
+                rc = rec_of ? pf_batch_read_recs(db, rec_of, as->n_reads) : PF_ERR_NOMEM;
+            }
+            uint64_t lines = 0;
+            if (!rc)
+                rc = pf_write_assign(H->apath, chrom, as, ws, we, rec_of, recs ? recs->qname_off : F->qname_off,
+                                     recs ? recs->qname : F->qname, 0, &lines);
+            if (!rc) {
+                H->ast.n_lines += lines;
+                for (uint32_t j = 0; j < k; j++) {
+                    H->ast.n_h1 += as->win_n[3 * j + 1];
+                    H->ast.n_h2 += as->win_n[3 * j + 2];
+                }
+                H->ast.ms_kernels += as->ms_kernels;
+            }
+            free(rec_of);
+        }
+        pf_assign_free(as);
         pf_perm_free(part);
         if (db) pf_batch_free(db);
         if (F) pf_bam_dev_fetch_free(F);
@@ -422,13 +499,13 @@ static int hm_perm(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t **
     return rc;
 }
 
-/* the contig's regions are complete: close the carry, (test,) append */
+/* the contig's regions are complete: close the carry, (test, assign,) append */
 static int hm_flush(hm_t *H, const char *chrom) {
     pf_dmr_t *fin = NULL;
     pf_perm_t *P = NULL;
     uint64_t lines = 0, dots = 0;
     int rc = pf_dmr_acc_flush(H->acc, &fin);
-    if (!rc && H->perm) rc = hm_perm(H, chrom, fin, &P);
+    if (!rc && (H->perm || H->assign)) rc = hm_second(H, chrom, fin, &P);
     if (!rc) rc = write_dmr(H->dpath, chrom, fin, P, H->dmr->max_p, 0, &lines, &dots);
     if (!rc) {
         H->dst.n_regions += lines;
@@ -483,17 +560,26 @@ int pf_hapmeth_run(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, pf_h
 
 int pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
                         pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats, pf_hapmeth_perm_stats_t *pstats) {
+    return pf_hapmeth_run_assign(o, dmr, perm, NULL, stats, dstats, pstats, NULL);
+}
+
+int pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
+                          const pf_hapmeth_assign_t *assign, pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats,
+                          pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats) {
     if (stats) memset(stats, 0, sizeof *stats);
     if (dstats) memset(dstats, 0, sizeof *dstats);
     if (pstats) memset(pstats, 0, sizeof *pstats);
+    if (astats) memset(astats, 0, sizeof *astats);
     if (!o || !o->bam_path || !o->out_prefix || !o->out_prefix[0]) return PF_ERR_ARG;
     if (dmr && (dmr->cfg.min_delta_pct > 100u || !(dmr->max_p >= 0.0))) return PF_ERR_ARG;
     if (perm && (!dmr || perm->n_perm < 1u || perm->n_perm > PF_PERM_MAX_PERM)) return PF_ERR_ARG;
+    if (assign && !dmr) return PF_ERR_ARG;
     hm_t H;
     memset(&H, 0, sizeof H);
     H.o = o;
     H.dmr = dmr;
     H.perm = perm;
+    H.assign = assign;
     H.lc = o->load;
     /* the batch's phasing parameters are not used by the pileup: the reference's defaults */
     H.cfg.k = 3; H.cfg.k_span = 5000; H.cfg.cov_for_selection = 6; H.cfg.n_cand = 15; H.cfg.hard_cov = 15;
@@ -514,7 +600,7 @@ int pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
         tid1 = tid0 + 1;
     }
     uint32_t *ws = NULL, *we = NULL;
-    int made = 0, dmade = 0;
+    int made = 0, dmade = 0, amade = 0;
     if (!rc && dmr && dmr->blocks_path) {
         rc = pf_interval_gaps(dmr->blocks_path, PF_INTERVALS_GTF, 0, &H.blocks);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot read the phase blocks of %s\n", dmr->blocks_path);
@@ -527,12 +613,14 @@ int pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
         const size_t l = strlen(o->out_prefix) + 24;
         H.path = (char *)malloc(l);
         H.dpath = (char *)malloc(l);
+        H.apath = (char *)malloc(l);
         ws = (uint32_t *)malloc(4ull * jw);
         we = (uint32_t *)malloc(4ull * jw);
-        if (!H.path || !H.dpath || !ws || !we) rc = PF_ERR_NOMEM;
+        if (!H.path || !H.dpath || !H.apath || !ws || !we) rc = PF_ERR_NOMEM;
         else {
             snprintf(H.path, l, "%s.hapmeth.bed", o->out_prefix);
             snprintf(H.dpath, l, "%s.hapmeth.dmr.bed", o->out_prefix);
+            snprintf(H.apath, l, "%s.hapmeth.assign.tsv", o->out_prefix);
         }
     }
     if (!rc) {
@@ -547,12 +635,18 @@ int pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.dpath);
         else dmade = 1;
     }
+    if (!rc && assign) {
+        rc = pf_write_assign(H.apath, NULL, NULL, NULL, NULL, NULL, NULL, NULL, 1, NULL);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.apath);
+        else amade = 1;
+    }
     for (int32_t t = tid0; t < tid1 && !rc; t++) {
         if (!o->region) { s = 0; e = pf_bam_target_len(H.bam, t); }
         rc = hm_span(&H, t, s, e, chunk, jw, ws, we);
     }
     if (rc && made) (void)unlink(H.path);              /* no truncated output behind a failure */
     if (rc && dmade) (void)unlink(H.dpath);
+    if (rc && amade) (void)unlink(H.apath);
     if (!rc && o->verbose)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu windows (%llu without reads in the index, skipped), %llu records, "
                 "%llu sites, pileup kernels %.3f ms\n", (unsigned long long)H.st.n_windows,
@@ -566,13 +660,20 @@ int pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
                 "%llu records fetched again, permutation kernels %.3f ms\n", (unsigned long long)H.pst.n_tested,
                 perm->n_perm, perm->seed, (unsigned long long)H.pst.n_untested, (unsigned long long)H.pst.n_records,
                 H.pst.ms_kernels);
+    if (!rc && o->verbose && assign)
+        fprintf(stderr, "[M::pf_hapmeth_main] %llu candidate reads scored, %llu assigned (%llu h1 / %llu h2), "
+                "%llu records fetched for it, assign kernels %.3f ms\n", (unsigned long long)H.ast.n_lines,
+                (unsigned long long)(H.ast.n_h1 + H.ast.n_h2), (unsigned long long)H.ast.n_h1,
+                (unsigned long long)H.ast.n_h2, (unsigned long long)H.ast.n_records, H.ast.ms_kernels);
     if (stats) *stats = H.st;
     if (dstats) *dstats = H.dst;
     if (pstats) *pstats = H.pst;
+    if (astats) *astats = H.ast;
     free(ws);
     free(we);
     free(H.path);
     free(H.dpath);
+    free(H.apath);
     free(H.brk);
     pf_dmr_acc_free(H.acc);
     pf_gaps_free(H.blocks);

@@ -34,7 +34,7 @@ import numpy as np
 from ._lib import (INTERVALS_GTF, INTERVALS_TSV, INTERVALS_VCF, PomfretError, _blocks_contigs, _check,  # noqa: F401
                    _breaks, _dmr_dict, _dmr_to_c, _gaps_contigs, _PfBlocks, _PfGaps, lib)
 from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfHapmethDmrStats, PfHapmethOpts,
-                  PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup)
+                  AssignConfig, PfAssign, PfHapmethAssign, PfHapmethAssignStats, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
 JOB_WINDOWS, JOB_HAPTAG = 0, 1
@@ -121,6 +121,10 @@ def _bind():
     L.pf_hapmeth_run_perm.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethPerm),
                                       C.POINTER(PfHapmethStats), C.POINTER(PfHapmethDmrStats),
                                       C.POINTER(PfHapmethPermStats)]
+    L.pf_hapmeth_run_assign.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethPerm),
+                                        C.POINTER(PfHapmethAssign), C.POINTER(PfHapmethStats),
+                                        C.POINTER(PfHapmethDmrStats), C.POINTER(PfHapmethPermStats),
+                                        C.POINTER(PfHapmethAssignStats)]
     L.pf_tags_new.restype = vp
     L.pf_tags_free.argtypes = [vp]
     L.pf_tags_size.argtypes = [vp]
@@ -484,7 +488,8 @@ def report_files(bam_path: str, vcf_path: str, out_prefix: Optional[str], cov: i
 def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk_size: int = 100_000,
                   lcfg: Optional[LoadConfig] = None, host_fetch: bool = False, threads: int = 1, device: int = 0,
                   job_windows: int = 0, dmr: Optional[DmrConfig] = None, dmr_max_p: float = 1.0,
-                  dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1) -> Dict:
+                  dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1,
+                  assign: Optional[AssignConfig] = None) -> Dict:
     """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
@@ -504,10 +509,18 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     p-value that holds under the correlation of one read's calls, and the dict
     n_tested (lines with a numeric perm_p), n_untested (lines with "."),
     perm_records (records the second pass fetched) and perm_ms_kernels;
-    dmr_seed seeds the permutations."""
+    dmr_seed seeds the permutations.
+    assign: an AssignConfig (`--assign`; needs dmr, whose min_cov is the one
+    used) also writes out_prefix + .hapmeth.assign.tsv, one line per region
+    and untagged read with a call at one of its member CpGs (qname, chrom,
+    start, end, n_calls, llr in bits, hp 1 / 2 / "."), and adds assign_path,
+    n_assign_lines, n_assigned (n_assigned_h1 + n_assigned_h2), assign_records
+    and assign_ms_kernels to the dict."""
     L = _bind()
     if dmr_perm and dmr is None:
         raise PomfretError("hapmeth_files: dmr_perm needs dmr")
+    if assign is not None and dmr is None:
+        raise PomfretError("hapmeth_files: assign needs dmr")
     lc = lcfg or LoadConfig(min_len=0)
     o = PfHapmethOpts(bam.encode(), out_prefix.encode(), region.encode() if region else None, int(chunk_size),
                       int(job_windows), lc.to_c(), int(threads), int(bool(host_fetch)), int(device), 0)
@@ -519,8 +532,14 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         dst = PfHapmethDmrStats()
         pm = PfHapmethPerm(int(dmr_perm), int(dmr_seed))
         pst = PfHapmethPermStats()
-        _check(L.pf_hapmeth_run_perm(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(st),
-                                     C.byref(dst), C.byref(pst)), "pf_hapmeth_run_perm")
+        if assign is None:
+            _check(L.pf_hapmeth_run_perm(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(st),
+                                         C.byref(dst), C.byref(pst)), "pf_hapmeth_run_perm")
+        else:
+            am = PfHapmethAssign(assign.min_llr_q16, int(assign.min_calls), 0)
+            ast = PfHapmethAssignStats()
+            _check(L.pf_hapmeth_run_assign(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(am),
+                                           C.byref(st), C.byref(dst), C.byref(pst), C.byref(ast)), "pf_hapmeth_run_assign")
     res = dict(path=out_prefix + ".hapmeth.bed", n_windows=int(st.n_windows), n_skipped=int(st.n_skipped),
                n_records=int(st.n_records), n_sites=int(st.n_sites), ms_kernels=float(st.ms_kernels))
     if dmr is not None:
@@ -529,6 +548,11 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         if dmr_perm:
             res.update(n_tested=int(pst.n_tested), n_untested=int(pst.n_untested), perm_records=int(pst.n_records),
                        perm_ms_kernels=float(pst.ms_kernels))
+        if assign is not None:
+            res.update(assign_path=out_prefix + ".hapmeth.assign.tsv", n_assign_lines=int(ast.n_lines),
+                       n_assigned=int(ast.n_h1 + ast.n_h2), n_assigned_h1=int(ast.n_h1), n_assigned_h2=int(ast.n_h2),
+                       assign_records=int(ast.n_records),
+                       assign_ms_kernels=float(ast.ms_kernels))
     return res
 
 
@@ -592,6 +616,45 @@ def write_dmr_perm(path: str, chrom: str, dmr: Dict, perm: Dict, max_p: float = 
                hits.ctypes.data_as(u32p), stat.ctypes.data_as(u32p), 0.0)
     _check(L.pf_write_dmr_perm(path.encode(), chrom.encode(), C.byref(d), C.byref(p), float(max_p), int(bool(header))),
            "pf_write_dmr_perm")
+
+
+def write_assign(path: str, chrom: str, res: Optional[Dict], win_start, win_end, qnames, rec_of_read=None,
+                 header: bool = True) -> int:
+    """The scored reads of a DeviceBatch.assign dict as hapmeth --assign lines
+    (pf_write_assign, host only): qname, chrom, the window's start and end,
+    n_calls, llr = S / 65536 as %.4f and hp 1 / 2 / "."; one line per window
+    and read of it with n_used >= 1.  qnames: the records' names (str or
+    bytes); rec_of_read: each read's record, None for the identity.  res None
+    (with header): the header alone.  Returns the lines written."""
+    L = _bind()
+    n = C.c_uint64(0)
+    if res is None:
+        _check(L.pf_write_assign(path.encode(), chrom.encode(), None, None, None, None, None, None, int(bool(header)),
+                                 C.byref(n)), "pf_write_assign")
+        return 0
+    names = [q if isinstance(q, bytes) else str(q).encode() for q in qnames]
+    qoff = np.zeros(len(names) + 1, np.uint64)
+    qoff[1:] = np.cumsum([len(q) for q in names])
+    blob = b"".join(names) + b"\0"
+    wro = np.ascontiguousarray(np.append(np.asarray(res["win_read_off"], np.uint32), 0).astype(np.uint32))
+    W, R = wro.size - 2, int(np.size(res["hp"]))
+    pad = lambda a, dt: np.ascontiguousarray(np.append(np.asarray(a, dt).ravel(), 0).astype(dt))
+    nu, llr, hp = pad(res["n_used"], np.uint32), pad(res["llr"], np.int64), pad(res["hp"], np.uint8)
+    wn = pad(res.get("win_n", np.zeros(3 * W)), np.uint32)
+    ws, we = pad(win_start, np.uint32), pad(win_end, np.uint32)
+    if ws.size - 1 != W or we.size - 1 != W or nu.size - 1 != R or llr.size - 1 != R:
+        raise PomfretError("inconsistent assign arrays")
+    rr = None if rec_of_read is None else pad(rec_of_read, np.uint32)
+    recs = np.arange(R) if rr is None else rr[:R]
+    if R and int(np.max(recs)) >= len(names):
+        raise PomfretError("write_assign: a read's record has no qname")
+    u32p = C.POINTER(C.c_uint32)
+    a = PfAssign(W, R, wro.ctypes.data_as(u32p), nu.ctypes.data_as(u32p), llr.ctypes.data_as(C.POINTER(C.c_int64)),
+                 hp.ctypes.data_as(C.POINTER(C.c_uint8)), wn.ctypes.data_as(u32p), 0.0)
+    _check(L.pf_write_assign(path.encode(), chrom.encode(), C.byref(a), ws.ctypes.data, we.ctypes.data,
+                             None if rr is None else rr.ctypes.data, qoff.ctypes.data, blob, int(bool(header)), C.byref(n)),
+           "pf_write_assign")
+    return int(n.value)
 
 
 def write_hapmeth(path: str, chrom: str, pile: Dict, header: bool = True, w0: int = 0, w1: Optional[int] = None):
