@@ -496,8 +496,9 @@ void pf_perm_free(pf_perm_t *p);
  * untagged read is never part of it.  All in integers; windows may overlap,
  * every window is scored on its own.  Out of scope: writing a retagged BAM;
  * merging one read's scores across regions or phase blocks (one row per
- * (window, read), the consumer decides); leave-one-out scoring of reads that
- * carry a tag; filtering regions by perm_p; more than one device.
+ * (window, read), the consumer decides); filtering regions by perm_p; more
+ * than one device.  Leave-one-out scoring of the reads that carry a tag is
+ * pf_batch_tagcheck's, below.
  *   model        for every position p of the window m1,u1,m2,u2 are the meth /
  *                unmeth entries of the window's reads tagged 0 and 1, exactly
  *                pf_batch_pileup's cnt[0..3]; n1 = m1+u1, n2 = m2+u2; p is
@@ -563,6 +564,84 @@ uint32_t pf_ilog2_q16(uint32_t x);
 /* The two weights of a site with the counts m1, u1, m2, u2 (host; the kernels
  * compute the same): w[0] = wM, w[1] = wU. */
 void pf_assign_site_weights(uint32_t m1, uint32_t u1, uint32_t m2, uint32_t u2, int32_t w[2]);
+
+/* Leave-one-out check of read tags (pf_tagcheck.hip; no reference counterpart):
+ * how far pf_batch_assign's rule can be trusted on this sample.  Every read
+ * that carries a tag is scored against its window's model with the read's own
+ * entries taken out, under exactly pf_batch_assign's rule: the share of reads
+ * that get their own tag back is the accuracy estimate for an assigned tag at
+ * the chosen thresholds, and a read that gets the other tag is a mis-tag or
+ * switch-error candidate.  Scoring a tagged read against the model it helped to
+ * build would be circular: where the haplotypes do not differ at all it still
+ * agrees with itself.  All in integers; L is pf_ilog2_q16.  Out of scope:
+ * removing all of a read's duplicate entries at a site (below); rewriting tags
+ * or a BAM; merging a read's verdicts across regions; choosing thresholds;
+ * more than one device.
+ *   model        per window [ws, we) and position p the pileup's m1, u1, m2, u2
+ *                under the call's tags, as in pf_batch_assign;
+ *   scored reads the window's reads tagged exactly 0 or 1; h is the read's tag;
+ *   leave one out  each entry of a scored read (position p, ws <= p < we,
+ *                category c: 0 meth, 1 unmeth) is scored against the counts
+ *                with that one entry removed: m_h or u_h at p is one less,
+ *                giving m1', u1', m2', u2' and n1', n2'; the other haplotype's
+ *                counts are untouched.  A duplicate entry of one read at one
+ *                position removes one entry each time, not all of them: the
+ *                read's other entry at p stays in the model.  That keeps the
+ *                weight a function of (site, tag, category);
+ *   usable       the entry is usable iff n1' >= min_cov && n2' >= min_cov;
+ *   weight       of a usable meth entry L(m1'+1) - L(n1'+2) - L(m2'+1) + L(n2'+2),
+ *                of an unmeth one the same in u.  Per site that is four weights,
+ *                  tag 0: wM0 = L(m1) - L(n1+1) - L(m2+1) + L(n2+2),
+ *                         wU0 = L(u1) - L(n1+1) - L(u2+1) + L(n2+2),
+ *                  tag 1: wM1 = L(m1+1) - L(n1+2) - L(m2) + L(n2+1),
+ *                         wU1 = L(u1+1) - L(n1+2) - L(u2) + L(n2+1),
+ *                and two flags: tag 0 usable iff n1 - 1 >= min_cov && n2 >= min_cov
+ *                (n1 >= 1), tag 1 iff n2 - 1 >= min_cov && n1 >= min_cov (n2 >= 1).
+ *                L(0) is never evaluated: an in-range entry of category c on a
+ *                read tagged h is itself counted, so that count is >= 1; where
+ *                it is 0 no read can look the weight up and 0 stands for it.
+ *                Arguments stay inside 1 .. 131,072 and |w| < 2^22;
+ *   score        S (int64) the sum over the read's usable entries, n_used their
+ *                number (cat 2 counts nowhere); positive favours tag 0;
+ *   decision     d is pf_batch_assign's on (S, n_used) with min_calls and
+ *                min_llr_q16: 0, 1 or none;
+ *   verdict      0 ok: d == h; 1 flip: d == 1 - h; 2 undecided: n_used >= 1 and
+ *                no decision; 255 not scored: tag not 0 / 1, or n_used == 0. */
+#define PF_TAGCHECK_OK 0
+#define PF_TAGCHECK_FLIP 1
+#define PF_TAGCHECK_UNDECIDED 2
+#define PF_TAGCHECK_NOT_SCORED 255
+typedef struct pf_tagcheck {
+    uint32_t n_windows;
+    uint32_t n_reads;
+    const uint32_t *win_read_off;  /* [n_windows+1] the batch's reads per window        */
+    const uint32_t *n_used;    /* [n_reads] 0 for reads that are not scored          */
+    const int64_t  *llr;       /* [n_reads] S, Q16; 0 for reads that are not scored  */
+    const uint8_t  *verdict;   /* [n_reads] PF_TAGCHECK_*                            */
+    const uint8_t  *hp;        /* [n_reads] the tags the call ran under: the batch's
+                                  or read_hp (the writer's hp column)                */
+    const uint32_t *win_n;     /* [n_windows*8] for tag 0, then tag 1: the window's
+                                  reads with that tag, those with n_used >= 1, ok,
+                                  flip                                               */
+    float ms_kernels;          /* event-timed: the tag-check kernels only (the site
+                                  table's pileup kernels are not part of it)         */
+} pf_tagcheck_t;
+/* Batches, tags, errors and ownership as in pf_batch_assign (read_hp NULL: the
+ * batch's own tags; n_hp other than the batch's reads: PF_ERR_ARG; a count past
+ * 65,535 in the pileup: PF_ERR_LIMIT; pf_tagcheck_free).  The result depends on
+ * neither the tile, the workgroup size nor atomic order.  PF_TAGCHECK_TILE=<n>
+ * in the environment (tests) sets the sites per LDS tile, a power of two in
+ * [64, 2048]; the default is 2,048; any other value returns PF_ERR_ARG. */
+int  pf_batch_tagcheck(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, const pf_assign_cfg_t *cfg,
+                       pf_tagcheck_t **out);
+void pf_tagcheck_free(pf_tagcheck_t *t);
+/* The four weights of a site with the counts m1, u1, m2, u2 (host; the kernels
+ * compute the same): w = wM0, wU0, wM1, wU1, usable[h] the flag of tag h; the
+ * weights of a tag that is not usable, and of a category whose count is 0, are
+ * 0.  A count above 65,535 is no pileup count and is taken as 65,535, as
+ * pf_assign_site_weights does, so that L's arguments stay in range. */
+void pf_tagcheck_site_weights(uint32_t m1, uint32_t u1, uint32_t m2, uint32_t u2, uint32_t min_cov, int32_t w[4],
+                              uint8_t usable[2]);
 
 /* -u pre-pass: hp_out[r] in {0, 1, 254} for every read of one contig. */
 int  pf_haptag_reads(pf_ctx_t *ctx, const pf_known_vars_t *known,
@@ -1346,6 +1425,58 @@ typedef struct pf_hapmeth_assign_stats {
 int  pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
                            const pf_hapmeth_assign_t *assign, pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst,
                            pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast);
+
+/* hapmeth --dmr --tag-check: the scored tagged reads of a pf_batch_tagcheck
+ * result as lines of {out_prefix}.hapmeth.tagcheck.tsv, tab-separated (host
+ * only):
+ *   qname chrom start end hp n_calls llr verdict
+ * one line per (window, read of it tagged 0 / 1 with n_used >= 1), windows in
+ * order and the batch's read order inside a window; hp "1" / "2" the read's own
+ * tag (t->hp), n_calls its n_used, llr = S / 65536.0 as %.4f, verdict "ok",
+ * "flip" or "." (undecided).  The other arguments as in pf_write_assign. */
+int  pf_write_tagcheck(const char *path, const char *chrom, const pf_tagcheck_t *t, const uint32_t *win_start,
+                       const uint32_t *win_end, const uint32_t *rec_of_read, const uint64_t *qname_off, const char *qname,
+                       int header, uint64_t *n_lines);
+/* ... and its windows' counters as lines of
+ * {out_prefix}.hapmeth.tagcheck.regions.tsv:
+ *   chrom start end reads_h1 scored_h1 ok_h1 flip_h1 reads_h2 scored_h2 ok_h2 flip_h2
+ * one line per window, t->win_n's eight numbers, also where nothing was scored. */
+int  pf_write_tagcheck_regions(const char *path, const char *chrom, const pf_tagcheck_t *t, const uint32_t *win_start,
+                               const uint32_t *win_end, int header, uint64_t *n_lines);
+
+#define PF_HAPMETH_TAGCHECK_RULE_ONLY 1u   /* assign names the rule to check; --assign itself is off */
+typedef struct pf_hapmeth_tagcheck {
+    uint32_t flags;            /* 0 or PF_HAPMETH_TAGCHECK_RULE_ONLY                       */
+    uint32_t reserved;
+} pf_hapmeth_tagcheck_t;
+
+typedef struct pf_hapmeth_tagcheck_stats {
+    uint64_t n_lines;          /* lines written to {out_prefix}.hapmeth.tagcheck.tsv       */
+    uint64_t n_regions;        /* lines written to ...tagcheck.regions.tsv                 */
+    uint64_t n_ok[2];          /* of n_lines, per tag 0 / 1: ok,                           */
+    uint64_t n_flip[2];        /* flip                                                     */
+    uint64_t n_undecided[2];   /* and undecided                                            */
+    uint64_t n_records;        /* records fetched by the second pass                       */
+    double ms_kernels;         /* summed pf_tagcheck_t.ms_kernels                          */
+} pf_hapmeth_tagcheck_stats_t;
+
+/* pf_hapmeth_run_assign, and with tagcheck != NULL the two tag-check files: the
+ * same second pass (the regions that pass dmr->max_p, each job fetched once)
+ * also runs pf_batch_tagcheck on the batch, under the records' HP tags, with
+ * min_cov = dmr->cfg.min_cov and the thresholds of assign -- the rule being
+ * checked -- or, where assign is NULL, 3 bits (196,608) and 2 calls; with
+ * tagcheck alone the pass still runs.  PF_HAPMETH_TAGCHECK_RULE_ONLY in
+ * tagcheck->flags: assign gives the thresholds and nothing else, no assign
+ * file is written and ast stays zero (`--tag-check --assign-min-llr 2`).  The
+ * concordance of the run is ok / (ok + flip) over both tags; the verbose line
+ * prints "n/a" for it where both are 0.  No file of the other features changes with
+ * tagcheck.  tagcheck == NULL: exactly pf_hapmeth_run_assign (tst is zeroed).
+ * tagcheck without dmr returns PF_ERR_ARG.  On failure every file is unlinked.
+ * Every stats pointer may be NULL. */
+int  pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
+                             const pf_hapmeth_assign_t *assign, const pf_hapmeth_tagcheck_t *tagcheck,
+                             pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst, pf_hapmeth_perm_stats_t *pst,
+                             pf_hapmeth_assign_stats_t *ast, pf_hapmeth_tagcheck_stats_t *tst);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

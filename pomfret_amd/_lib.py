@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from .abi import (DMR_RUN_DTYPE, AlnBatch, AssignConfig, PfAssign, PfAssignCfg, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
-                  PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfReadAlnBatch, PfWindowBatch, PfWindowOut, ReadAlnBatch,
+                  PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfReadAlnBatch, PfTagcheck, PfWindowBatch, PfWindowOut, ReadAlnBatch,
                   WindowBatch, WindowResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -106,6 +106,15 @@ def lib():
         L.pf_assign_site_weights.restype = None
         L.pf_write_assign.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfAssign), C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
+        L.pf_batch_tagcheck.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PfAssignCfg),
+                                        C.POINTER(C.POINTER(PfTagcheck))]
+        L.pf_tagcheck_free.argtypes = [C.POINTER(PfTagcheck)]
+        L.pf_tagcheck_site_weights.argtypes = [C.c_uint32] * 5 + [C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]
+        L.pf_tagcheck_site_weights.restype = None
+        L.pf_write_tagcheck.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfTagcheck), C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]
+        L.pf_write_tagcheck_regions.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfTagcheck), C.c_void_p, C.c_void_p,
+                                                C.c_int, C.POINTER(C.c_uint64)]
         if hasattr(L, "pf_haptag_reads"):
             L.pf_haptag_reads.argtypes = [C.c_void_p, C.POINTER(PfKnownVars),
                                           C.POINTER(PfReadAlnBatch), C.c_void_p]
@@ -657,6 +666,36 @@ class DeviceBatch:
                         win_n=arr(r.win_n, 3 * W, np.uint32).reshape(W, 3), ms=float(r.ms_kernels))
         finally:
             lib().pf_assign_free(p)
+
+    def tagcheck(self, cfg: AssignConfig = None, read_hp=None) -> dict:
+        """Leave-one-out check of the batch's tagged reads under cfg, the rule
+        assign applies (pf_batch_tagcheck; include/pomfret_amd.h has the
+        definition): dict(win_read_off [W+1], n_used [R] the read's usable
+        entries, llr [R] the score S in Q16 bits (int64; positive: haplotype
+        1), verdict [R] 0 ok / 1 flip / 2 undecided / 255 not scored, hp [R]
+        the tags the call ran under, win_n [W, 2, 4] per tag the window's
+        reads, those with n_used >= 1, ok, flip, ms the tag-check kernels'
+        time).  read_hp as in pileup."""
+        hp_ptr, n_hp = None, 0
+        if read_hp is not None:
+            hp = np.zeros(np.size(read_hp) + 1, np.uint8)
+            hp[:-1] = np.asarray(read_hp, np.uint8).ravel()
+            hp_ptr, n_hp = hp.ctypes.data, hp.size - 1
+        c = (cfg or AssignConfig()).to_c()
+        p = C.POINTER(PfTagcheck)()
+        _check(lib().pf_batch_tagcheck(self.ctx.handle, self.handle, hp_ptr, n_hp, C.byref(c), C.byref(p)),
+               "pf_batch_tagcheck")
+        try:
+            r = p.contents
+            W, R = int(r.n_windows), int(r.n_reads)
+
+            def arr(ptr, n, dt):
+                return np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dt)
+            return dict(win_read_off=arr(r.win_read_off, W + 1, np.uint32), n_used=arr(r.n_used, R, np.uint32),
+                        llr=arr(r.llr, R, np.int64), verdict=arr(r.verdict, R, np.uint8), hp=arr(r.hp, R, np.uint8),
+                        win_n=arr(r.win_n, 8 * W, np.uint32).reshape(W, 2, 4), ms=float(r.ms_kernels))
+        finally:
+            lib().pf_tagcheck_free(p)
 
     def stats(self) -> np.ndarray:
         """Per-(window, dir) counters of the last run: [W, 2, 8] (see pf_batch_stats)."""

@@ -470,6 +470,28 @@ class PfHapmethAssignStats(C.Structure):
                 ("ms_kernels", C.c_double)]
 
 
+class PfTagcheck(C.Structure):
+    """pf_tagcheck_t: the leave-one-out scores and verdicts of a batch's tagged reads (pf_batch_tagcheck)."""
+    _fields_ = [("n_windows", C.c_uint32), ("n_reads", C.c_uint32), ("win_read_off", C.POINTER(C.c_uint32)),
+                ("n_used", C.POINTER(C.c_uint32)), ("llr", C.POINTER(C.c_int64)), ("verdict", C.POINTER(C.c_uint8)),
+                ("hp", C.POINTER(C.c_uint8)), ("win_n", C.POINTER(C.c_uint32)), ("ms_kernels", C.c_float)]
+
+
+TAGCHECK_OK, TAGCHECK_FLIP, TAGCHECK_UNDECIDED, TAGCHECK_NOT_SCORED = 0, 1, 2, 255
+HAPMETH_TAGCHECK_RULE_ONLY = 1
+
+
+class PfHapmethTagcheck(C.Structure):
+    """pf_hapmeth_tagcheck_t (pf_hapmeth_run_tagcheck)."""
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PfHapmethTagcheckStats(C.Structure):
+    """pf_hapmeth_tagcheck_stats_t."""
+    _fields_ = [("n_lines", C.c_uint64), ("n_regions", C.c_uint64), ("n_ok", C.c_uint64 * 2), ("n_flip", C.c_uint64 * 2),
+                ("n_undecided", C.c_uint64 * 2), ("n_records", C.c_uint64), ("ms_kernels", C.c_double)]
+
+
 class PfAlnBatch(C.Structure):
     _fields_ = [("n_windows", C.c_uint32), ("n_recs", C.c_uint32)] + [
         (n, C.c_void_p) for n in (

@@ -33,6 +33,7 @@
 #include <string.h>
 #include <vector>
 #include "pf_device.h"
+#include "pf_llr.h"                 // ilog2_q16, site_weights: shared with pf_tagcheck.hip
 #include "../../include/pomfret_amd.h"
 
 struct pf_ctx;
@@ -44,7 +45,7 @@ extern "C" void pf_pile_dev_free(pf_pile_dev *dev);
 
 namespace {
 
-#define ASSIGN_NONE INT32_MIN       /* first weight of a site that is not informative */
+#define ASSIGN_NONE PF_LLR_NONE     /* first weight of a site that is not informative */
 
 struct assign_args {
     uint32_t W, T, min_cov, min_calls;
@@ -64,29 +65,6 @@ struct assign_args {
     uint8_t *hp;                                     /* [R] */
     uint32_t *win_n;                                 /* [W*3] */
 };
-
-// L(x) of the header, x >= 1
-__host__ __device__ inline uint32_t ilog2_q16(uint32_t x) {
-#ifdef __HIP_DEVICE_COMPILE__
-    const uint32_t e = 31u - (uint32_t)__clz((int)x);
-#else
-    const uint32_t e = 31u - (uint32_t)__builtin_clz(x);
-#endif
-    uint64_t y = (uint64_t)x << (31u - e);           // [2^31, 2^32)
-    uint32_t f = 0;
-    for (int i = 0; i < 16; i++) {
-        y = (y * y) >> 31;                           // [2^31, 2^33)
-        f <<= 1;
-        if (y >= 0x100000000ull) { y >>= 1; f |= 1u; }
-    }
-    return (e << 16) | f;
-}
-
-__host__ __device__ inline void site_weights(uint32_t m1, uint32_t u1, uint32_t m2, uint32_t u2, int32_t *wm, int32_t *wu) {
-    const int32_t d = (int32_t)ilog2_q16(m2 + u2 + 2u) - (int32_t)ilog2_q16(m1 + u1 + 2u);
-    *wm = (int32_t)ilog2_q16(m1 + 1u) - (int32_t)ilog2_q16(m2 + 1u) + d;
-    *wu = (int32_t)ilog2_q16(u1 + 1u) - (int32_t)ilog2_q16(u2 + 1u) + d;
-}
 
 }  // namespace
 

@@ -10,7 +10,7 @@
  *   pomfret-amd hapmeth   -o out [-r chrom[:beg-end]] [--chunk-size N] [-q mapq] [-L minlen] [--host-fetch]
  *                         [--dmr [--dmr-min-cov N] [--dmr-delta PCT] [--dmr-gap N] [--dmr-min-sites N] [--dmr-max-p P]
  *                         [--dmr-blocks blocks.gtf] [--dmr-perm N [--dmr-seed S]]
- *                         [--assign [--assign-min-llr BITS] [--assign-min-calls N]]] tagged.bam
+ *                         [--assign] [--tag-check] [--assign-min-llr BITS] [--assign-min-calls N]] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
  * cliopt_haptag_t (cli.c:332-343); the -c arithmetic (cov/10, cov/4), the
@@ -96,7 +96,7 @@ static void help_methphase(const char *prefix) {
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
        O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
        O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED,
-       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS };
+       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -117,7 +117,7 @@ static const struct option longopts[] = {
     {"dmr-blocks", required_argument, 0, O_DMR_BLOCKS},
     {"dmr-perm", required_argument, 0, O_DMR_PERM}, {"dmr-seed", required_argument, 0, O_DMR_SEED},
     {"assign", no_argument, 0, O_ASSIGN},        {"assign-min-llr", required_argument, 0, O_ASSIGN_LLR},
-    {"assign-min-calls", required_argument, 0, O_ASSIGN_CALLS},
+    {"assign-min-calls", required_argument, 0, O_ASSIGN_CALLS}, {"tag-check", no_argument, 0, O_TAGCHECK},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -325,6 +325,14 @@ static void help_hapmeth(void) {
     fprintf(stderr, "  --assign-min-llr BITS [opt] Least |llr| for a tag, a decimal in (0, 64].  The default asks for\n"
                     "               odds of 8:1; it is a choice, not a measured optimum. [3]\n");
     fprintf(stderr, "  --assign-min-calls N [opt] Least n_calls for a tag, 1 .. 65535; a choice as well. [2]\n");
+    fprintf(stderr, "  --tag-check [opt] Needs --dmr.  How far an --assign tag can be trusted on this sample: every tagged read\n"
+                    "               of a region is scored as --assign would score it, against the region's tagged reads with\n"
+                    "               its own calls taken out (leave-one-out), under --assign-min-llr / --assign-min-calls (given\n"
+                    "               with --assign or --tag-check).  Writes {out_prefix}.hapmeth.tagcheck.tsv: qname, chrom,\n"
+                    "               start, end, hp (the read's tag), n_calls, llr and verdict: ok (its own tag back), flip\n"
+                    "               (the other one: a mis-tag or switch-error candidate) or \".\" (undecided); and\n"
+                    "               {out_prefix}.hapmeth.tagcheck.regions.tsv: per region the reads, scored, ok and flip\n"
+                    "               counts of each haplotype.  -v prints the concordance ok / (ok + flip).\n");
 }
 
 /* hapmeth: one device, the jobs one after another (pf_hapmeth_main) */
@@ -342,7 +350,7 @@ static int hapmeth(int argc, char **argv) {
     pm.n_perm = 0; pm.seed = 1;
     pf_hapmeth_assign_t am;
     memset(&am, 0, sizeof am);
-    int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0;
+    int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0, tagcheck = 0;
     long dcov = 5, ddelta = 40, dgap = 500, dsites = 5, dperm = 0, dseed = 1, acalls = 2;
     double allr = 3.0;
     char *end;
@@ -373,6 +381,7 @@ static int hapmeth(int argc, char **argv) {
         case O_DMR_PERM: dmr_opt = 1; dperm = strtol(optarg, &end, 10); if (*end || !*optarg) dperm = -1; break;
         case O_DMR_SEED: dmr_opt = 1; dseed = strtol(optarg, &end, 10); if (*end || !*optarg) dseed = -1; break;
         case O_ASSIGN: assign = 1; break;
+        case O_TAGCHECK: tagcheck = 1; break;
         case O_ASSIGN_LLR: assign_opt = 1; allr = strtod(optarg, &end); if (*end || !*optarg) allr = -1.0; break;
         case O_ASSIGN_CALLS: assign_opt = 1; acalls = strtol(optarg, &end, 10); if (*end || !*optarg) acalls = -1; break;
         default:
@@ -397,8 +406,12 @@ static int hapmeth(int argc, char **argv) {
     if (!(dm.max_p >= 0.0 && dm.max_p <= 1.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-max-p (0 .. 1)\n"); return 1; }
     if (dperm < 0 || dperm > 1000000) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-perm (0 .. 1000000)\n"); return 1; }
     if (dseed < 0 || dseed > 0xFFFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-seed (0 .. 4294967295)\n"); return 1; }
-    if (assign_opt && !assign) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign-* options need --assign\n"); return 1; }
+    if (assign_opt && !assign && !tagcheck) {
+        fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign-* options need --assign or --tag-check\n");
+        return 1;
+    }
     if (assign && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign needs --dmr\n"); return 1; }
+    if (tagcheck && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --tag-check needs --dmr\n"); return 1; }
     if (!(allr > 0.0 && allr <= 64.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --assign-min-llr (above 0, at most 64)\n"); return 1; }
     if (acalls < 1 || acalls > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --assign-min-calls (1 .. 65535)\n"); return 1; }
     am.min_llr_q16 = (int64_t)llround(allr * 65536.0); am.min_calls = (uint32_t)acalls;
@@ -415,8 +428,13 @@ static int hapmeth(int argc, char **argv) {
     pf_hapmeth_dmr_stats_t dst;
     pf_hapmeth_perm_stats_t pst;
     pf_hapmeth_assign_stats_t ast;
-    const int rc = pf_hapmeth_run_assign(&op, dmr ? &dm : NULL, pm.n_perm ? &pm : NULL, assign ? &am : NULL, &st, &dst, &pst,
-                                         &ast);
+    pf_hapmeth_tagcheck_t tm;
+    memset(&tm, 0, sizeof tm);
+    if (!assign) tm.flags = PF_HAPMETH_TAGCHECK_RULE_ONLY;
+    pf_hapmeth_tagcheck_stats_t tst;
+    /* --tag-check checks the rule the two --assign-* options set, with --assign or without */
+    const int rc = pf_hapmeth_run_tagcheck(&op, dmr ? &dm : NULL, pm.n_perm ? &pm : NULL, assign || tagcheck ? &am : NULL,
+                                           tagcheck ? &tm : NULL, &st, &dst, &pst, &ast, &tst);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;
@@ -430,6 +448,10 @@ static int hapmeth(int argc, char **argv) {
     if (assign)
         fprintf(stderr, "[M::main] %llu scored reads written to %s.hapmeth.assign.tsv, %llu of them with a tag\n",
                 (unsigned long long)ast.n_lines, op.out_prefix, (unsigned long long)(ast.n_h1 + ast.n_h2));
+    if (tagcheck)
+        fprintf(stderr, "[M::main] %llu tagged reads checked in %s.hapmeth.tagcheck.tsv, %llu regions in "
+                "%s.hapmeth.tagcheck.regions.tsv\n", (unsigned long long)tst.n_lines, op.out_prefix,
+                (unsigned long long)tst.n_regions, op.out_prefix);
     return 0;
 }
 

@@ -57,6 +57,11 @@
 #define PF_ASSIGN_THREADS 256       /* its workgroup: each wave takes 64 of the window's reads at a time (1,024 measured:
                                       profiles/assign/README.md) */
 #define PF_ASSIGN_WAVES (PF_ASSIGN_THREADS / PF_WAVE)
+#define PF_TAGCHECK_TILE 2048       /* sites per LDS tile of pf_tagcheck_score: position and four weights, 20 B each, 40 KB
+                                      (PF_TAGCHECK_TILE=<n> overrides it downwards; 4,096 would be 80 KB) */
+#define PF_TAGCHECK_THREADS 256     /* its workgroup: 256 of the window's reads at a time, one per lane, their hits dealt
+                                      to the four waves */
+#define PF_TAGCHECK_WAVES (PF_TAGCHECK_THREADS / PF_WAVE)
 #define PF_NONE 0xFFFFFFFFu
 
 /* status bits */

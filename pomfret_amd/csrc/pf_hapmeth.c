@@ -31,7 +31,13 @@
  *   pf_hapmeth_run_assign: pf_hapmeth_run_perm, and with --assign the same
  *                     second pass (each job fetched once, for the test and the
  *                     assignment alike) scores every region's untagged reads
- *                     against the region's tagged ones (pf_batch_assign).
+ *                     against the region's tagged ones (pf_batch_assign);
+ *   pf_write_tagcheck, pf_write_tagcheck_regions: a pf_batch_tagcheck result as
+ *                     lines of {prefix}.hapmeth.tagcheck.tsv and
+ *                     {prefix}.hapmeth.tagcheck.regions.tsv (host only);
+ *   pf_hapmeth_run_tagcheck: pf_hapmeth_run_assign, and with --tag-check the
+ *                     same second pass, on the same fetched batch, scores every
+ *                     region's tagged reads leave-one-out (pf_batch_tagcheck).
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -262,6 +268,54 @@ int pf_write_assign(const char *path, const char *chrom, const pf_assign_t *a, c
     return PF_OK;
 }
 
+int pf_write_tagcheck(const char *path, const char *chrom, const pf_tagcheck_t *t, const uint32_t *win_start,
+                      const uint32_t *win_end, const uint32_t *rec_of_read, const uint64_t *qname_off, const char *qname,
+                      int header, uint64_t *n_lines) {
+    if (n_lines) *n_lines = 0;
+    const uint32_t W = t ? t->n_windows : 0;
+    if (!path) return PF_ERR_ARG;
+    if (W && (!chrom || !win_start || !win_end || !t->win_read_off || t->win_read_off[W] > t->n_reads)) return PF_ERR_ARG;
+    if (W && t->win_read_off[W] && (!t->n_used || !t->llr || !t->verdict || !t->hp || !qname_off || !qname)) return PF_ERR_ARG;
+    for (uint32_t w = 0; w < W; w++)
+        if (t->win_read_off[w] > t->win_read_off[w + 1]) return PF_ERR_ARG;
+    FILE *fp = fopen(path, header ? "w" : "a");
+    if (!fp) return -1;
+    if (header) fprintf(fp, "#qname\tchrom\tstart\tend\thp\tn_calls\tllr\tverdict\n");
+    for (uint32_t w = 0; w < W; w++)
+        for (uint32_t r = t->win_read_off[w]; r < t->win_read_off[w + 1]; r++) {
+            if (t->hp[r] > 1u || t->n_used[r] < 1u) continue;
+            const uint32_t rec = rec_of_read ? rec_of_read[r] : r;
+            const uint8_t v = t->verdict[r];
+            fprintf(fp, "%.*s\t%s\t%u\t%u\t%s\t%u\t%.4f\t%s\n", (int)(qname_off[rec + 1] - qname_off[rec]),
+                    qname + qname_off[rec], chrom, win_start[w], win_end[w], t->hp[r] == 0 ? "1" : "2", t->n_used[r],
+                    (double)t->llr[r] / 65536.0, v == PF_TAGCHECK_OK ? "ok" : v == PF_TAGCHECK_FLIP ? "flip" : ".");
+            if (n_lines) ++*n_lines;
+        }
+    const int bad = ferror(fp);
+    if (fclose(fp) != 0 || bad) return -1;
+    return PF_OK;
+}
+
+int pf_write_tagcheck_regions(const char *path, const char *chrom, const pf_tagcheck_t *t, const uint32_t *win_start,
+                              const uint32_t *win_end, int header, uint64_t *n_lines) {
+    if (n_lines) *n_lines = 0;
+    const uint32_t W = t ? t->n_windows : 0;
+    if (!path || (W && (!chrom || !win_start || !win_end || !t->win_n))) return PF_ERR_ARG;
+    FILE *fp = fopen(path, header ? "w" : "a");
+    if (!fp) return -1;
+    if (header)
+        fprintf(fp, "#chrom\tstart\tend\treads_h1\tscored_h1\tok_h1\tflip_h1\treads_h2\tscored_h2\tok_h2\tflip_h2\n");
+    for (uint32_t w = 0; w < W; w++) {
+        const uint32_t *n = t->win_n + 8ull * w;
+        fprintf(fp, "%s\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\n", chrom, win_start[w], win_end[w], n[0], n[1], n[2], n[3],
+                n[4], n[5], n[6], n[7]);
+        if (n_lines) ++*n_lines;
+    }
+    const int bad = ferror(fp);
+    if (fclose(fp) != 0 || bad) return -1;
+    return PF_OK;
+}
+
 /* "chrom" or "chrom:beg-end" / "chrom:beg" (1-based inclusive, commas allowed)
  * -> tid and the 0-based [*s, *e); a name that holds ':' itself is tried whole
  * first */
@@ -320,6 +374,11 @@ typedef struct {
     const pf_hapmeth_assign_t *assign;
     char *apath;
     pf_hapmeth_assign_stats_t ast;
+    /* --tag-check */
+    const pf_hapmeth_tagcheck_t *tagcheck;
+    const pf_hapmeth_assign_t *rule;   /* the thresholds it checks; NULL: the defaults */
+    char *tpath, *trpath;
+    pf_hapmeth_tagcheck_stats_t tst;
 } hm_t;
 
 /* the fetch of one job, the same in both passes: the records of the windows
@@ -399,7 +458,9 @@ static int hm_breaks(hm_t *H, const char *chrom) {
     return PF_OK;
 }
 
-/* the second pass over a contig's final regions, for --dmr-perm and --assign:
+/* the second pass over a contig's final regions, for --dmr-perm, --assign and
+ * --tag-check (pf_batch_tagcheck on the same batch, its lines appended to the
+ * two tag-check files job by job):
  * the regions that pass max_p are the windows [start, end) of jobs of at most
  * jw windows, each fetched once as in the first pass; on that batch, under the
  * records' HP tags, pf_batch_permtest (run k's result lands in window k of
@@ -442,10 +503,12 @@ static int hm_second(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t 
         pf_bam_records_t *recs = NULL;
         pf_perm_t *part = NULL;
         pf_assign_t *as = NULL;
+        pf_tagcheck_t *tc = NULL;
         uint64_t fetched = 0;
         rc = hm_fetch(H, chrom, k, ws, we, &db, &F, &recs, &fetched);
         if (H->perm) H->pst.n_records += fetched;
         if (H->assign) H->ast.n_records += fetched;
+        if (H->tagcheck) H->tst.n_records += fetched;
         if (rc == PF_ERR_LIMIT)
             fprintf(stderr, "[E::pf_hapmeth_main] %s:%u-%u: a region exceeds a device limit (65,535 records per window)\n",
                     chrom, ws[0] + 1, we[k - 1]);
@@ -485,6 +548,39 @@ static int hm_second(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t 
             }
             free(rec_of);
         }
+        if (!rc && H->tagcheck) {
+            /* the rule being checked: --assign's thresholds, or its defaults */
+            pf_assign_cfg_t ac;
+            ac.min_cov = H->dmr->cfg.min_cov;
+            ac.min_calls = H->rule ? H->rule->min_calls : 2u;
+            ac.min_llr_q16 = H->rule ? H->rule->min_llr_q16 : 3 * 65536;
+            rc = pf_batch_tagcheck(H->ctx, db, NULL, 0, &ac, &tc);
+            if (!rc && tc->n_windows != k) rc = PF_ERR_INTERNAL;
+            uint32_t *rec_of = NULL;
+            if (!rc) {
+                rec_of = (uint32_t *)malloc(4ull * tc->n_reads + 4);
+                rc = rec_of ? pf_batch_read_recs(db, rec_of, tc->n_reads) : PF_ERR_NOMEM;
+            }
+            uint64_t lines = 0, regions = 0;
+            if (!rc)
+                rc = pf_write_tagcheck(H->tpath, chrom, tc, ws, we, rec_of, recs ? recs->qname_off : F->qname_off,
+                                       recs ? recs->qname : F->qname, 0, &lines);
+            if (!rc) rc = pf_write_tagcheck_regions(H->trpath, chrom, tc, ws, we, 0, &regions);
+            if (!rc) {
+                H->tst.n_lines += lines;
+                H->tst.n_regions += regions;
+                for (uint32_t j = 0; j < k; j++)
+                    for (int h = 0; h < 2; h++) {
+                        const uint32_t *c = tc->win_n + 8ull * j + 4 * h;
+                        H->tst.n_ok[h] += c[2];
+                        H->tst.n_flip[h] += c[3];
+                        H->tst.n_undecided[h] += c[1] - c[2] - c[3];
+                    }
+                H->tst.ms_kernels += tc->ms_kernels;
+            }
+            free(rec_of);
+        }
+        pf_tagcheck_free(tc);
         pf_assign_free(as);
         pf_perm_free(part);
         if (db) pf_batch_free(db);
@@ -505,7 +601,7 @@ static int hm_flush(hm_t *H, const char *chrom) {
     pf_perm_t *P = NULL;
     uint64_t lines = 0, dots = 0;
     int rc = pf_dmr_acc_flush(H->acc, &fin);
-    if (!rc && (H->perm || H->assign)) rc = hm_second(H, chrom, fin, &P);
+    if (!rc && (H->perm || H->assign || H->tagcheck)) rc = hm_second(H, chrom, fin, &P);
     if (!rc) rc = write_dmr(H->dpath, chrom, fin, P, H->dmr->max_p, 0, &lines, &dots);
     if (!rc) {
         H->dst.n_regions += lines;
@@ -566,6 +662,16 @@ int pf_hapmeth_run_perm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
 int pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
                           const pf_hapmeth_assign_t *assign, pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats,
                           pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats) {
+    return pf_hapmeth_run_tagcheck(o, dmr, perm, assign, NULL, stats, dstats, pstats, astats, NULL);
+}
+
+int pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_perm_t *perm,
+                            const pf_hapmeth_assign_t *assign, const pf_hapmeth_tagcheck_t *tagcheck,
+                            pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats, pf_hapmeth_perm_stats_t *pstats,
+                            pf_hapmeth_assign_stats_t *astats, pf_hapmeth_tagcheck_stats_t *tstats) {
+    if (tstats) memset(tstats, 0, sizeof *tstats);
+    const pf_hapmeth_assign_t *rule = assign;
+    if (tagcheck && (tagcheck->flags & PF_HAPMETH_TAGCHECK_RULE_ONLY)) assign = NULL;
     if (stats) memset(stats, 0, sizeof *stats);
     if (dstats) memset(dstats, 0, sizeof *dstats);
     if (pstats) memset(pstats, 0, sizeof *pstats);
@@ -574,12 +680,15 @@ int pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dm
     if (dmr && (dmr->cfg.min_delta_pct > 100u || !(dmr->max_p >= 0.0))) return PF_ERR_ARG;
     if (perm && (!dmr || perm->n_perm < 1u || perm->n_perm > PF_PERM_MAX_PERM)) return PF_ERR_ARG;
     if (assign && !dmr) return PF_ERR_ARG;
+    if (tagcheck && !dmr) return PF_ERR_ARG;
     hm_t H;
     memset(&H, 0, sizeof H);
     H.o = o;
     H.dmr = dmr;
     H.perm = perm;
     H.assign = assign;
+    H.tagcheck = tagcheck;
+    H.rule = rule;
     H.lc = o->load;
     /* the batch's phasing parameters are not used by the pileup: the reference's defaults */
     H.cfg.k = 3; H.cfg.k_span = 5000; H.cfg.cov_for_selection = 6; H.cfg.n_cand = 15; H.cfg.hard_cov = 15;
@@ -600,7 +709,7 @@ int pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dm
         tid1 = tid0 + 1;
     }
     uint32_t *ws = NULL, *we = NULL;
-    int made = 0, dmade = 0, amade = 0;
+    int made = 0, dmade = 0, amade = 0, tmade = 0, trmade = 0;
     if (!rc && dmr && dmr->blocks_path) {
         rc = pf_interval_gaps(dmr->blocks_path, PF_INTERVALS_GTF, 0, &H.blocks);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot read the phase blocks of %s\n", dmr->blocks_path);
@@ -610,17 +719,21 @@ int pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dm
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] no usable GPU (device %d): %s\n", o->device, pf_strerror(rc));
     }
     if (!rc) {
-        const size_t l = strlen(o->out_prefix) + 24;
+        const size_t l = strlen(o->out_prefix) + 40;
         H.path = (char *)malloc(l);
         H.dpath = (char *)malloc(l);
         H.apath = (char *)malloc(l);
+        H.tpath = (char *)malloc(l);
+        H.trpath = (char *)malloc(l);
         ws = (uint32_t *)malloc(4ull * jw);
         we = (uint32_t *)malloc(4ull * jw);
-        if (!H.path || !H.dpath || !H.apath || !ws || !we) rc = PF_ERR_NOMEM;
+        if (!H.path || !H.dpath || !H.apath || !H.tpath || !H.trpath || !ws || !we) rc = PF_ERR_NOMEM;
         else {
             snprintf(H.path, l, "%s.hapmeth.bed", o->out_prefix);
             snprintf(H.dpath, l, "%s.hapmeth.dmr.bed", o->out_prefix);
             snprintf(H.apath, l, "%s.hapmeth.assign.tsv", o->out_prefix);
+            snprintf(H.tpath, l, "%s.hapmeth.tagcheck.tsv", o->out_prefix);
+            snprintf(H.trpath, l, "%s.hapmeth.tagcheck.regions.tsv", o->out_prefix);
         }
     }
     if (!rc) {
@@ -640,6 +753,16 @@ int pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dm
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.apath);
         else amade = 1;
     }
+    if (!rc && tagcheck) {
+        rc = pf_write_tagcheck(H.tpath, NULL, NULL, NULL, NULL, NULL, NULL, NULL, 1, NULL);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.tpath);
+        else tmade = 1;
+    }
+    if (!rc && tagcheck) {
+        rc = pf_write_tagcheck_regions(H.trpath, NULL, NULL, NULL, NULL, 1, NULL);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.trpath);
+        else trmade = 1;
+    }
     for (int32_t t = tid0; t < tid1 && !rc; t++) {
         if (!o->region) { s = 0; e = pf_bam_target_len(H.bam, t); }
         rc = hm_span(&H, t, s, e, chunk, jw, ws, we);
@@ -647,6 +770,8 @@ int pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dm
     if (rc && made) (void)unlink(H.path);              /* no truncated output behind a failure */
     if (rc && dmade) (void)unlink(H.dpath);
     if (rc && amade) (void)unlink(H.apath);
+    if (rc && tmade) (void)unlink(H.tpath);
+    if (rc && trmade) (void)unlink(H.trpath);
     if (!rc && o->verbose)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu windows (%llu without reads in the index, skipped), %llu records, "
                 "%llu sites, pileup kernels %.3f ms\n", (unsigned long long)H.st.n_windows,
@@ -665,15 +790,29 @@ int pf_hapmeth_run_assign(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dm
                 "%llu records fetched for it, assign kernels %.3f ms\n", (unsigned long long)H.ast.n_lines,
                 (unsigned long long)(H.ast.n_h1 + H.ast.n_h2), (unsigned long long)H.ast.n_h1,
                 (unsigned long long)H.ast.n_h2, (unsigned long long)H.ast.n_records, H.ast.ms_kernels);
+    if (!rc && o->verbose && tagcheck) {
+        const uint64_t ok = H.tst.n_ok[0] + H.tst.n_ok[1], flip = H.tst.n_flip[0] + H.tst.n_flip[1];
+        char conc[16] = "n/a";                         /* no decision at all: no figure, not a measured zero */
+        if (ok + flip) snprintf(conc, sizeof conc, "%.4f", (double)ok / (double)(ok + flip));
+        fprintf(stderr, "[M::pf_hapmeth_main] tag check: %llu tagged reads scored, %llu ok (%llu h1 / %llu h2), %llu flip "
+                "(%llu h1 / %llu h2), %llu undecided, concordance %s, %llu records fetched for it, tag-check kernels %.3f ms\n",
+                (unsigned long long)H.tst.n_lines, (unsigned long long)ok, (unsigned long long)H.tst.n_ok[0],
+                (unsigned long long)H.tst.n_ok[1], (unsigned long long)flip, (unsigned long long)H.tst.n_flip[0],
+                (unsigned long long)H.tst.n_flip[1], (unsigned long long)(H.tst.n_undecided[0] + H.tst.n_undecided[1]),
+                conc, (unsigned long long)H.tst.n_records, H.tst.ms_kernels);
+    }
     if (stats) *stats = H.st;
     if (dstats) *dstats = H.dst;
     if (pstats) *pstats = H.pst;
     if (astats) *astats = H.ast;
+    if (tstats) *tstats = H.tst;
     free(ws);
     free(we);
     free(H.path);
     free(H.dpath);
     free(H.apath);
+    free(H.tpath);
+    free(H.trpath);
     free(H.brk);
     pf_dmr_acc_free(H.acc);
     pf_gaps_free(H.blocks);

@@ -34,7 +34,8 @@ import numpy as np
 from ._lib import (INTERVALS_GTF, INTERVALS_TSV, INTERVALS_VCF, PomfretError, _blocks_contigs, _check,  # noqa: F401
                    _breaks, _dmr_dict, _dmr_to_c, _gaps_contigs, _PfBlocks, _PfGaps, lib)
 from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfHapmethDmrStats, PfHapmethOpts,
-                  AssignConfig, PfAssign, PfHapmethAssign, PfHapmethAssignStats, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup)
+                  AssignConfig, HAPMETH_TAGCHECK_RULE_ONLY, PfAssign, PfHapmethAssign, PfHapmethAssignStats,
+                  PfHapmethTagcheck, PfHapmethTagcheckStats, PfTagcheck, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
 JOB_WINDOWS, JOB_HAPTAG = 0, 1
@@ -125,6 +126,11 @@ def _bind():
                                         C.POINTER(PfHapmethAssign), C.POINTER(PfHapmethStats),
                                         C.POINTER(PfHapmethDmrStats), C.POINTER(PfHapmethPermStats),
                                         C.POINTER(PfHapmethAssignStats)]
+    L.pf_hapmeth_run_tagcheck.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethPerm),
+                                          C.POINTER(PfHapmethAssign), C.POINTER(PfHapmethTagcheck),
+                                          C.POINTER(PfHapmethStats), C.POINTER(PfHapmethDmrStats),
+                                          C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
+                                          C.POINTER(PfHapmethTagcheckStats)]
     L.pf_tags_new.restype = vp
     L.pf_tags_free.argtypes = [vp]
     L.pf_tags_size.argtypes = [vp]
@@ -489,7 +495,7 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
                   lcfg: Optional[LoadConfig] = None, host_fetch: bool = False, threads: int = 1, device: int = 0,
                   job_windows: int = 0, dmr: Optional[DmrConfig] = None, dmr_max_p: float = 1.0,
                   dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1,
-                  assign: Optional[AssignConfig] = None) -> Dict:
+                  assign: Optional[AssignConfig] = None, tag_check=False) -> Dict:
     """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
@@ -515,12 +521,27 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     and untagged read with a call at one of its member CpGs (qname, chrom,
     start, end, n_calls, llr in bits, hp 1 / 2 / "."), and adds assign_path,
     n_assign_lines, n_assigned (n_assigned_h1 + n_assigned_h2), assign_records
-    and assign_ms_kernels to the dict."""
+    and assign_ms_kernels to the dict.
+    tag_check: True (`--tag-check`; needs dmr) also writes out_prefix +
+    .hapmeth.tagcheck.tsv, one line per region and tagged read of it with a
+    usable call, scored leave-one-out under assign's thresholds (AssignConfig's
+    defaults when assign is None; an AssignConfig in place of True names the
+    rule without turning assign on): qname, chrom, start, end, hp, n_calls, llr,
+    verdict ok / flip / "."; and out_prefix + .hapmeth.tagcheck.regions.tsv, one
+    line per region with the reads, scored, ok and flip counts of each
+    haplotype.  Adds tagcheck_path, tagcheck_regions_path, n_tagcheck_lines,
+    n_tagcheck_regions, tagcheck_ok / _flip / _undecided (each [h1, h2]),
+    tagcheck_concordance (ok / (ok + flip), None when both are 0),
+    tagcheck_records and tagcheck_ms_kernels to the dict."""
     L = _bind()
     if dmr_perm and dmr is None:
         raise PomfretError("hapmeth_files: dmr_perm needs dmr")
     if assign is not None and dmr is None:
         raise PomfretError("hapmeth_files: assign needs dmr")
+    if tag_check and dmr is None:
+        raise PomfretError("hapmeth_files: tag_check needs dmr")
+    if isinstance(tag_check, AssignConfig) and assign is not None:
+        raise PomfretError("hapmeth_files: with assign, tag_check checks assign's rule: pass True")
     lc = lcfg or LoadConfig(min_len=0)
     o = PfHapmethOpts(bam.encode(), out_prefix.encode(), region.encode() if region else None, int(chunk_size),
                       int(job_windows), lc.to_c(), int(threads), int(bool(host_fetch)), int(device), 0)
@@ -532,7 +553,15 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         dst = PfHapmethDmrStats()
         pm = PfHapmethPerm(int(dmr_perm), int(dmr_seed))
         pst = PfHapmethPermStats()
-        if assign is None:
+        if tag_check:
+            rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
+            am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
+            tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
+            ast, tst = PfHapmethAssignStats(), PfHapmethTagcheckStats()
+            _check(L.pf_hapmeth_run_tagcheck(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(am),
+                                             C.byref(tm), C.byref(st), C.byref(dst), C.byref(pst), C.byref(ast),
+                                             C.byref(tst)), "pf_hapmeth_run_tagcheck")
+        elif assign is None:
             _check(L.pf_hapmeth_run_perm(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(st),
                                          C.byref(dst), C.byref(pst)), "pf_hapmeth_run_perm")
         else:
@@ -553,6 +582,14 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
                        n_assigned=int(ast.n_h1 + ast.n_h2), n_assigned_h1=int(ast.n_h1), n_assigned_h2=int(ast.n_h2),
                        assign_records=int(ast.n_records),
                        assign_ms_kernels=float(ast.ms_kernels))
+        if tag_check:
+            ok, flip = [int(x) for x in tst.n_ok], [int(x) for x in tst.n_flip]
+            res.update(tagcheck_path=out_prefix + ".hapmeth.tagcheck.tsv",
+                       tagcheck_regions_path=out_prefix + ".hapmeth.tagcheck.regions.tsv",
+                       n_tagcheck_lines=int(tst.n_lines), n_tagcheck_regions=int(tst.n_regions), tagcheck_ok=ok,
+                       tagcheck_flip=flip, tagcheck_undecided=[int(x) for x in tst.n_undecided],
+                       tagcheck_concordance=sum(ok) / (sum(ok) + sum(flip)) if sum(ok) + sum(flip) else None,
+                       tagcheck_records=int(tst.n_records), tagcheck_ms_kernels=float(tst.ms_kernels))
     return res
 
 
@@ -655,6 +692,54 @@ def write_assign(path: str, chrom: str, res: Optional[Dict], win_start, win_end,
                              None if rr is None else rr.ctypes.data, qoff.ctypes.data, blob, int(bool(header)), C.byref(n)),
            "pf_write_assign")
     return int(n.value)
+
+
+def write_tagcheck(path: str, regions_path: Optional[str], chrom: str, res: Optional[Dict], win_start, win_end, qnames,
+                   rec_of_read=None, header: bool = True):
+    """The scored reads of a DeviceBatch.tagcheck dict as hapmeth --tag-check
+    lines (pf_write_tagcheck, host only): qname, chrom, the window's start and
+    end, hp 1 / 2, n_calls, llr = S / 65536 as %.4f and the verdict ok / flip /
+    "."; one line per window and tagged read of it with n_used >= 1; and, with
+    regions_path, the windows' counters (pf_write_tagcheck_regions), one line
+    per window.  qnames, rec_of_read, res None as in write_assign.  Returns
+    (read lines, region lines) written."""
+    L = _bind()
+    n, nr = C.c_uint64(0), C.c_uint64(0)
+    if res is None:
+        _check(L.pf_write_tagcheck(path.encode(), chrom.encode(), None, None, None, None, None, None, int(bool(header)),
+                                   C.byref(n)), "pf_write_tagcheck")
+        if regions_path:
+            _check(L.pf_write_tagcheck_regions(regions_path.encode(), chrom.encode(), None, None, None, int(bool(header)),
+                                               C.byref(nr)), "pf_write_tagcheck_regions")
+        return 0, 0
+    names = [q if isinstance(q, bytes) else str(q).encode() for q in qnames]
+    qoff = np.zeros(len(names) + 1, np.uint64)
+    qoff[1:] = np.cumsum([len(q) for q in names])
+    blob = b"".join(names) + b"\0"
+    wro = np.ascontiguousarray(np.append(np.asarray(res["win_read_off"], np.uint32), 0).astype(np.uint32))
+    W, R = wro.size - 2, int(np.size(res["verdict"]))
+    pad = lambda a, dt: np.ascontiguousarray(np.append(np.asarray(a, dt).ravel(), 0).astype(dt))
+    nu, llr = pad(res["n_used"], np.uint32), pad(res["llr"], np.int64)
+    vd, hp = pad(res["verdict"], np.uint8), pad(res["hp"], np.uint8)
+    wn = pad(res["win_n"], np.uint32)
+    ws, we = pad(win_start, np.uint32), pad(win_end, np.uint32)
+    if (ws.size - 1 != W or we.size - 1 != W or nu.size - 1 != R or llr.size - 1 != R or hp.size - 1 != R
+            or wn.size - 1 != 8 * W):
+        raise PomfretError("inconsistent tagcheck arrays")
+    rr = None if rec_of_read is None else pad(rec_of_read, np.uint32)
+    recs = np.arange(R) if rr is None else rr[:R]
+    if R and int(np.max(recs)) >= len(names):
+        raise PomfretError("write_tagcheck: a read's record has no qname")
+    u32p, u8p = C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+    t = PfTagcheck(W, R, wro.ctypes.data_as(u32p), nu.ctypes.data_as(u32p), llr.ctypes.data_as(C.POINTER(C.c_int64)),
+                   vd.ctypes.data_as(u8p), hp.ctypes.data_as(u8p), wn.ctypes.data_as(u32p), 0.0)
+    _check(L.pf_write_tagcheck(path.encode(), chrom.encode(), C.byref(t), ws.ctypes.data, we.ctypes.data,
+                               None if rr is None else rr.ctypes.data, qoff.ctypes.data, blob, int(bool(header)), C.byref(n)),
+           "pf_write_tagcheck")
+    if regions_path:
+        _check(L.pf_write_tagcheck_regions(regions_path.encode(), chrom.encode(), C.byref(t), ws.ctypes.data, we.ctypes.data,
+                                           int(bool(header)), C.byref(nr)), "pf_write_tagcheck_regions")
+    return int(n.value), int(nr.value)
 
 
 def write_hapmeth(path: str, chrom: str, pile: Dict, header: bool = True, w0: int = 0, w1: Optional[int] = None):

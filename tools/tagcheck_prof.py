@@ -1,0 +1,95 @@
+"""The tag-check kernels (pf_batch_tagcheck) beside the pileup kernels and the
+assign kernels of the same batch, in one process: profiles/tagcheck/README.md's
+numbers.
+
+tools/assign_prof.py's protocol and batches: record-level synth_aln at 60x
+(seed 7) of 16 and 256 windows of 50,000 bases, and (--cut N) the calls-level
+batch of about N windows of 1,000 bases cut from the largest one, the shape the
+second pass of hapmeth produces.  Per repeat the pileup (its kernels' ms), the
+assignment (its two kernels' ms) and the tag check (pf_tagcheck_weights +
+pf_tagcheck_score; the site table's pileup kernels are outside both) for each
+tile in turn.  3 warm-up repeats, 15 timed; median [min-max].
+
+usage: python tools/tagcheck_prof.py [--windows 16,256] [--tiles 2048,1024,512,64] [--cut 1000] [--min-cov 5]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from tools.dmr_perm_prof import cut_batch, stat  # noqa: E402
+
+
+def time_batch(db, name, extra, tiles, cfg, warmup, steps):
+    pile_ms, assign_ms, ker, first = [], [], {t: [] for t in tiles}, None
+    for it in range(warmup + steps):
+        pile = db.pileup()
+        asg = db.assign(cfg)
+        if it >= warmup:
+            pile_ms.append(pile["ms"])
+            assign_ms.append(asg["ms"])
+        for t in tiles:
+            os.environ["PF_TAGCHECK_TILE"] = str(t)
+            res = db.tagcheck(cfg)
+            if first is not None:                    # the result does not depend on the tile
+                assert all(np.array_equal(res[k], first[k]) for k in ("n_used", "llr", "verdict", "win_n"))
+            first = first or res
+            if it >= warmup:
+                ker[t].append(res["ms"])
+    os.environ.pop("PF_TAGCHECK_TILE", None)
+    sites = np.diff(pile["win_off"].astype(np.int64))
+    reads = np.diff(first["win_read_off"].astype(np.int64))
+    tagged = int(first["win_n"][:, :, 0].sum())
+    scored = int(first["win_n"][:, :, 1].sum())
+    a_scored = int(asg["win_n"][:, 0].sum())
+    t_med = float(np.median(ker[tiles[0]]))
+    a_med = float(np.median(assign_ms))
+    print(json.dumps(dict(batch=name, **extra, windows=int(reads.size),
+                          reads_per_window="%d [%d-%d]" % (int(np.median(reads)), int(reads.min()), int(reads.max())),
+                          sites_per_window="%d [%d-%d]" % (int(np.median(sites)), int(sites.min()), int(sites.max())),
+                          tagged=tagged, scored=scored, entries_used=int(first["n_used"].sum()),
+                          ok=int(first["win_n"][:, :, 2].sum()), flip=int(first["win_n"][:, :, 3].sum()),
+                          assign_scored=a_scored, assign_entries_used=int(asg["n_used"].sum()),
+                          pileup_ms=stat(pile_ms), assign_ms=stat(assign_ms),
+                          tagcheck_ms={"tile %d" % t: stat(v) for t, v in ker.items()},
+                          # the yardstick: kernel time per scored read, tag check over assign, first tile listed
+                          per_scored_read_ratio=round((t_med / max(scored, 1)) / (a_med / max(a_scored, 1)), 3))), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--windows", default="16,256")
+    ap.add_argument("--tiles", default="2048,1024,512,64")
+    ap.add_argument("--cut", type=int, default=1000)
+    ap.add_argument("--min-cov", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=15)
+    a = ap.parse_args()
+    from pomfret_amd import Config, Context, LoadConfig
+    from pomfret_amd.abi import AssignConfig
+    from pomfret_amd.synth_aln import AlnSpec, make_aln_batch
+    tiles = [int(x) for x in a.tiles.split(",")]
+    acfg = AssignConfig(min_cov=a.min_cov)
+    cfg = Config.from_coverage(60, given=True)
+    ctx = Context(0)
+    sizes = [int(x) for x in a.windows.split(",")]
+    for n in sizes:
+        print(f"[tagcheck_prof] {n} windows: generating", file=sys.stderr, flush=True)
+        aln = make_aln_batch(AlnSpec(n_windows=n, coverage=60, seed=7), workers=min(16, n))
+        db = ctx.upload_aln(cfg, aln, LoadConfig())
+        time_batch(db, "50 kb windows", dict(records=int(aln.n_recs)), tiles, acfg, a.warmup, a.steps)
+        if a.cut and n == max(sizes):
+            cb = cut_batch(db, aln, a.cut)
+            db.free()
+            db = ctx.upload(cfg, cb)
+            time_batch(db, "1 kb windows", dict(reads=int(cb.n_reads), calls=int(cb.call_pos.size)), tiles, acfg, a.warmup, a.steps)
+        db.free()
+    ctx.close()
+
+
+if __name__ == "__main__":
+    main()
