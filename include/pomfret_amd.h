@@ -288,6 +288,10 @@ int  pf_batch_k3_paths(pf_dbatch_t *db, uint8_t *out, uint64_t n);
  * (no calls, or the left-coverage check of blockjoin.c:1161).  n >= n_windows.
  * Tests assert which path the wide headline windows took. */
 int  pf_batch_k12_paths(pf_dbatch_t *db, uint8_t *out, uint64_t n);
+/* The items (chunks of PF_K12C_READS reads of one window) K12 handed to
+ * pf_k12_chunks in the last run; 0 when every window's methmer phase ran in
+ * K12 itself.  Tests assert that PF_K12C_MINR forced the chunk route. */
+int  pf_batch_k12_chunk_items(pf_dbatch_t *db, uint32_t *out);
 
 /* Masked reference positions (the masked_poss set of get_methmer_sites_and_ranges,
  * blockjoin.c:3202-3205, 3277-3283): a position that qualifies as a

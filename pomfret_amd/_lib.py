@@ -710,6 +710,15 @@ class DeviceBatch:
         _check(lib().pf_batch_k12_paths(self.handle, out.ctypes.data, out.size), "pf_batch_k12_paths")
         return out[:self.n_windows]
 
+    def k12_chunk_items(self) -> int:
+        """The read chunks the last run's K12 handed to pf_k12_chunks
+        (pf_batch_k12_chunk_items); 0: every methmer phase ran in K12."""
+        f = lib().pf_batch_k12_chunk_items
+        f.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)]
+        n = C.c_uint32(0)
+        _check(f(self.handle, C.byref(n)), "pf_batch_k12_chunk_items")
+        return int(n.value)
+
     def set_mask(self, pos, win_rng=None):
         """Masked reference positions (pf_batch_set_mask): a position that
         qualifies as a methylation site and is in `pos` (strictly ascending,

@@ -1816,6 +1816,14 @@ extern "C" int pf_batch_k12_paths(pf_dbatch_t *b, uint8_t *out, uint64_t n) {
     return PF_OK;
 }
 
+extern "C" int pf_batch_k12_chunk_items(pf_dbatch_t *b, uint32_t *out) {
+    if (!b || !out) return PF_ERR_ARG;
+    HIPCHK(hipSetDevice(b->ctx->device));
+    HIPCHK(hipStreamSynchronize(b->ctx->stream));
+    HIPCHK(hipMemcpy(out, b->d.k12c_ctr, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return PF_OK;
+}
+
 extern "C" int pf_batch_k3_budget(const pf_dbatch_t *b, uint32_t *out, uint64_t n) {
     if (!b || !out || n < 4) return PF_ERR_ARG;
     HIPCHK(hipSetDevice(b->ctx->device));

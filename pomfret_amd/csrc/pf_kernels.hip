@@ -360,67 +360,15 @@ DEV void wave_lb2(const uint32_t *a, uint32_t n, uint32_t kA, uint32_t kB, uint3
     lbB = rdl(lo, 32);
 }
 
-// Position -> site index hash of a window's sites (LDS), entries
-// (pos - pmin) << 13 | index; positions of hash-path windows span < 2^19.
-struct K2SiteHash {
-    const uint32_t *t;
-    uint32_t mask, pmin;
-};
-DEV uint32_t k2_hash_slot(uint32_t rel) { return (rel * 2654435761u) >> 7; }
-DEV uint32_t k2_site_of(const K2SiteHash &hs, uint32_t p) {
-    const uint32_t rel = p - hs.pmin;
-    if (p < hs.pmin || rel >= (1u << 19)) return PF_NONE;
-    uint32_t h = k2_hash_slot(rel) & hs.mask;
-    for (;;) {
-        const uint32_t e = hs.t[h];
-        if (e == PF_NONE) return PF_NONE;
-        if ((e >> 13) == rel) return e & 8191u;
-        h = (h + 1) & hs.mask;
-    }
-}
-
 // Per-read scalars of the methmer walk.
 struct K2Read {
     uint64_t c0, c1;
     uint32_t F, L, cap, maxcall;
 };
 
-// Calls of one read held in registers (reads of up to 64*K2_CR calls): the
-// position and, for the first call at a position, its category (3 = none).
+// Reads of up to 64*K2_CR calls are loaded into registers, K2_CR per lane
+// (k2_issue_calls), and staged in the wave's LDS buffer (k2_stage_calls).
 #define K2_CR 8
-struct K2Calls {
-    uint32_t pos[K2_CR], cat[K2_CR], site[K2_CR];
-};
-
-// site index of each first call (PF_NONE if its position is not a site), once
-// per read for both directions: hash lookup, or lower bound over all sites
-// (the hash is passed by value: a pointer to a local struct would put it on
-// the scratch stack, and every reload's vmcnt wait would drain the next
-// read's prefetched calls)
-DEV void k2_calls_sites(K2Calls &cl, uint32_t nc, const uint32_t *sp, uint32_t S, const K2SiteHash hs,
-                        bool use_hash) {
-    // the sites' range once per read; slots beyond the read's nc calls hold
-    // no call (nc is wave-uniform: a scalar branch)
-    const uint32_t sfirst = S ? sp[0] : 1u, slast = S ? sp[S - 1] : 0u;
-#pragma unroll
-    for (int u = 0; u < K2_CR; u++) {
-        const uint32_t p = cl.pos[u];
-        uint32_t si = PF_NONE;
-        if (64u * u >= nc) { cl.site[u] = si; continue; }
-        if (cl.cat[u] < 3u && p >= sfirst && p <= slast) {
-            if (use_hash) si = k2_site_of(hs, p);
-            else {
-                uint32_t lo = 0, hi = S;
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (sp[mid] < p) lo = mid + 1; else hi = mid;
-                }
-                si = sp[lo] == p ? lo : PF_NONE;
-            }
-        }
-        cl.site[u] = si;
-    }
-}
 
 DEV void k2_load_scalars(const pf_dev_batch &d, uint32_t r, K2Read &rd) {
     rd.c0 = d.read_call_off[r];
@@ -443,33 +391,46 @@ DEV void k2_issue_calls(const pf_dev_batch &d, const K2Read &rd, uint32_t lane, 
     }
 }
 
-// first-call flags: the previous call's position comes from the lane below
-// (DPP wave_shr:1) or, for lane 0, from lane 63 of the previous round
-DEV void k2_finish_calls(uint64_t c0, uint64_t c1, uint32_t lane, const uint32_t *pos, const uint32_t *cat,
-                         K2Calls &cl) {
-    uint32_t last = 0xFFFFFFFFu;
+// The calls of a read, from the registers k2_issue_calls filled, into cv in
+// call order, one word (pos << 2) | cat per call.  A read's calls are sorted by
+// (pos, cat) and positions are below 2^29 (pf_batch_upload and K0's emission
+// check it), so the words ascend and the first call at a position, the one
+// whose category counts, is the lower bound of pos << 2.  nc is wave-uniform.
+DEV void k2_stage_calls(const uint32_t *pos, const uint32_t *cat, uint32_t nc, uint32_t lane, uint32_t *cv) {
 #pragma unroll
-    for (int u = 0; u < K2_CR; u++) {
-        const uint64_t c = c0 + lane + 64u * u;
-        uint32_t prv = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)pos[u], 0x138, 0xF, 0xF, false);  // wave_shr:1
-        if (lane == 0) prv = last;
-        last = rdl(pos[u], 63);
-        cl.pos[u] = pos[u];
-        cl.cat[u] = (c < c1 && (c == c0 || prv != pos[u])) ? cat[u] : 3u;
-    }
+    for (int u = 0; u < K2_CR; u++)
+        if (64u * u + lane < nc) cv[64u * u + lane] = pos[u] << 2 | cat[u];
+}
+// The same from HBM, for the second of two k2_core calls: the first one's keys
+// have gone through the buffer.  Its loads are younger than the next read's
+// prefetched calls, so waiting for them drains the prefetch; only a read that
+// k2_pair turned down comes here.
+DEV void k2_restage_calls(const pf_dev_batch &d, uint64_t c0, uint32_t nc, uint32_t lane, uint32_t *cv) {
+    for (uint32_t c = lane; c < nc; c += 64) cv[c] = d.call_pos[c0 + c] << 2 | (uint32_t)d.call_cat[c0 + c];
 }
 
-// k2_chars from calls held in registers with their site indices
-DEV void k2_chars_reg(const K2Calls &cl, uint32_t qlo, uint32_t qhi, uint32_t lane, uint8_t *chars) {
-    const uint32_t nq = qhi - qlo;
-    for (uint32_t j = lane; j < nq; j += 64) chars[j] = 2;
-    wave_sync();
-#pragma unroll
-    for (int u = 0; u < K2_CR; u++) {
-        const uint32_t si = cl.site[u];
-        if (si >= qlo && si < qhi) chars[si - qlo] = (uint8_t)cl.cat[u];
+// k2_chars from the staged calls cv[0, n), n >= 1: one lane per site of [qlo,
+// qhi) takes the lower bound of the site's position.  The search halves a
+// wave-uniform length, so its loop is scalar and the lanes do not diverge:
+// ceil(log2 n) dependent LDS reads and one for the element found.  A site
+// without a call, or whose first call has category 2 or 3, gets '-'.
+DEV void k2_chars_site(const uint32_t *cv, uint32_t n, const uint32_t *sp, uint32_t qlo, uint32_t qhi, uint32_t lane,
+                       uint8_t *chars) {
+    wave_sync();                                         // the staged calls
+    for (uint32_t q = qlo + lane; q < qhi; q += 64) {
+        const uint32_t p = sp[q], key = p << 2;
+        uint32_t base = 0;                               // the lower bound is in [base, base + len]
+        for (uint32_t len = n; len > 1;) {
+            const uint32_t half = len >> 1;
+            if (cv[base + half - 1] < key) base += half;
+            len -= half;
+        }
+        uint32_t v = cv[base];
+        if (v < key) v = base + 1 < n ? cv[base + 1] : 0xFFFFFFFFu;
+        const uint32_t c = v & 3u;
+        chars[q - qlo] = (uint8_t)((v >> 2) == p && c < 2u ? c : 2u);
     }
-    wave_sync();
+    wave_sync();                                         // cv is free for keys from here
 }
 
 // One read, one direction, one wavefront.  sp = real site positions, st =
@@ -477,11 +438,13 @@ DEV void k2_chars_reg(const K2Calls &cl, uint32_t qlo, uint32_t qhi, uint32_t la
 // index of each start; buffers of capw entries (LDS or HBM scratch).
 // With kst, keys go to that LDS staging buffer (the caller copies them to the
 // arena) and the number staged is returned; otherwise straight to the arena.
+// cv: the read's calls staged in LDS (k2_stage_calls; it may be kst itself, the
+// characters are built before the first key is staged), null: calls from HBM.
 template <typename IR>
 DEV uint32_t k2_core(const pf_dev_batch &d, uint32_t r, uint32_t dir, uint32_t lane, uint32_t S,
                      const uint32_t *sp, const uint32_t *st, const uint8_t *lens, const uint32_t *q1,
                      uint8_t *chars, uint8_t *crank, IR *irank, uint32_t capw, const K2Read &rd,
-                     const K2Calls *cl, uint64_t koff, unsigned long long *k2acc = nullptr,
+                     const uint32_t *cv, uint64_t koff, unsigned long long *k2acc = nullptr,
                      uint32_t *kst = nullptr) {
     uint32_t staged_n = 0;
     const uint32_t g = 2 * r + dir;
@@ -508,7 +471,7 @@ DEV uint32_t k2_core(const pf_dev_batch &d, uint32_t r, uint32_t dir, uint32_t l
                     if (lane == 0) atomicOr(d.status, PF_ST_INTERNAL);
                 } else {
                     K2_STAMP(0);
-                    if (cl) k2_chars_reg(*cl, qlo, qhi, lane, chars);
+                    if (cv) k2_chars_site(cv, (uint32_t)(c1 - c0), sp, qlo, qhi, lane, chars);
                     else k2_chars(d, c0, c1, sp, qlo, qhi, lane, chars);
                     K2_STAMP(1);
                     // buffer site entries: indices of [xl,xr) except repeats of the
@@ -742,7 +705,7 @@ DEV uint32_t k2_key_bytes(const uint8_t *cb, uint32_t e, uint32_t L) {
 // exceeds k12_capw.
 DEV bool k2_pair(const pf_dev_batch &d, uint32_t r, uint32_t lane, uint32_t S, const uint32_t *sp,
                  const uint32_t *st1, const uint32_t *q1s, const uint8_t *l0s, const uint8_t *l1s, uint8_t *wb,
-                 const K2Read &rd, const K2Calls &cl, uint64_t k0, uint64_t k1, unsigned long long *k2acc,
+                 const K2Read &rd, uint64_t k0, uint64_t k1, unsigned long long *k2acc,
                  uint32_t &pend_n) {
     uint8_t *chars = wb, *crank = wb + PF_K12_CAPW;
     uint16_t *irank = reinterpret_cast<uint16_t *>(wb + 2 * PF_K12_CAPW);
@@ -783,7 +746,7 @@ DEV bool k2_pair(const pf_dev_batch &d, uint32_t r, uint32_t lane, uint32_t S, c
     const uint32_t ulo = xl0 < ql1 ? xl0 : ql1, uhi = xr0 > qh1 ? xr0 : qh1;
     if (xr0 - xl0 > PF_K12_CAPW || xr1 - xl1 > PF_K12_CAPW || uhi - ulo > d.k12_capw) return false;
     K2_STAMP(0);
-    k2_chars_reg(cl, ulo, uhi, lane, chars);
+    k2_chars_site(kst, (uint32_t)(rd.c1 - rd.c0), sp, ulo, uhi, lane, chars);
     const uint32_t cap = rd.cap, maxcall = rd.maxcall;
     // ---- direction 0
     {
@@ -943,12 +906,12 @@ DEV bool k2_pair(const pf_dev_batch &d, uint32_t r, uint32_t lane, uint32_t S, c
 
 // The methmer phase of one window over its reads i0, i0 + NW, ... < i1 (wave
 // wid of NW): one wavefront per read, both directions, the window's site
-// arrays in LDS (sp, st1, q1s, l0s, l1s; hsd when use_hash), the wave's
+// arrays in LDS (sp, st1, q1s, l0s, l1s), the wave's
 // buffers at wb.  Used by K12 for its own reads and by pf_k12_chunks for the
 // read chunks of the windows K12 hands over.
 DEV void k12_methmers(const pf_dev_batch &d, uint32_t r0, uint32_t i0, uint32_t i1, uint32_t wid, uint32_t NW,
                       uint32_t lane, uint32_t S, const uint32_t *sp, const uint32_t *st1, const uint32_t *q1s,
-                      const uint8_t *l0s, const uint8_t *l1s, const K2SiteHash &hsd, bool use_hash, uint8_t *wb,
+                      const uint8_t *l0s, const uint8_t *l1s, uint8_t *wb,
                       unsigned long long *k2acc, uint32_t *rctr) {
         uint8_t *chars = wb, *crank = wb + PF_K12_CAPW;
         uint16_t *irank = reinterpret_cast<uint16_t *>(wb + 2 * PF_K12_CAPW);
@@ -985,23 +948,25 @@ DEV void k12_methmers(const pf_dev_batch &d, uint32_t r0, uint32_t i0, uint32_t 
             K2Read rd = rdA;
             const uint64_t nc = rd.c1 - rd.c0;
             const bool regs = rd.cap <= d.k12_capw && nc <= 64ull * K2_CR;
-            K2Calls cl;
             if (regs) {
-                k2_finish_calls(rd.c0, rd.c1, lane, pA, tA, cl);
                 // last call position (sorted order) from the registers
                 uint32_t mc = 0;
                 if (nc) {
                     const uint32_t ul = (uint32_t)((nc - 1) >> 6), ll = (uint32_t)((nc - 1) & 63);
 #pragma unroll
                     for (int u = 0; u < K2_CR; u++)
-                        if ((uint32_t)u == ul) mc = rdl(cl.pos[u], ll);
+                        if ((uint32_t)u == ul) mc = rdl(pA[u], ll);
                 }
                 rd.maxcall = mc;
-                k2_calls_sites(cl, uni((uint32_t)nc), sp, S, hsd, use_hash);
             }
             K2_STAMP(4);
             k2_flush(d, kst, pend_off, pend_n, lane);
             pend_n = 0;
+            K2_STAMP(8);
+            // kst is free between that copy and this read's first staged key:
+            // the read's calls go there for k2_chars_site
+            if (regs) k2_stage_calls(pA, tA, uni((uint32_t)nc), lane, kst);
+            K2_STAMP(4);
             K2Read rdC = {0, 0, 0, 0, 0, 0};
             const uint32_t iC = iB < i1 ? take() : i1;
             if (iC < i1) k2_load_scalars(d, r0 + iC, rdC);
@@ -1013,17 +978,18 @@ DEV void k12_methmers(const pf_dev_batch &d, uint32_t r0, uint32_t i0, uint32_t 
                 const uint64_t k0 = d.mmr_off[2ull * r], k1 = d.mmr_off[2ull * r + 1];
                 if (regs) {
 #if PF_K12_PAIR
-                    const bool paired = k2_pair(d, r, lane, S, sp, st1, q1s, l0s, l1s, wb, rd, cl, k0, k1, k2acc, pend_n);
+                    const bool paired = k2_pair(d, r, lane, S, sp, st1, q1s, l0s, l1s, wb, rd, k0, k1, k2acc, pend_n);
 #else
                     const bool paired = false;
 #endif
                     if (!paired) {
                         const uint32_t n0 = k2_core(d, r, 0, lane, S, sp, sp, l0s, q1s, chars, crank, irank,
-                                                    PF_K12_CAPW, rd, &cl, k0, k2acc, kst);
+                                                    PF_K12_CAPW, rd, kst, k0, k2acc, kst);
                         k2_flush(d, kst, k0, n0, lane);
+                        k2_restage_calls(d, rd.c0, (uint32_t)nc, lane, kst);
                         K2_STAMP(5);
                         pend_n = k2_core(d, r, 1, lane, S, sp, st1, l1s, q1s, chars, crank, irank, PF_K12_CAPW, rd,
-                                         &cl, k1, k2acc, kst);
+                                         kst, k1, k2acc, kst);
                     }
                     pend_off = k1;
                     K2_STAMP(5);
@@ -1647,30 +1613,9 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
     // one wavefront per read, both directions, site arrays in LDS.  Reads
     // whose site-entry bound exceeds the wave buffer (and every read of a
     // window whose sites do not fit LDS) go to the K2 fallback kernel.
-    // position -> site index hash (hash-path windows whose hash fits beside
-    // the arrays and the wave buffers)
     const uint32_t arr_b = (uint32_t)((14ull * S + 15) & ~15ull);
-    // load factor <= 1/4: most lookups are misses (calls at CpGs that are not
-    // sites), which linear probing makes long at high load
-    uint32_t HS = 1;
-    while (HS < S * 4) HS <<= 1;
-    const bool use_hash = staged && fast && nseg == 1 && arr_b + 4u * HS + 16u * PF_K12_WB * PF_K12_CAPW <= 4u * PF_K1_TILE;
-    uint32_t *hst = reinterpret_cast<uint32_t *>(reinterpret_cast<uint8_t *>(tile) + arr_b);
     if (tid == 0) sh_misc[5] = NW;                       // the methmer phase's read counter
-    if (use_hash) {
-        for (uint32_t j = tid; j < HS; j += NT) hst[j] = PF_NONE;
-        __syncthreads();
-        for (uint32_t p = tid; p < S; p += NT) {
-            const uint32_t rel = sp[p] - pmin;
-            uint32_t h = k2_hash_slot(rel) & (HS - 1);
-            while (atomicCAS(&hst[h], PF_NONE, (rel << 13) | p) != PF_NONE) h = (h + 1) & (HS - 1);
-        }
-    }
     __syncthreads();
-    K2SiteHash hsd;
-    hsd.t = hst;
-    hsd.mask = HS - 1;
-    hsd.pmin = pmin;
 
     if (staged && R >= d.k12c_minr && S <= d.k12c_smax) {
         // a heavy window: its reads go to pf_k12_chunks in chunks of
@@ -1684,15 +1629,14 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
         }
     } else if (staged) {
         // per-wave buffers: chars, crank (u8), irank (u16), key staging (u32)
-        uint8_t *wb = reinterpret_cast<uint8_t *>(tile) + arr_b + (use_hash ? 4u * HS : 0u) +
-                      wid * (uint64_t)PF_K12_WB * PF_K12_CAPW;
+        uint8_t *wb = reinterpret_cast<uint8_t *>(tile) + arr_b + wid * (uint64_t)PF_K12_WB * PF_K12_CAPW;
 #ifdef PF_K3_PROFILE
         unsigned long long k2a[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, __builtin_amdgcn_s_memtime()};
         unsigned long long *k2acc = wid == 0 ? k2a : nullptr;
 #else
         unsigned long long *k2acc = nullptr;
 #endif
-        k12_methmers(d, r0, 0, R, wid, NW, lane, S, sp, st1, q1s, l0s, l1s, hsd, use_hash, wb, k2acc, &sh_misc[5]);
+        k12_methmers(d, r0, 0, R, wid, NW, lane, S, sp, st1, q1s, l0s, l1s, wb, k2acc, &sh_misc[5]);
 #ifdef PF_K3_PROFILE
         if (tid == 0) {
             for (int j = 0; j < 7; j++) d.prof[64ull * d.W + (uint64_t)w * 16 + 8 + j] = k2a[j];
@@ -1711,9 +1655,6 @@ __global__ __launch_bounds__(PF_K1_THREADS) void pf_k12_sites_methmers(pf_dev_ba
 // PF_K12C_READS reads of one window; a workgroup stages the window's site
 // arrays (14 B per site, written by K12) in LDS and runs k12_methmers over
 // the chunk with its PF_K12C_WAVES waves.  Persistent over the item counter.
-// No position hash (the heavy windows' calls span beyond K12's bitmap): the
-// calls' site indices come from binary searches in LDS, as K12's dense-path
-// windows do.
 // 4 waves per SIMD (128 VGPRs): without the bound the allocator spreads the
 // methmer phase over ~150 registers and the kernel drops to 3 waves.
 __global__ __launch_bounds__(PF_K12C_WAVES * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void pf_k12_chunks(pf_dev_batch d) {
@@ -1743,10 +1684,8 @@ __global__ __launch_bounds__(PF_K12C_WAVES * 64) __attribute__((amdgpu_waves_per
         __syncthreads();
         const uint32_t arr_b = (uint32_t)((14ull * S + 15) & ~15ull);
         uint8_t *wb = smem + arr_b + wid * (uint64_t)PF_K12_WB * PF_K12_CAPW;
-        K2SiteHash hsd;
-        hsd.t = nullptr; hsd.mask = 0; hsd.pmin = 0;
         const uint32_t c1 = min(R, c0 + PF_K12C_READS);
-        k12_methmers(d, r0, c0, c1, wid, PF_K12C_WAVES, lane, S, sp, st1, q1s, l0s, l1s, hsd, false, wb, nullptr,
+        k12_methmers(d, r0, c0, c1, wid, PF_K12C_WAVES, lane, S, sp, st1, q1s, l0s, l1s, wb, nullptr,
                      &s_rctr);
         __syncthreads();                                 // the site arrays are reused by the next item
     }

@@ -181,7 +181,10 @@ if (~dense).any():
     cpr = k12[~dense, 2] / np.maximum(rw[~dense], 1)
     print(f"  fast-path sites cycles per record: p10 {np.percentile(cpr, 10):.0f} p50 {np.median(cpr):.0f} "
           f"p90 {np.percentile(cpr, 90):.0f}")
-k2n = ["lb + ranges", "chars", "entries", "emission", "calls: flags+sites", "core tails", "loop back-edge"]
+# "calls: staging": the wait for the read's prefetched calls, its last call's
+# position and the copy of the calls to the wave's LDS buffer; the search from
+# the site side is in "chars"
+k2n = ["lb + ranges", "chars", "entries", "emission", "calls: staging", "core tails", "loop back-edge"]
 print("  K12 methmer phase, wave 0, cycles summed over its reads: mean over windows")
 for j in range(7):
     print(f"    {k2n[j]:18s} {k12[:, 8 + j].mean():10.0f}")

@@ -58,7 +58,7 @@ for cov in COVS:
     print("  K12 phases, cycles: mean over windows | slowest window")
     for j in range(1, 7):
         print(f"    {names12[j]:12s} {k12[:, j].mean():10.0f} | {k12[mx, j]:10.0f}")
-    k2n = ["lb + ranges", "chars", "entries", "emission", "calls: flags+sites", "core tails",
+    k2n = ["lb + ranges", "chars", "entries", "emission", "calls: staging", "core tails",
            "loop back-edge"]
     print("  K12 methmer phase, wave 0, cycles summed over its reads: mean over windows")
     for j in range(7):
