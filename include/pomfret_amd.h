@@ -438,6 +438,87 @@ int  pf_dmr_acc_add(pf_dmr_acc_t *acc, const pf_dmr_t *part);
 int  pf_dmr_acc_flush(pf_dmr_acc_t *acc, pf_dmr_t **final);
 void pf_dmr_acc_free(pf_dmr_acc_t *acc);
 
+/* Allele-specific regions by a hidden Markov model (pf_dmr_hmm.hip; no
+ * reference counterpart): where pf_dmr_regions asks every CpG of a run to pass
+ * a fixed difference, this sums per-site evidence along the contig and makes a
+ * region pay to open and to close, so one noisy CpG does not cut a region in
+ * two.  Input as pf_dmr_regions: the position-sorted sites of windows [w0, w1)
+ * of a pileup, pf_dmr_cfg_t and sorted breaks.  All in integers; L is
+ * pf_ilog2_q16; scores are int64 in Q16 bits.
+ *   informative  n1 >= min_cov && n2 >= min_cov; every other site is
+ *                transparent, as in pf_dmr_regions;
+ *   chain        a maximal sequence of consecutive informative sites a < b
+ *                with b - a <= max_gap and no break x in a < x <= b
+ *                (pf_dmr_regions' join rule without the sign); chains are
+ *                independent of one another;
+ *   evidence     of an informative site, with m = m1+m2, u = u1+u2, n = n1+n2:
+ *                sep  = m1*(L(m1+1)-L(n1+2)) + u1*(L(u1+1)-L(n1+2))
+ *                     + m2*(L(m2+1)-L(n2+2)) + u2*(L(u2+1)-L(n2+2)),
+ *                pool = m*(L(m+1)-L(n+2)) + u*(L(u+1)-L(n+2)),
+ *                g = min(max(sep - pool, 0), 2^28): the Laplace-smoothed
+ *                log-likelihood ratio, in bits, of "two levels" against "one
+ *                level"; d = m1*n2 - m2*n1; e = g if d > 0, -g if d < 0, else
+ *                0 (pf_dmr_hmm_evidence).  With the clamp, and the two costs at
+ *                most 2^22 each, every path sum stays below 2^60 in magnitude
+ *                for any range below 2^31 sites;
+ *   states       0 none, 1 h1>h2, 2 h1<h2; emission em[0] = 0,
+ *                em[1] = e - site_cost_q16, em[2] = -e - site_cost_q16;
+ *   Viterbi      per chain: V_0[s] = em_0[s]; for i >= 1
+ *                cand(r,s) = V_{i-1}[r] - (r != s ? switch_q16 : 0),
+ *                best[s] = max_r cand(r,s), V_i[s] = em_i[s] + best[s],
+ *                bp_i[s] = s if cand(s,s) == best[s], else the smallest r that
+ *                attains it.  The last site's state is the smallest s that
+ *                attains max V_last; x_{i-1} = bp_i[x_i].  Both ends of a chain
+ *                are free;
+ *   run          a maximal stretch of consecutive sites of one chain in one
+ *                non-zero state: start, end, n_sites (all members, the weak
+ *                ones included), sign (+1 for state 1, -1 for state 2), sum[4]
+ *                over the members, open = 0;
+ *   kept         a run with n_sites >= min_sites and, with M1,U1,M2,U2 = sum[],
+ *                N1 = M1+U1, N2 = M2+U2,
+ *                sign*(M1*N2 - M2*N1)*100 >= min_delta_pct*N1*N2 in 128 bits:
+ *                under the model min_delta_pct is a property of the region's
+ *                pooled levels, not of each CpG.
+ * There is no stitching: the call takes everything the caller regards as a
+ * whole, and the chains at the range's ends are closed there.  The device
+ * result is the sequential one bit for bit, for any block: the forward pass is
+ * a scan of 3x3 max-plus matrices, the backtrace a reverse scan of composed
+ * maps {0,1,2} -> {0,1,2}, both exact and associative.  The two defaults are
+ * choices made on simulated data, not measured on real samples. */
+typedef struct pf_dmr_hmm_cfg {
+    int32_t site_cost_q16;     /* what a site pays to be in state 1 or 2; default 2 bits (131,072); [0, 64*65536] */
+    int32_t switch_q16;        /* what a change of state pays; default 8 bits (524,288); [0, 64*65536]            */
+} pf_dmr_hmm_cfg_t;
+
+#define PF_DMR_HMM_SITES 1u    /* flags: also return state[] and evidence[] */
+typedef struct pf_dmr_hmm {
+    uint64_t n_runs;
+    const pf_dmr_run_t *runs;  /* [n_runs] ascending, the kept runs, open = 0    */
+    uint64_t n_informative;    /* informative sites of the range                 */
+    uint64_t n_chains;         /* chains of the range                            */
+    uint64_t n_sites;          /* sites of the range                             */
+    const uint8_t *state;      /* [n_sites] 0, 1, 2; 255 a transparent site; NULL without PF_DMR_HMM_SITES */
+    const int64_t *evidence;   /* [n_sites] e; 0 at a transparent site; NULL without PF_DMR_HMM_SITES      */
+    float ms_kernels;          /* event-timed: the model's and the run kernels   */
+    float ms_upload;           /* host clock: the range's pos, cnt and the breaks to the device */
+} pf_dmr_hmm_t;
+
+/* The kept runs of the sites of windows [w0, w1) of pile.  Errors as
+ * pf_dmr_regions (positions not ascending, unsorted breaks, min_delta_pct >
+ * 100: PF_ERR_ARG; a count above 65,535: PF_ERR_LIMIT), and PF_ERR_ARG for a
+ * cost outside [0, 64*65536].  block as in pf_dmr_regions_block: 0 is
+ * PF_DMR_BLOCK of the environment or 1,024; a power of two in [64, 1024].  An
+ * empty range and a range without an informative site are valid, empty
+ * results.  Runs on ctx's stream; the result is owned by the library
+ * (pf_dmr_hmm_free). */
+int  pf_dmr_hmm_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w0, uint32_t w1, const pf_dmr_cfg_t *cfg,
+                        const pf_dmr_hmm_cfg_t *hcfg, const uint32_t *breaks, uint32_t n_breaks, uint32_t block,
+                        uint32_t flags, pf_dmr_hmm_t **out);
+void pf_dmr_hmm_free(pf_dmr_hmm_t *h);
+/* e of a site on the host (the code the kernels compile); each count at most
+ * 65,535, 0 for anything larger. */
+int64_t pf_dmr_hmm_evidence(uint32_t m1, uint32_t u1, uint32_t m2, uint32_t u2);
+
 /* Read-label permutation test of windows (pf_perm.hip; no reference
  * counterpart): for each window [ws, we) of a batch, how often a random
  * relabelling of its reads separates the two pooled methylation fractions at
@@ -1481,6 +1562,34 @@ int  pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t 
                              const pf_hapmeth_assign_t *assign, const pf_hapmeth_tagcheck_t *tagcheck,
                              pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst, pf_hapmeth_perm_stats_t *pst,
                              pf_hapmeth_assign_stats_t *ast, pf_hapmeth_tagcheck_stats_t *tst);
+
+/* hapmeth --dmr --dmr-hmm: the regions by pf_dmr_hmm_regions instead of
+ * pf_dmr_regions. */
+typedef struct pf_hapmeth_hmm {
+    pf_dmr_hmm_cfg_t cfg;
+} pf_hapmeth_hmm_t;
+
+typedef struct pf_hapmeth_hmm_stats {
+    uint64_t n_chains;         /* summed pf_dmr_hmm_t.n_chains                             */
+    double ms_kernels;         /* summed pf_dmr_hmm_t.ms_kernels                           */
+} pf_hapmeth_hmm_stats_t;
+
+/* pf_hapmeth_run_tagcheck, and with hmm != NULL the regions of a contig come
+ * from one pf_dmr_hmm_regions call at its end: each job's informative sites
+ * (dmr->cfg.min_cov; transparent sites change nothing and are dropped) are
+ * kept on the host, the contig's sites go through the model as one range under
+ * dmr->cfg and the contig's breaks, and the kept runs are the regions --
+ * tested, assigned from, checked and written exactly as pf_dmr_regions' are,
+ * into the same file with the same columns.  Neither the chunk size, the job
+ * size nor a skipped window changes a byte of it.  dst->ms_kernels counts the
+ * model's kernels as the region kernels.  hmm == NULL: exactly
+ * pf_hapmeth_run_tagcheck (hst is zeroed).  hmm without dmr, or a cost outside
+ * [0, 64*65536], returns PF_ERR_ARG.  Every stats pointer may be NULL. */
+int  pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                        const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                        const pf_hapmeth_tagcheck_t *tagcheck, pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst,
+                        pf_hapmeth_hmm_stats_t *hst, pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast,
+                        pf_hapmeth_tagcheck_stats_t *tst);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

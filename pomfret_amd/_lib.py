@@ -12,7 +12,7 @@ import weakref
 
 import numpy as np
 
-from .abi import (DMR_RUN_DTYPE, AlnBatch, AssignConfig, PfAssign, PfAssignCfg, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
+from .abi import (DMR_HMM_SITES, DMR_RUN_DTYPE, HmmConfig, PfDmrHmm, PfDmrHmmCfg, AlnBatch, AssignConfig, PfAssign, PfAssignCfg, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
                   PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfReadAlnBatch, PfTagcheck, PfWindowBatch, PfWindowOut, ReadAlnBatch,
                   WindowBatch, WindowResult)
 
@@ -87,6 +87,12 @@ def lib():
         L.pf_dmr_regions_block.argtypes = [C.c_void_p, C.POINTER(PfPileup), C.c_uint32, C.c_uint32, C.POINTER(PfDmrCfg),
                                            C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.POINTER(PfDmr))]
         L.pf_dmr_free.argtypes = [C.POINTER(PfDmr)]
+        L.pf_dmr_hmm_regions.argtypes = [C.c_void_p, C.POINTER(PfPileup), C.c_uint32, C.c_uint32, C.POINTER(PfDmrCfg),
+                                         C.POINTER(PfDmrHmmCfg), C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.POINTER(C.POINTER(PfDmrHmm))]
+        L.pf_dmr_hmm_free.argtypes = [C.POINTER(PfDmrHmm)]
+        L.pf_dmr_hmm_evidence.argtypes = [C.c_uint32] * 4
+        L.pf_dmr_hmm_evidence.restype = C.c_int64
         L.pf_dmr_acc_new.argtypes = [C.POINTER(PfDmrCfg), C.c_void_p, C.c_uint32]
         L.pf_dmr_acc_new.restype = C.c_void_p
         L.pf_dmr_acc_add.argtypes = [C.c_void_p, C.POINTER(PfDmr)]
@@ -454,6 +460,35 @@ class Context:
             return _dmr_dict(d.contents)
         finally:
             lib().pf_dmr_free(d)
+
+    def dmr_hmm_regions(self, pile: dict, cfg: DmrConfig = None, hcfg: HmmConfig = None, breaks=None, w0: int = 0,
+                        w1: int = None, block: int = 0, sites: bool = False) -> dict:
+        """The allele-specific regions of the sites of windows [w0, w1) of a
+        pileup dict by the hidden Markov model (pf_dmr_hmm_regions;
+        include/pomfret_amd.h has the model): the dict of dmr_regions -- the
+        kept runs only, open all 0 -- plus n_chains; with sites=True also
+        state ([n_sites] uint8: 0 none, 1 h1>h2, 2 h1<h2, 255 a transparent
+        site) and evidence ([n_sites] int64, Q16 bits).  The range is taken as
+        a whole: there is no stitching."""
+        p, keep = _pile_to_c(pile)
+        c = (cfg or DmrConfig()).to_c()
+        hc = (hcfg or HmmConfig()).to_c()
+        b, bp, nb = _breaks(breaks)
+        h = C.POINTER(PfDmrHmm)()
+        _check(lib().pf_dmr_hmm_regions(self.handle, C.byref(p), int(w0), p.n_windows if w1 is None else int(w1),
+                                        C.byref(c), C.byref(hc), bp, nb, int(block), DMR_HMM_SITES if sites else 0,
+                                        C.byref(h)), "pf_dmr_hmm_regions")
+        try:
+            x = h.contents
+            res = _dmr_dict(x)
+            res["n_chains"] = int(x.n_chains)
+            if sites:
+                n = int(x.n_sites)
+                res["state"] = np.ctypeslib.as_array(x.state, (n,)).copy() if n else np.zeros(0, np.uint8)
+                res["evidence"] = np.ctypeslib.as_array(x.evidence, (n,)).copy() if n else np.zeros(0, np.int64)
+            return res
+        finally:
+            lib().pf_dmr_hmm_free(h)
 
     def haptag_reads(self, known: KnownVars, reads: ReadAlnBatch) -> np.ndarray:
         out = np.zeros(max(reads.n_reads, 1), np.uint8)

@@ -409,6 +409,45 @@ class PfHapmethDmrStats(C.Structure):
     _fields_ = [("n_regions", C.c_uint64), ("n_informative", C.c_uint64), ("ms_kernels", C.c_double)]
 
 
+class PfDmrHmmCfg(C.Structure):
+    """pf_dmr_hmm_cfg_t."""
+    _fields_ = [("site_cost_q16", C.c_int32), ("switch_q16", C.c_int32)]
+
+
+@dataclass
+class HmmConfig:
+    """Parameters of the hidden Markov model of pf_dmr_hmm_regions, in bits
+    (Q16 inside: round(bits * 65536)): site_cost is what every CpG of a region
+    pays, switch what opening and what closing a region pays; both in
+    [0, 64].  The defaults are choices made on simulated data, not measured on
+    real samples."""
+    site_cost: float = 2.0
+    switch: float = 8.0
+
+    def to_c(self) -> PfDmrHmmCfg:
+        return PfDmrHmmCfg(int(round(self.site_cost * 65536)), int(round(self.switch * 65536)))
+
+
+DMR_HMM_SITES = 1
+
+
+class PfDmrHmm(C.Structure):
+    """pf_dmr_hmm_t: the kept runs of one range under the model (pf_dmr_hmm_regions)."""
+    _fields_ = [("n_runs", C.c_uint64), ("runs", C.POINTER(PfDmrRun)), ("n_informative", C.c_uint64),
+                ("n_chains", C.c_uint64), ("n_sites", C.c_uint64), ("state", C.POINTER(C.c_uint8)),
+                ("evidence", C.POINTER(C.c_int64)), ("ms_kernels", C.c_float), ("ms_upload", C.c_float)]
+
+
+class PfHapmethHmm(C.Structure):
+    """pf_hapmeth_hmm_t (pf_hapmeth_run_hmm)."""
+    _fields_ = [("cfg", PfDmrHmmCfg)]
+
+
+class PfHapmethHmmStats(C.Structure):
+    """pf_hapmeth_hmm_stats_t."""
+    _fields_ = [("n_chains", C.c_uint64), ("ms_kernels", C.c_double)]
+
+
 class PfPerm(C.Structure):
     """pf_perm_t: the permutation test of a batch's windows (pf_batch_permtest)."""
     _fields_ = [("n_windows", C.c_uint32), ("n_perm", C.c_uint32), ("seed", C.c_uint32),

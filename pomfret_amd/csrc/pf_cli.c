@@ -10,6 +10,7 @@
  *   pomfret-amd hapmeth   -o out [-r chrom[:beg-end]] [--chunk-size N] [-q mapq] [-L minlen] [--host-fetch]
  *                         [--dmr [--dmr-min-cov N] [--dmr-delta PCT] [--dmr-gap N] [--dmr-min-sites N] [--dmr-max-p P]
  *                         [--dmr-blocks blocks.gtf] [--dmr-perm N [--dmr-seed S]]
+ *                         [--dmr-hmm [--dmr-hmm-site-cost BITS] [--dmr-hmm-switch BITS]]
  *                         [--assign] [--tag-check] [--assign-min-llr BITS] [--assign-min-calls N]] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
@@ -96,7 +97,7 @@ static void help_methphase(const char *prefix) {
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
        O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
        O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED,
-       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK };
+       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK, O_DMR_HMM, O_DMR_HMM_SITE, O_DMR_HMM_SWITCH };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -118,6 +119,8 @@ static const struct option longopts[] = {
     {"dmr-perm", required_argument, 0, O_DMR_PERM}, {"dmr-seed", required_argument, 0, O_DMR_SEED},
     {"assign", no_argument, 0, O_ASSIGN},        {"assign-min-llr", required_argument, 0, O_ASSIGN_LLR},
     {"assign-min-calls", required_argument, 0, O_ASSIGN_CALLS}, {"tag-check", no_argument, 0, O_TAGCHECK},
+    {"dmr-hmm", no_argument, 0, O_DMR_HMM},      {"dmr-hmm-site-cost", required_argument, 0, O_DMR_HMM_SITE},
+    {"dmr-hmm-switch", required_argument, 0, O_DMR_HMM_SWITCH},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -317,6 +320,18 @@ static void help_hapmeth(void) {
                     "               holds although one read contributes to many CpGs (\".\" where a region has reads of\n"
                     "               one haplotype only, or more than 4096).  N in 1 .. 1000000. [0: off]\n");
     fprintf(stderr, "  --dmr-seed S [opt] Seed of the permutations. [1]\n");
+    fprintf(stderr, "  --dmr-hmm [opt] Needs --dmr.  Find the regions with a three-state hidden Markov model (none, h1>h2,\n"
+                    "               h1<h2) over each contig's CpGs instead of the per-CpG threshold: every CpG adds its\n"
+                    "               evidence for one direction (log2 likelihood ratio of two methylation levels against\n"
+                    "               one), so a single noisy CpG does not cut a region in two.  --dmr-delta then applies to\n"
+                    "               a region's pooled difference, not to each CpG; --dmr-min-cov, --dmr-gap, --dmr-min-sites,\n"
+                    "               --dmr-blocks and the file's columns are as without it.\n");
+    fprintf(stderr, "  --dmr-hmm-site-cost BITS [opt] Needs --dmr-hmm.  What every CpG of a region pays, a decimal in\n"
+                    "               [0, 64]: the evidence a CpG must bring to extend a region; lower lets regions creep\n"
+                    "               into flat stretches.  A choice made on simulated data, not measured on real samples. [2]\n");
+    fprintf(stderr, "  --dmr-hmm-switch BITS [opt] Needs --dmr-hmm.  What opening and what closing a region pays, a decimal\n"
+                    "               in [0, 64]: higher asks for more evidence per region and bridges longer weak stretches.\n"
+                    "               A choice made on simulated data as well. [8]\n");
     fprintf(stderr, "  --assign [opt] Needs --dmr.  Also write {out_prefix}.hapmeth.assign.tsv: every untagged read with a call\n"
                     "               at a member CpG of a region (those that pass --dmr-max-p), scored against the region's\n"
                     "               tagged reads: qname, chrom, start, end (the region), n_calls (the read's calls used),\n"
@@ -350,7 +365,8 @@ static int hapmeth(int argc, char **argv) {
     pm.n_perm = 0; pm.seed = 1;
     pf_hapmeth_assign_t am;
     memset(&am, 0, sizeof am);
-    int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0, tagcheck = 0;
+    int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0, tagcheck = 0, hmm = 0, hmm_opt = 0;
+    double hsite = 2.0, hswitch = 8.0;
     long dcov = 5, ddelta = 40, dgap = 500, dsites = 5, dperm = 0, dseed = 1, acalls = 2;
     double allr = 3.0;
     char *end;
@@ -382,6 +398,9 @@ static int hapmeth(int argc, char **argv) {
         case O_DMR_SEED: dmr_opt = 1; dseed = strtol(optarg, &end, 10); if (*end || !*optarg) dseed = -1; break;
         case O_ASSIGN: assign = 1; break;
         case O_TAGCHECK: tagcheck = 1; break;
+        case O_DMR_HMM: hmm = 1; break;
+        case O_DMR_HMM_SITE: hmm_opt = 1; hsite = strtod(optarg, &end); if (*end || !*optarg) hsite = -1.0; break;
+        case O_DMR_HMM_SWITCH: hmm_opt = 1; hswitch = strtod(optarg, &end); if (*end || !*optarg) hswitch = -1.0; break;
         case O_ASSIGN_LLR: assign_opt = 1; allr = strtod(optarg, &end); if (*end || !*optarg) allr = -1.0; break;
         case O_ASSIGN_CALLS: assign_opt = 1; acalls = strtol(optarg, &end, 10); if (*end || !*optarg) acalls = -1; break;
         default:
@@ -412,6 +431,10 @@ static int hapmeth(int argc, char **argv) {
     }
     if (assign && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign needs --dmr\n"); return 1; }
     if (tagcheck && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --tag-check needs --dmr\n"); return 1; }
+    if (hmm_opt && !hmm) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-hmm-* options need --dmr-hmm\n"); return 1; }
+    if (hmm && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-hmm needs --dmr\n"); return 1; }
+    if (!(hsite >= 0.0 && hsite <= 64.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-hmm-site-cost (0 .. 64)\n"); return 1; }
+    if (!(hswitch >= 0.0 && hswitch <= 64.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-hmm-switch (0 .. 64)\n"); return 1; }
     if (!(allr > 0.0 && allr <= 64.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --assign-min-llr (above 0, at most 64)\n"); return 1; }
     if (acalls < 1 || acalls > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --assign-min-calls (1 .. 65535)\n"); return 1; }
     am.min_llr_q16 = (int64_t)llround(allr * 65536.0); am.min_calls = (uint32_t)acalls;
@@ -433,8 +456,11 @@ static int hapmeth(int argc, char **argv) {
     if (!assign) tm.flags = PF_HAPMETH_TAGCHECK_RULE_ONLY;
     pf_hapmeth_tagcheck_stats_t tst;
     /* --tag-check checks the rule the two --assign-* options set, with --assign or without */
-    const int rc = pf_hapmeth_run_tagcheck(&op, dmr ? &dm : NULL, pm.n_perm ? &pm : NULL, assign || tagcheck ? &am : NULL,
-                                           tagcheck ? &tm : NULL, &st, &dst, &pst, &ast, &tst);
+    pf_hapmeth_hmm_t hm;
+    hm.cfg.site_cost_q16 = (int32_t)llround(hsite * 65536.0); hm.cfg.switch_q16 = (int32_t)llround(hswitch * 65536.0);
+    pf_hapmeth_hmm_stats_t hst;
+    const int rc = pf_hapmeth_run_hmm(&op, dmr ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
+                                      assign || tagcheck ? &am : NULL, tagcheck ? &tm : NULL, &st, &dst, &hst, &pst, &ast, &tst);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;

@@ -68,6 +68,7 @@ struct dmr_args {
     uint32_t *status;              // bit 0: positions not ascending, bit 1: a count above 65,535
     pf_dmr_run_t *out;             // [n_out]
     uint64_t n_out;
+    const uint8_t *state;          // [n] pf_dmr_hmm_regions' runs only: a site's sign code, 255 a transparent site
 };
 
 __device__ __forceinline__ dmr_agg agg_none() {
@@ -167,10 +168,35 @@ __device__ __forceinline__ dmr_agg block_exclusive(const dmr_agg &mine, dmr_agg 
     return agg_combine(pre, ex, max_gap, min_sites);
 }
 
-// site i as an aggregate of its own; flags 0 when it is not informative
+// site i as an aggregate of its own; flags 0 when it is not informative.
+// STATE: the sign is the site's entry of a.state (the range was checked when
+// the states were made), not the delta rule's
+template <bool STATE>
 __device__ __forceinline__ dmr_agg site_agg(const dmr_args &a, uint32_t i, uint32_t &st) {
     dmr_agg r = agg_none();
     const uint32_t p = a.pos[i];
+    if constexpr (STATE) {
+        const uint32_t sg = a.state[i];
+        if (sg > 2u) return r;
+        uint32_t lo = 0, hi = a.n_brk;                       // breaks <= p
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (a.brk[mid] <= p) lo = mid + 1; else hi = mid;
+        }
+        r.flags = 1u | (sg ? 2u : 0u) | (sg << 2) | (sg << 4);
+        r.f_pos = r.l_pos = p;
+        r.f_rank = r.l_rank = lo;
+        r.n_inf = 1;
+        if (sg) {
+            const uint2 c01 = *reinterpret_cast<const uint2 *>(a.cnt + 6ull * i);
+            const uint2 c23 = *reinterpret_cast<const uint2 *>(a.cnt + 6ull * i + 2);
+            r.p_n = r.s_n = 1;
+            r.p_last = r.s_start = p;
+            r.p_sum[0] = r.s_sum[0] = c01.x; r.p_sum[1] = r.s_sum[1] = c01.y;
+            r.p_sum[2] = r.s_sum[2] = c23.x; r.p_sum[3] = r.s_sum[3] = c23.y;
+        }
+        return r;
+    }
     const uint2 c01 = *reinterpret_cast<const uint2 *>(a.cnt + 6ull * i);
     const uint2 c23 = *reinterpret_cast<const uint2 *>(a.cnt + 6ull * i + 2);
     const uint32_t m1 = c01.x, u1 = c01.y, m2 = c23.x, u2 = c23.y;
@@ -215,7 +241,7 @@ __device__ __forceinline__ void write_run(const dmr_args &a, const dmr_agg &X, u
     a.out[idx] = r;
 }
 
-template <bool EMIT>
+template <bool EMIT, bool STATE>
 __device__ __forceinline__ void dmr_block(const dmr_args &a) {
     __shared__ dmr_agg wtot[PF_DMR_WAVES];
     const uint32_t blk = blockIdx.x, tid = threadIdx.x;
@@ -229,7 +255,7 @@ __device__ __forceinline__ void dmr_block(const dmr_args &a) {
     uint32_t st = 0;
     dmr_agg X = agg_none();
     for (uint64_t i = i0; i < i1; i++) {
-        const dmr_agg s = site_agg(a, (uint32_t)i, st);
+        const dmr_agg s = site_agg<STATE>(a, (uint32_t)i, st);
         X = agg_combine(X, s, a.max_gap, a.min_sites);
     }
     if (!EMIT && st) atomicOr(a.status, st);                 // the error path only
@@ -240,7 +266,7 @@ __device__ __forceinline__ void dmr_block(const dmr_args &a) {
     }
     X = agg_combine(agg_load(a.agg + blk), ex, a.max_gap, a.min_sites); // everything left of this thread's sites
     for (uint64_t i = i0; i < i1; i++) {
-        const dmr_agg s = site_agg(a, (uint32_t)i, st);
+        const dmr_agg s = site_agg<STATE>(a, (uint32_t)i, st);
         if (!(s.flags & 1u)) continue;
         if ((X.flags & 1u) && X.s_n && !agg_joins(X, s, a.max_gap)) {
             const bool whole = X.flags & 2u;                 // the run that starts at the range's first informative site
@@ -254,8 +280,11 @@ __device__ __forceinline__ void dmr_block(const dmr_args &a) {
 
 }  // namespace
 
-__global__ __launch_bounds__(PF_DMR_THREADS) void pf_dmr_count(dmr_args a) { dmr_block<false>(a); }
-__global__ __launch_bounds__(PF_DMR_THREADS) void pf_dmr_emit(dmr_args a) { dmr_block<true>(a); }
+__global__ __launch_bounds__(PF_DMR_THREADS) void pf_dmr_count(dmr_args a) { dmr_block<false, false>(a); }
+__global__ __launch_bounds__(PF_DMR_THREADS) void pf_dmr_emit(dmr_args a) { dmr_block<true, false>(a); }
+// the same two passes over the states of pf_dmr_hmm_regions
+__global__ __launch_bounds__(PF_DMR_THREADS) void pf_dmr_count_state(dmr_args a) { dmr_block<false, true>(a); }
+__global__ __launch_bounds__(PF_DMR_THREADS) void pf_dmr_emit_state(dmr_args a) { dmr_block<true, true>(a); }
 
 // agg[b] <- the aggregate of the blocks before b; tot <- records, informative
 // sites: one workgroup, each thread a contiguous run of blocks
@@ -396,4 +425,72 @@ extern "C" int pf_dmr_regions_block(pf_ctx_t *ctx, const pf_pileup_t *pile, uint
 extern "C" int pf_dmr_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w0, uint32_t w1, const pf_dmr_cfg_t *cfg,
                               const uint32_t *breaks, uint32_t n_breaks, pf_dmr_t **out) {
     return pf_dmr_regions_block(ctx, pile, w0, w1, cfg, breaks, n_breaks, 0, out);
+}
+
+// pf_dmr_hmm.hip's run extraction: the three passes above over arrays that are
+// on the device already, the sign of a site taken from d_state.  Enqueues on
+// ctx's stream and waits; *runs is malloc'ed, exactly sized, with the open bits
+// of pf_dmr_regions (the caller closes and filters them).
+int pf_dmr_state_runs(pf_ctx_t *ctx, const uint32_t *d_pos, const uint32_t *d_cnt, const uint32_t *d_brk, uint32_t n_brk,
+                      const uint8_t *d_state, uint32_t n, uint32_t B, const pf_dmr_cfg_t *cfg, pf_dmr_run_t **runs,
+                      uint64_t *n_runs, float *ms) {
+    *runs = nullptr; *n_runs = 0; *ms = 0.0f;
+    if (n == 0) return PF_OK;
+    hipStream_t st = pf_ctx_stream(ctx);
+    std::vector<void *> tmp;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    pf_dmr_run_t *h = nullptr;
+    auto done = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        for (void *p : tmp) (void)hipFree(p);
+        for (auto e : ev) if (e) (void)hipEventDestroy(e);
+        if (rc) { free(h); *n_runs = 0; } else *runs = h;
+        return rc;
+    };
+    auto talloc = [&](void **p, size_t bytes) {
+        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
+        tmp.push_back(*p);
+        return PF_OK;
+    };
+    dmr_args a;
+    memset(&a, 0, sizeof a);
+    a.n = n; a.B = B; a.K = B > PF_DMR_THREADS ? B / PF_DMR_THREADS : 1u;
+    a.n_blocks = (uint32_t)(((uint64_t)n + B - 1) / B);
+    a.min_cov = cfg->min_cov; a.min_delta_pct = cfg->min_delta_pct; a.max_gap = cfg->max_gap; a.min_sites = cfg->min_sites;
+    a.pos = d_pos; a.cnt = d_cnt; a.brk = d_brk; a.n_brk = n_brk; a.state = d_state;
+    void *p_agg = nullptr, *p_tot = nullptr, *p_st = nullptr;
+    if (talloc(&p_agg, sizeof(dmr_agg) * (size_t)a.n_blocks) || talloc(&p_tot, 16) || talloc(&p_st, 8)) return done(PF_ERR_NOMEM);
+    for (auto &e : ev)
+        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
+    a.agg = static_cast<dmr_agg *>(p_agg);
+    a.tot = static_cast<uint64_t *>(p_tot);
+    a.status = static_cast<uint32_t *>(p_st);
+    uint64_t tot[2] = {0, 0};
+    if (hipMemsetAsync(p_st, 0, 8, st) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess) return done(PF_ERR_HIP);
+    hipLaunchKernelGGL(pf_dmr_count_state, dim3(a.n_blocks), dim3(PF_DMR_THREADS), 0, st, a);
+    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    hipLaunchKernelGGL(pf_dmr_scan, dim3(1), dim3(PF_DMR_THREADS), 0, st, a);
+    if (hipGetLastError() != hipSuccess || hipEventRecord(ev[1], st) != hipSuccess ||
+        hipMemcpyAsync(tot, p_tot, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return done(PF_ERR_HIP);
+    float ms0 = 0.0f, ms1 = 0.0f;
+    if (tot[0]) {
+        h = (pf_dmr_run_t *)malloc(sizeof(pf_dmr_run_t) * (size_t)tot[0]);
+        void *p_out = nullptr;
+        if (!h || talloc(&p_out, sizeof(pf_dmr_run_t) * (size_t)tot[0])) return done(PF_ERR_NOMEM);
+        a.out = static_cast<pf_dmr_run_t *>(p_out);
+        a.n_out = tot[0];
+        if (hipEventRecord(ev[2], st) != hipSuccess) return done(PF_ERR_HIP);
+        hipLaunchKernelGGL(pf_dmr_emit_state, dim3(a.n_blocks), dim3(PF_DMR_THREADS), 0, st, a);
+        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[3], st) != hipSuccess ||
+            hipMemcpyAsync(h, p_out, sizeof(pf_dmr_run_t) * (size_t)tot[0], hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return done(PF_ERR_HIP);
+        (void)hipEventElapsedTime(&ms1, ev[2], ev[3]);
+    }
+    (void)hipEventElapsedTime(&ms0, ev[0], ev[1]);
+    (void)hipGetLastError();
+    *n_runs = tot[0];
+    *ms = ms0 + ms1;
+    return done(PF_OK);
 }

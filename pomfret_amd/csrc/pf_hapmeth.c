@@ -37,7 +37,10 @@
  *                     {prefix}.hapmeth.tagcheck.regions.tsv (host only);
  *   pf_hapmeth_run_tagcheck: pf_hapmeth_run_assign, and with --tag-check the
  *                     same second pass, on the same fetched batch, scores every
- *                     region's tagged reads leave-one-out (pf_batch_tagcheck).
+ *                     region's tagged reads leave-one-out (pf_batch_tagcheck);
+ *   pf_hapmeth_run_hmm: pf_hapmeth_run_tagcheck, and with --dmr-hmm the regions
+ *                     of a contig come from one pf_dmr_hmm_regions call over
+ *                     the informative sites its jobs left on the host.
  */
 #include <stdint.h>
 #include <stdio.h>
@@ -379,6 +382,11 @@ typedef struct {
     const pf_hapmeth_assign_t *rule;   /* the thresholds it checks; NULL: the defaults */
     char *tpath, *trpath;
     pf_hapmeth_tagcheck_stats_t tst;
+    /* --dmr-hmm */
+    const pf_hapmeth_hmm_t *hmm;
+    uint32_t *hpos, *hcnt;     /* the current contig's informative sites: position, six counts */
+    uint64_t hn, hcap;
+    pf_hapmeth_hmm_stats_t hst;
 } hm_t;
 
 /* the fetch of one job, the same in both passes: the records of the windows
@@ -399,6 +407,56 @@ static int hm_fetch(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, 
     return rc;
 }
 
+/* --dmr-hmm: the job's informative sites join the contig's */
+static int hm_keep(hm_t *H, const pf_pileup_t *pile) {
+    const uint32_t mc = H->dmr->cfg.min_cov;
+    for (uint64_t i = 0; i < pile->n_sites; i++) {
+        const uint32_t *c = pile->cnt + 6 * i;
+        if (c[0] + c[1] < mc || c[2] + c[3] < mc) continue;
+        if (H->hn == H->hcap) {
+            const uint64_t nc = H->hcap ? H->hcap * 2 : 4096;
+            uint32_t *p = (uint32_t *)realloc(H->hpos, 4ull * nc);
+            if (!p) return PF_ERR_NOMEM;
+            H->hpos = p;
+            uint32_t *q = (uint32_t *)realloc(H->hcnt, 24ull * nc);
+            if (!q) return PF_ERR_NOMEM;
+            H->hcnt = q;
+            H->hcap = nc;
+        }
+        H->hpos[H->hn] = pile->pos[i];
+        memcpy(H->hcnt + 6 * H->hn, c, 16);
+        H->hcnt[6 * H->hn + 4] = H->hcnt[6 * H->hn + 5] = 0;
+        H->hn++;
+    }
+    return PF_OK;
+}
+
+/* --dmr-hmm: the contig's kept sites as one range through the model */
+static int hm_model(hm_t *H, pf_dmr_t **fin) {
+    *fin = NULL;
+    const uint64_t off[2] = {0, H->hn};
+    pf_pileup_t one;
+    memset(&one, 0, sizeof one);
+    one.n_windows = 1; one.n_sites = H->hn; one.win_off = off; one.pos = H->hpos; one.cnt = H->hcnt;
+    pf_dmr_hmm_t *h = NULL;
+    int rc = pf_dmr_hmm_regions(H->ctx, &one, 0, 1, &H->dmr->cfg, &H->hmm->cfg, H->brk, H->n_brk, 0, 0, &h);
+    H->hn = 0;
+    if (rc) return rc;
+    pf_dmr_t *d = (pf_dmr_t *)calloc(1, sizeof *d);
+    pf_dmr_run_t *r = h->n_runs ? (pf_dmr_run_t *)malloc(h->n_runs * sizeof *r) : NULL;
+    if (!d || (h->n_runs && !r)) { free(d); free(r); pf_dmr_hmm_free(h); return PF_ERR_NOMEM; }
+    if (h->n_runs) memcpy(r, h->runs, h->n_runs * sizeof *r);
+    d->n_runs = h->n_runs;
+    d->runs = r;                                             /* pf_dmr_free */
+    d->n_informative = h->n_informative;
+    H->dst.ms_kernels += h->ms_kernels;
+    H->hst.ms_kernels += h->ms_kernels;
+    H->hst.n_chains += h->n_chains;
+    pf_dmr_hmm_free(h);
+    *fin = d;
+    return PF_OK;
+}
+
 /* one job: the windows ws/we[0, n) of chrom */
 static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, const uint32_t *we) {
     pf_dbatch_t *db = NULL;
@@ -415,7 +473,8 @@ static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, co
         H->st.n_sites += pile->n_sites;
         H->st.ms_kernels += pile->ms_kernels;
     }
-    if (!rc && H->dmr) {
+    if (!rc && H->hmm) rc = hm_keep(H, pile);
+    if (!rc && H->dmr && !H->hmm) {
         pf_dmr_t *part = NULL;
         rc = pf_dmr_regions(H->ctx, pile, 0, n, &H->dmr->cfg, H->brk, H->n_brk, &part);
         if (!rc) rc = pf_dmr_acc_add(H->acc, part);
@@ -600,7 +659,7 @@ static int hm_flush(hm_t *H, const char *chrom) {
     pf_dmr_t *fin = NULL;
     pf_perm_t *P = NULL;
     uint64_t lines = 0, dots = 0;
-    int rc = pf_dmr_acc_flush(H->acc, &fin);
+    int rc = H->hmm ? hm_model(H, &fin) : pf_dmr_acc_flush(H->acc, &fin);
     if (!rc && (H->perm || H->assign || H->tagcheck)) rc = hm_second(H, chrom, fin, &P);
     if (!rc) rc = write_dmr(H->dpath, chrom, fin, P, H->dmr->max_p, 0, &lines, &dots);
     if (!rc) {
@@ -626,8 +685,11 @@ static int hm_span(hm_t *H, int32_t tid, uint32_t s, uint32_t e, uint32_t chunk,
     if (H->dmr) {
         rc = hm_breaks(H, chrom);
         if (rc) return rc;
-        H->acc = pf_dmr_acc_new(&H->dmr->cfg, H->brk, H->n_brk);
-        if (!H->acc) return PF_ERR_NOMEM;
+        H->hn = 0;
+        if (!H->hmm) {
+            H->acc = pf_dmr_acc_new(&H->dmr->cfg, H->brk, H->n_brk);
+            if (!H->acc) return PF_ERR_NOMEM;
+        }
     }
     for (uint64_t a = s; a < e && !rc; a += chunk) {
         const uint64_t b = a + chunk < e ? a + chunk : e;
@@ -669,6 +731,15 @@ int pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *
                             const pf_hapmeth_assign_t *assign, const pf_hapmeth_tagcheck_t *tagcheck,
                             pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats, pf_hapmeth_perm_stats_t *pstats,
                             pf_hapmeth_assign_stats_t *astats, pf_hapmeth_tagcheck_stats_t *tstats) {
+    return pf_hapmeth_run_hmm(o, dmr, NULL, perm, assign, tagcheck, stats, dstats, NULL, pstats, astats, tstats);
+}
+
+int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                       const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                       const pf_hapmeth_tagcheck_t *tagcheck, pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats,
+                       pf_hapmeth_hmm_stats_t *hstats, pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats,
+                       pf_hapmeth_tagcheck_stats_t *tstats) {
+    if (hstats) memset(hstats, 0, sizeof *hstats);
     if (tstats) memset(tstats, 0, sizeof *tstats);
     const pf_hapmeth_assign_t *rule = assign;
     if (tagcheck && (tagcheck->flags & PF_HAPMETH_TAGCHECK_RULE_ONLY)) assign = NULL;
@@ -681,6 +752,9 @@ int pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *
     if (perm && (!dmr || perm->n_perm < 1u || perm->n_perm > PF_PERM_MAX_PERM)) return PF_ERR_ARG;
     if (assign && !dmr) return PF_ERR_ARG;
     if (tagcheck && !dmr) return PF_ERR_ARG;
+    if (hmm && (!dmr || hmm->cfg.site_cost_q16 < 0 || hmm->cfg.site_cost_q16 > 64 * 65536 || hmm->cfg.switch_q16 < 0 ||
+                hmm->cfg.switch_q16 > 64 * 65536))
+        return PF_ERR_ARG;
     hm_t H;
     memset(&H, 0, sizeof H);
     H.o = o;
@@ -689,6 +763,7 @@ int pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *
     H.assign = assign;
     H.tagcheck = tagcheck;
     H.rule = rule;
+    H.hmm = hmm;
     H.lc = o->load;
     /* the batch's phasing parameters are not used by the pileup: the reference's defaults */
     H.cfg.k = 3; H.cfg.k_span = 5000; H.cfg.cov_for_selection = 6; H.cfg.n_cand = 15; H.cfg.hard_cov = 15;
@@ -780,6 +855,9 @@ int pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *
     if (!rc && o->verbose && dmr)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu informative sites, %llu regions, region kernels %.3f ms\n",
                 (unsigned long long)H.dst.n_informative, (unsigned long long)H.dst.n_regions, H.dst.ms_kernels);
+    if (!rc && o->verbose && hmm)
+        fprintf(stderr, "[M::pf_hapmeth_main] hidden Markov model: %llu chains, %llu regions, model kernels %.3f ms\n",
+                (unsigned long long)H.hst.n_chains, (unsigned long long)H.dst.n_regions, H.hst.ms_kernels);
     if (!rc && o->verbose && perm)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu regions tested (%u permutations, seed %u), %llu without a test, "
                 "%llu records fetched again, permutation kernels %.3f ms\n", (unsigned long long)H.pst.n_tested,
@@ -806,6 +884,7 @@ int pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *
     if (pstats) *pstats = H.pst;
     if (astats) *astats = H.ast;
     if (tstats) *tstats = H.tst;
+    if (hstats) *hstats = H.hst;
     free(ws);
     free(we);
     free(H.path);
@@ -814,6 +893,8 @@ int pf_hapmeth_run_tagcheck(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *
     free(H.tpath);
     free(H.trpath);
     free(H.brk);
+    free(H.hpos);
+    free(H.hcnt);
     pf_dmr_acc_free(H.acc);
     pf_gaps_free(H.blocks);
     if (H.ctx) pf_ctx_destroy(H.ctx);

@@ -1,7 +1,8 @@
-// pf_llr.h -- the integer log-odds shared by pf_assign.hip and pf_tagcheck.hip
-// (include/pomfret_amd.h has the definitions): the Q16 log2, the two weights
-// of pf_batch_assign's informative site and the four leave-one-out weights of
-// pf_batch_tagcheck's.  Host and device compute the same.
+// pf_llr.h -- the integer log-odds shared by pf_assign.hip, pf_tagcheck.hip and
+// pf_dmr_hmm.hip (include/pomfret_amd.h has the definitions): the Q16 log2, the
+// two weights of pf_batch_assign's informative site, the four leave-one-out
+// weights of pf_batch_tagcheck's and the evidence of pf_dmr_hmm_regions'.  Host
+// and device compute the same.
 #ifndef PF_LLR_H
 #define PF_LLR_H
 #include <hip/hip_runtime.h>
@@ -50,6 +51,23 @@ __host__ __device__ inline void loo_weights(uint32_t m1, uint32_t u1, uint32_t m
         w[2] = m2 ? (int32_t)ilog2_q16(m1 + 1u) - (int32_t)ilog2_q16(m2) + d : 0;
         w[3] = u2 ? (int32_t)ilog2_q16(u1 + 1u) - (int32_t)ilog2_q16(u2) + d : 0;
     }
+}
+
+// pf_dmr_hmm_regions' evidence e of an informative site (counts at most 65,535
+// each, so every product stays below 2^39): the Laplace-smoothed log-likelihood
+// ratio of "two levels" against "one level" in Q16 bits, clamped to [0, 2^28],
+// with the sign of m1*n2 - m2*n1.
+__host__ __device__ inline int64_t hmm_evidence(uint32_t m1, uint32_t u1, uint32_t m2, uint32_t u2) {
+    const uint32_t n1 = m1 + u1, n2 = m2 + u2, m = m1 + m2, u = u1 + u2, n = n1 + n2;
+    const int64_t l1 = (int64_t)ilog2_q16(n1 + 2u), l2 = (int64_t)ilog2_q16(n2 + 2u), l = (int64_t)ilog2_q16(n + 2u);
+    const int64_t sep = (int64_t)m1 * ((int64_t)ilog2_q16(m1 + 1u) - l1) + (int64_t)u1 * ((int64_t)ilog2_q16(u1 + 1u) - l1) +
+                        (int64_t)m2 * ((int64_t)ilog2_q16(m2 + 1u) - l2) + (int64_t)u2 * ((int64_t)ilog2_q16(u2 + 1u) - l2);
+    const int64_t pool = (int64_t)m * ((int64_t)ilog2_q16(m + 1u) - l) + (int64_t)u * ((int64_t)ilog2_q16(u + 1u) - l);
+    int64_t g = sep - pool;
+    if (g < 0) g = 0;
+    if (g > ((int64_t)1 << 28)) g = (int64_t)1 << 28;
+    const int64_t d = (int64_t)m1 * n2 - (int64_t)m2 * n1;
+    return d > 0 ? g : (d < 0 ? -g : 0);
 }
 
 #endif

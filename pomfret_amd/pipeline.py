@@ -35,7 +35,8 @@ from ._lib import (INTERVALS_GTF, INTERVALS_TSV, INTERVALS_VCF, PomfretError, _b
                    _breaks, _dmr_dict, _dmr_to_c, _gaps_contigs, _PfBlocks, _PfGaps, lib)
 from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfHapmethDmrStats, PfHapmethOpts,
                   AssignConfig, HAPMETH_TAGCHECK_RULE_ONLY, PfAssign, PfHapmethAssign, PfHapmethAssignStats,
-                  PfHapmethTagcheck, PfHapmethTagcheckStats, PfTagcheck, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup)
+                  PfHapmethTagcheck, PfHapmethTagcheckStats, PfTagcheck, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup,
+                  HmmConfig, PfHapmethHmm, PfHapmethHmmStats)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
 JOB_WINDOWS, JOB_HAPTAG = 0, 1
@@ -131,6 +132,11 @@ def _bind():
                                           C.POINTER(PfHapmethStats), C.POINTER(PfHapmethDmrStats),
                                           C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
                                           C.POINTER(PfHapmethTagcheckStats)]
+    L.pf_hapmeth_run_hmm.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethHmm),
+                                     C.POINTER(PfHapmethPerm), C.POINTER(PfHapmethAssign), C.POINTER(PfHapmethTagcheck),
+                                     C.POINTER(PfHapmethStats), C.POINTER(PfHapmethDmrStats), C.POINTER(PfHapmethHmmStats),
+                                     C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
+                                     C.POINTER(PfHapmethTagcheckStats)]
     L.pf_tags_new.restype = vp
     L.pf_tags_free.argtypes = [vp]
     L.pf_tags_size.argtypes = [vp]
@@ -495,7 +501,8 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
                   lcfg: Optional[LoadConfig] = None, host_fetch: bool = False, threads: int = 1, device: int = 0,
                   job_windows: int = 0, dmr: Optional[DmrConfig] = None, dmr_max_p: float = 1.0,
                   dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1,
-                  assign: Optional[AssignConfig] = None, tag_check=False) -> Dict:
+                  assign: Optional[AssignConfig] = None, tag_check=False,
+                  dmr_hmm: Optional[HmmConfig] = None) -> Dict:
     """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
@@ -532,7 +539,13 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     haplotype.  Adds tagcheck_path, tagcheck_regions_path, n_tagcheck_lines,
     n_tagcheck_regions, tagcheck_ok / _flip / _undecided (each [h1, h2]),
     tagcheck_concordance (ok / (ok + flip), None when both are 0),
-    tagcheck_records and tagcheck_ms_kernels to the dict."""
+    tagcheck_records and tagcheck_ms_kernels to the dict.
+    dmr_hmm: an HmmConfig (`--dmr-hmm`; needs dmr) finds the regions with the
+    hidden Markov model of pf_dmr_hmm_regions, one call per contig, instead of
+    the per-CpG threshold; dmr.min_delta_pct then applies to a region's pooled
+    difference.  The region file keeps its name and columns and everything
+    after it works on these regions.  Adds n_chains and hmm_ms_kernels to the
+    dict (dmr_ms_kernels counts the model's kernels too)."""
     L = _bind()
     if dmr_perm and dmr is None:
         raise PomfretError("hapmeth_files: dmr_perm needs dmr")
@@ -540,6 +553,8 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         raise PomfretError("hapmeth_files: assign needs dmr")
     if tag_check and dmr is None:
         raise PomfretError("hapmeth_files: tag_check needs dmr")
+    if dmr_hmm is not None and dmr is None:
+        raise PomfretError("hapmeth_files: dmr_hmm needs dmr")
     if isinstance(tag_check, AssignConfig) and assign is not None:
         raise PomfretError("hapmeth_files: with assign, tag_check checks assign's rule: pass True")
     lc = lcfg or LoadConfig(min_len=0)
@@ -553,7 +568,17 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         dst = PfHapmethDmrStats()
         pm = PfHapmethPerm(int(dmr_perm), int(dmr_seed))
         pst = PfHapmethPermStats()
-        if tag_check:
+        if dmr_hmm is not None:
+            rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
+            am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
+            tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
+            hm = PfHapmethHmm(dmr_hmm.to_c())
+            hst, ast, tst = PfHapmethHmmStats(), PfHapmethAssignStats(), PfHapmethTagcheckStats()
+            _check(L.pf_hapmeth_run_hmm(C.byref(o), C.byref(d), C.byref(hm), C.byref(pm) if dmr_perm else None,
+                                        C.byref(am) if assign is not None or tag_check else None,
+                                        C.byref(tm) if tag_check else None, C.byref(st), C.byref(dst), C.byref(hst),
+                                        C.byref(pst), C.byref(ast), C.byref(tst)), "pf_hapmeth_run_hmm")
+        elif tag_check:
             rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
             am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
             tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
@@ -574,6 +599,8 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     if dmr is not None:
         res.update(dmr_path=out_prefix + ".hapmeth.dmr.bed", n_regions=int(dst.n_regions),
                    n_informative=int(dst.n_informative), dmr_ms_kernels=float(dst.ms_kernels))
+        if dmr_hmm is not None:
+            res.update(n_chains=int(hst.n_chains), hmm_ms_kernels=float(hst.ms_kernels))
         if dmr_perm:
             res.update(n_tested=int(pst.n_tested), n_untested=int(pst.n_untested), perm_records=int(pst.n_records),
                        perm_ms_kernels=float(pst.ms_kernels))
