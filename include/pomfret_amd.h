@@ -519,6 +519,49 @@ void pf_dmr_hmm_free(pf_dmr_hmm_t *h);
  * 65,535, 0 for anything larger. */
 int64_t pf_dmr_hmm_evidence(uint32_t m1, uint32_t u1, uint32_t m2, uint32_t u2);
 
+/* Given regions (pf_regions.hip; no reference counterpart): what the two
+ * haplotypes look like inside regions the caller names, whether or not either
+ * region call above would have found them.  Input as pf_dmr_regions: the
+ * position-sorted sites of windows [w0, w1) of a pileup and pf_dmr_cfg_t, of
+ * which min_cov and min_delta_pct are used and max_gap and min_sites are not.
+ * A region is half-open [start, end); regions may come in any order and may
+ * overlap, nest and repeat, every region is summed on its own, and none of that
+ * changes the cost: the kernels make the prefix sums of the range once and a
+ * region is the difference of two rows.  The informative rule and the sign are
+ * pf_dmr_regions', the evidence is pf_dmr_hmm_regions' e.
+ * Additivity: every field is a sum over sites, so the records of one region
+ * over two disjoint site ranges add field by field to its record over their
+ * union.  That is all the stitching there is: a caller that cuts a contig into
+ * ranges adds the parts. */
+typedef struct pf_region_sum {
+    uint32_t n_cpg;            /* sites of the range with start <= pos < end                 */
+    uint32_t n_sites;          /* of those, informative (pf_dmr_cfg_t.min_cov on both haps)  */
+    uint32_t n_pos;            /* informative sites with sign +1 (pf_dmr_regions' sign rule) */
+    uint32_t n_neg;            /* ... with sign -1                                           */
+    uint64_t sum[4];           /* informative sites' m1, u1, m2, u2                          */
+    int64_t  evidence;         /* sum of e (pf_dmr_hmm_evidence) over informative sites, Q16 */
+} pf_region_sum_t;
+typedef struct pf_regions {
+    uint64_t n;
+    const pf_region_sum_t *r;  /* [n], in the caller's region order                          */
+    uint64_t n_informative;    /* informative sites of the range                             */
+    float ms_kernels;          /* event-timed: the four kernels                              */
+    float ms_upload;           /* host clock: the range's pos and cnt and the regions to the device */
+} pf_regions_t;
+/* Errors as pf_dmr_regions: positions not strictly ascending over the range or
+ * min_delta_pct > 100: PF_ERR_ARG; a count above 65,535: PF_ERR_LIMIT.  A
+ * region with start > end: PF_ERR_ARG; start == end is an empty region, all
+ * zero.  n_regions >= 2^31: PF_ERR_LIMIT.  n_regions == 0, an empty range and a
+ * range without sites are valid results.  block: sites per workgroup, a power
+ * of two in [64, 1024]; 0 is PF_REG_BLOCK of the environment or 1,024; any
+ * other value PF_ERR_ARG.  The records are the same for any block.  Scratch on
+ * the device: 64 bytes per site of the range while the call runs.  Runs on
+ * ctx's stream; the result is owned by the library (pf_regions_free). */
+int  pf_region_sums(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w0, uint32_t w1, const pf_dmr_cfg_t *cfg,
+                    const uint32_t *reg_start, const uint32_t *reg_end, uint64_t n_regions, uint32_t block,
+                    pf_regions_t **out);
+void pf_regions_free(pf_regions_t *r);
+
 /* Read-label permutation test of windows (pf_perm.hip; no reference
  * counterpart): for each window [ws, we) of a batch, how often a random
  * relabelling of its reads separates the two pooled methylation fractions at
@@ -1590,6 +1633,105 @@ int  pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
                         const pf_hapmeth_tagcheck_t *tagcheck, pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst,
                         pf_hapmeth_hmm_stats_t *hst, pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast,
                         pf_hapmeth_tagcheck_stats_t *tst);
+
+/* hapmeth --regions: the regions come from the caller, not from the data.
+ *
+ * pf_regions_load reads a BED: lines `chrom start end [name ...]`, tab or
+ * space separated, 0-based half-open, plain or gzipped.  Lines that are empty
+ * or start with '#', "track" or "browser" are skipped.  A last line without a
+ * newline IS read (pf_mask_load and the other loaders of pf_windows.c drop it,
+ * as the reference's reader does; there is no reference to follow here).  The
+ * name is column 4, "." when absent; further columns are ignored.  Fewer than
+ * three columns, a non-numeric bound or start > end: PF_ERR_ARG; end > 2^29:
+ * PF_ERR_LIMIT; both name the line (1-based, every line counted) on stderr.  A
+ * file that cannot be read: -1.  Lines whose contig is not in `names` are
+ * dropped and counted (pf_regions_unknown).  Per contig the regions are stably
+ * sorted by (start, end): ties keep file order. */
+typedef struct pf_region_list pf_region_list_t;
+int  pf_regions_load(const char *bed_path, uint32_t n_contigs, const char *const *names, pf_region_list_t **out);
+/* contig c's regions (valid until pf_region_list_free); NULL arrays when *n is 0 */
+int  pf_regions_contig(const pf_region_list_t *list, uint32_t c, const uint32_t **start, const uint32_t **end,
+                       const char *const **name, uint64_t *n);
+uint64_t pf_regions_unknown(const pf_region_list_t *list);
+void pf_region_list_free(pf_region_list_t *list);
+
+/* Benjamini-Hochberg q-values over the tested entries of a run's regions, from
+ * the permutation test's hits.  With m the number of tested entries,
+ *   p_i    = (hits_i + 1.0) / (n_perm + 1.0),
+ *   rank_i = the number of tested entries with hits <= hits_i (ties share the
+ *            largest rank),
+ *   q_i    = min(1.0, min over tested j with hits_j >= hits_i of
+ *                     (p_j * (double)m) / (double)rank_j),
+ * evaluated in exactly this order of operations in doubles.  q[i] is NaN for an
+ * untested entry.  The correction is right for a list fixed in advance; the
+ * regions of --dmr and --dmr-hmm are selected on the data and get none. */
+int  pf_bh_adjust(const uint32_t *hits, const uint8_t *tested, uint64_t n, uint32_t n_perm, double *q);
+
+#define PF_REGION_TEST_MAX_SPAN 1000000u   /* a longer region is summed and never tested: its one window would risk
+                                              the fetch's 65,535 records per window, which fails the whole run */
+#define PF_REGION_SPLIT    1u  /* flags: a phase-block break x with start < x < end; counted, never tested */
+#define PF_REGION_ELIGIBLE 2u  /* flags: the second pass took it: reads, hits and status are set         */
+typedef struct pf_region_rec {
+    const char *chrom, *name;
+    uint32_t start, end;
+    pf_region_sum_t s;         /* summed over the contig's jobs                  */
+    uint32_t flags;            /* PF_REGION_*                                    */
+    uint32_t reads[2];         /* pf_perm_t.n_reads of its window                */
+    uint32_t hits, status;     /* pf_perm_t.hits, .status of its window          */
+} pf_region_rec_t;
+/* {prefix}.hapmeth.regions.bed, the whole file, tab-separated:
+ *   #chrom start end name n_cpg n_sites n_h1gt n_h2gt dir h1_meth h1_unmeth
+ *   h2_meth h2_unmeth delta pooled_p llr_bits block
+ * n_h1gt / n_h2gt: s.n_pos / s.n_neg.  dir, with M1,U1,M2,U2 = s.sum[], N1 =
+ * M1+U1, N2 = M2+U2: "h1>h2" if M1*N2 > M2*N1 (128 bits), "h1<h2" if less, "."
+ * otherwise.  delta (%.4f) and pooled_p (%.6g) as pf_write_dmr; pooled_p is "."
+ * when a sum exceeds INT32_MAX (a whole chromosome can; no error here).
+ * llr_bits: s.evidence / 65536.0 as %.3f.  block: "split" or "ok".  perm != 0:
+ * four more columns, reads_h1 reads_h2 perm_p perm_q.  A region that is not
+ * PF_REGION_ELIGIBLE prints "." in all four; an eligible one its reads, and
+ * with status 0 perm_p = (hits + 1) / (n_perm + 1) and perm_q =
+ * pf_bh_adjust over the eligible status-0 records of rec[0, n), both %.6g,
+ * else "." in both.  *n_tested: the records with a numeric perm_p. */
+int  pf_write_regions(const char *path, const pf_region_rec_t *rec, uint64_t n, int perm, uint32_t n_perm,
+                      uint64_t *n_tested);
+
+typedef struct pf_hapmeth_regions {
+    const char *bed_path;
+} pf_hapmeth_regions_t;
+
+typedef struct pf_hapmeth_regions_stats {
+    uint64_t n_regions;        /* lines of {prefix}.hapmeth.regions.bed                    */
+    uint64_t n_unknown_contig; /* BED lines on a contig the BAM does not have              */
+    uint64_t n_outside;        /* regions not wholly inside the run's range (opts.region)  */
+    uint64_t n_split;          /* written regions with block "split"                       */
+    uint64_t n_tested;         /* with perm: written regions with a perm_p                 */
+    uint64_t n_untested;       /* with perm: the other written regions                     */
+    double ms_kernels;         /* summed pf_regions_t.ms_kernels                           */
+} pf_hapmeth_regions_stats_t;
+
+/* pf_hapmeth_run_hmm, and with regions != NULL the second source of regions:
+ * the BED's.  After each job's pileup pf_region_sums takes the contig's regions
+ * that can intersect the job's span, and the records add up per region on the
+ * host (additivity, above), so neither the chunk size, the job size, a skipped
+ * window nor the fetch kind changes a byte.  With opts.region, regions not
+ * wholly inside it are dropped and counted.  {out_prefix}.hapmeth.regions.bed
+ * (pf_write_regions) holds one line per kept region, contigs in header order,
+ * regions in pf_regions_load's order; it is written at the end of the run
+ * because perm_q needs every region.  No .hapmeth.dmr.bed is written.  dmr
+ * gives cfg (min_cov, min_delta_pct; min_sites and max_p for eligibility),
+ * and blocks_path the breaks.  The second pass (perm, assign, tagcheck; files
+ * and formats as before) runs on the windows [start, end) of the eligible
+ * regions: not split, s.n_sites >= min_sites, pooled_p numeric and <= max_p,
+ * start < end and end - start <= PF_REGION_TEST_MAX_SPAN.  regions == NULL:
+ * exactly pf_hapmeth_run_hmm (rst is zeroed).  regions without dmr, or with
+ * hmm, returns PF_ERR_ARG.  On failure every file is unlinked.  Every stats
+ * pointer may be NULL. */
+int  pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                            const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                            const pf_hapmeth_tagcheck_t *tagcheck, const pf_hapmeth_regions_t *regions,
+                            pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst, pf_hapmeth_hmm_stats_t *hst,
+                            pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast, pf_hapmeth_tagcheck_stats_t *tst,
+                            pf_hapmeth_regions_stats_t *rst);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

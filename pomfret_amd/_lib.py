@@ -12,7 +12,7 @@ import weakref
 
 import numpy as np
 
-from .abi import (DMR_HMM_SITES, DMR_RUN_DTYPE, HmmConfig, PfDmrHmm, PfDmrHmmCfg, AlnBatch, AssignConfig, PfAssign, PfAssignCfg, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
+from .abi import (DMR_HMM_SITES, DMR_RUN_DTYPE, REGION_SUM_DTYPE, PfRegions, HmmConfig, PfDmrHmm, PfDmrHmmCfg, AlnBatch, AssignConfig, PfAssign, PfAssignCfg, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
                   PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfReadAlnBatch, PfTagcheck, PfWindowBatch, PfWindowOut, ReadAlnBatch,
                   WindowBatch, WindowResult)
 
@@ -93,6 +93,9 @@ def lib():
         L.pf_dmr_hmm_free.argtypes = [C.POINTER(PfDmrHmm)]
         L.pf_dmr_hmm_evidence.argtypes = [C.c_uint32] * 4
         L.pf_dmr_hmm_evidence.restype = C.c_int64
+        L.pf_region_sums.argtypes = [C.c_void_p, C.POINTER(PfPileup), C.c_uint32, C.c_uint32, C.POINTER(PfDmrCfg),
+                                     C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.POINTER(PfRegions))]
+        L.pf_regions_free.argtypes = [C.POINTER(PfRegions)]
         L.pf_dmr_acc_new.argtypes = [C.POINTER(PfDmrCfg), C.c_void_p, C.c_uint32]
         L.pf_dmr_acc_new.restype = C.c_void_p
         L.pf_dmr_acc_add.argtypes = [C.c_void_p, C.POINTER(PfDmr)]
@@ -489,6 +492,41 @@ class Context:
             return res
         finally:
             lib().pf_dmr_hmm_free(h)
+
+    def region_sums(self, pile: dict, cfg: DmrConfig = None, starts=(), ends=(), w0: int = 0, w1: int = None,
+                    block: int = 0) -> dict:
+        """The sums of the caller's regions [starts[i], ends[i]) over the sites
+        of windows [w0, w1) of a pileup dict (pf_region_sums;
+        include/pomfret_amd.h has the rules): dict(n_cpg, n_sites, n_pos,
+        n_neg, sum [n, 4] = the informative sites' m1, u1, m2, u2, evidence
+        (int64, Q16 bits), each in the caller's region order, n_informative,
+        ms the kernels' time, ms_upload).  Regions may come in any order and
+        overlap, nest and repeat.  Of cfg only min_cov and min_delta_pct are
+        used.  block: sites per workgroup (tests; 0: PF_REG_BLOCK of the
+        environment or the default)."""
+        p, keep = _pile_to_c(pile)
+        c = (cfg or DmrConfig()).to_c()
+        s = np.ascontiguousarray(starts, np.uint32).ravel()
+        e = np.ascontiguousarray(ends, np.uint32).ravel()
+        if s.size != e.size:
+            raise PomfretError("region_sums: starts and ends differ in length")
+        r = C.POINTER(PfRegions)()
+        _check(lib().pf_region_sums(self.handle, C.byref(p), int(w0), p.n_windows if w1 is None else int(w1), C.byref(c),
+                                    s.ctypes.data if s.size else None, e.ctypes.data if e.size else None, s.size, int(block),
+                                    C.byref(r)), "pf_region_sums")
+        try:
+            x = r.contents
+            n = int(x.n)
+            if n:
+                rec = np.ctypeslib.as_array(C.cast(x.r, C.POINTER(C.c_uint8)), (n * REGION_SUM_DTYPE.itemsize,)).copy()
+                rec = rec.view(REGION_SUM_DTYPE)
+            else:
+                rec = np.zeros(0, REGION_SUM_DTYPE)
+            return dict(n_cpg=rec["n_cpg"].copy(), n_sites=rec["n_sites"].copy(), n_pos=rec["n_pos"].copy(),
+                        n_neg=rec["n_neg"].copy(), sum=rec["sum"].copy().reshape(n, 4), evidence=rec["evidence"].copy(),
+                        n_informative=int(x.n_informative), ms=float(x.ms_kernels), ms_upload=float(x.ms_upload))
+        finally:
+            lib().pf_regions_free(r)
 
     def haptag_reads(self, known: KnownVars, reads: ReadAlnBatch) -> np.ndarray:
         out = np.zeros(max(reads.n_reads, 1), np.uint8)

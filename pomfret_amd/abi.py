@@ -438,6 +438,45 @@ class PfDmrHmm(C.Structure):
                 ("evidence", C.POINTER(C.c_int64)), ("ms_kernels", C.c_float), ("ms_upload", C.c_float)]
 
 
+class PfRegionSum(C.Structure):
+    """pf_region_sum_t."""
+    _fields_ = [("n_cpg", C.c_uint32), ("n_sites", C.c_uint32), ("n_pos", C.c_uint32), ("n_neg", C.c_uint32),
+                ("sum", C.c_uint64 * 4), ("evidence", C.c_int64)]
+
+
+REGION_SUM_DTYPE = np.dtype([("n_cpg", np.uint32), ("n_sites", np.uint32), ("n_pos", np.uint32), ("n_neg", np.uint32),
+                             ("sum", np.uint64, (4,)), ("evidence", np.int64)])
+
+
+class PfRegions(C.Structure):
+    """pf_regions_t: the sums of the caller's regions over one range (pf_region_sums)."""
+    _fields_ = [("n", C.c_uint64), ("r", C.POINTER(PfRegionSum)), ("n_informative", C.c_uint64),
+                ("ms_kernels", C.c_float), ("ms_upload", C.c_float)]
+
+
+class PfRegionRec(C.Structure):
+    """pf_region_rec_t: one line of {prefix}.hapmeth.regions.bed (pf_write_regions)."""
+    _fields_ = [("chrom", C.c_char_p), ("name", C.c_char_p), ("start", C.c_uint32), ("end", C.c_uint32),
+                ("s", PfRegionSum), ("flags", C.c_uint32), ("reads", C.c_uint32 * 2), ("hits", C.c_uint32),
+                ("status", C.c_uint32)]
+
+
+REGION_SPLIT, REGION_ELIGIBLE = 1, 2
+REGION_TEST_MAX_SPAN = 1_000_000
+
+
+class PfHapmethRegions(C.Structure):
+    """pf_hapmeth_regions_t (pf_hapmeth_run_regions)."""
+    _fields_ = [("bed_path", C.c_char_p)]
+
+
+class PfHapmethRegionsStats(C.Structure):
+    """pf_hapmeth_regions_stats_t."""
+    _fields_ = [("n_regions", C.c_uint64), ("n_unknown_contig", C.c_uint64), ("n_outside", C.c_uint64),
+                ("n_split", C.c_uint64), ("n_tested", C.c_uint64), ("n_untested", C.c_uint64),
+                ("ms_kernels", C.c_double)]
+
+
 class PfHapmethHmm(C.Structure):
     """pf_hapmeth_hmm_t (pf_hapmeth_run_hmm)."""
     _fields_ = [("cfg", PfDmrHmmCfg)]

@@ -11,6 +11,7 @@
  *                         [--dmr [--dmr-min-cov N] [--dmr-delta PCT] [--dmr-gap N] [--dmr-min-sites N] [--dmr-max-p P]
  *                         [--dmr-blocks blocks.gtf] [--dmr-perm N [--dmr-seed S]]
  *                         [--dmr-hmm [--dmr-hmm-site-cost BITS] [--dmr-hmm-switch BITS]]
+ *                         [--regions regions.bed  (instead of --dmr: the regions are given)]
  *                         [--assign] [--tag-check] [--assign-min-llr BITS] [--assign-min-calls N]] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
@@ -97,7 +98,7 @@ static void help_methphase(const char *prefix) {
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
        O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
        O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED,
-       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK, O_DMR_HMM, O_DMR_HMM_SITE, O_DMR_HMM_SWITCH };
+       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK, O_DMR_HMM, O_DMR_HMM_SITE, O_DMR_HMM_SWITCH, O_REGIONS };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -121,6 +122,7 @@ static const struct option longopts[] = {
     {"assign-min-calls", required_argument, 0, O_ASSIGN_CALLS}, {"tag-check", no_argument, 0, O_TAGCHECK},
     {"dmr-hmm", no_argument, 0, O_DMR_HMM},      {"dmr-hmm-site-cost", required_argument, 0, O_DMR_HMM_SITE},
     {"dmr-hmm-switch", required_argument, 0, O_DMR_HMM_SWITCH},
+    {"regions", required_argument, 0, O_REGIONS},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -332,6 +334,19 @@ static void help_hapmeth(void) {
     fprintf(stderr, "  --dmr-hmm-switch BITS [opt] Needs --dmr-hmm.  What opening and what closing a region pays, a decimal\n"
                     "               in [0, 64]: higher asks for more evidence per region and bridges longer weak stretches.\n"
                     "               A choice made on simulated data as well. [8]\n");
+    fprintf(stderr, "  --regions FILE [opt] Instead of --dmr: the regions are given, not found.  FILE is a BED (chrom start end\n"
+                    "               [name], 0-based half-open, plain or gzipped; regions may overlap, nest and repeat).  Writes\n"
+                    "               {out_prefix}.hapmeth.regions.bed, one line per region whether the haplotypes differ in it\n"
+                    "               or not: chrom, start, end, name, n_cpg, n_sites (CpGs with --dmr-min-cov calls on both\n"
+                    "               haplotypes), n_h1gt and n_h2gt (of those, with a --dmr-delta difference either way), dir,\n"
+                    "               the pooled counts, delta, pooled_p, llr_bits (the summed per-CpG evidence of two levels\n"
+                    "               against one, signed) and block (split: a --dmr-blocks phase block ends inside; such a\n"
+                    "               region is never tested).  Excludes --dmr, --dmr-hmm* and --dmr-gap and stands in for\n"
+                    "               --dmr wherever another option needs it.  --dmr-perm, --assign and --tag-check run on the\n"
+                    "               regions that are not split, have --dmr-min-sites CpGs, pass --dmr-max-p and are at most\n"
+                    "               1,000,000 bases long; --dmr-perm adds reads_h1, reads_h2, perm_p and perm_q, the\n"
+                    "               Benjamini-Hochberg q-value over the tested regions of the run.  With -r, regions not\n"
+                    "               wholly inside the range are dropped.\n");
     fprintf(stderr, "  --assign [opt] Needs --dmr.  Also write {out_prefix}.hapmeth.assign.tsv: every untagged read with a call\n"
                     "               at a member CpG of a region (those that pass --dmr-max-p), scored against the region's\n"
                     "               tagged reads: qname, chrom, start, end (the region), n_calls (the read's calls used),\n"
@@ -366,6 +381,9 @@ static int hapmeth(int argc, char **argv) {
     pf_hapmeth_assign_t am;
     memset(&am, 0, sizeof am);
     int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0, tagcheck = 0, hmm = 0, hmm_opt = 0;
+    int gap_opt = 0;
+    pf_hapmeth_regions_t rg;
+    rg.bed_path = NULL;
     double hsite = 2.0, hswitch = 8.0;
     long dcov = 5, ddelta = 40, dgap = 500, dsites = 5, dperm = 0, dseed = 1, acalls = 2;
     double allr = 3.0;
@@ -390,7 +408,7 @@ static int hapmeth(int argc, char **argv) {
         case O_DMR: dmr = 1; break;
         case O_DMR_COV: dmr_opt = 1; dcov = strtol(optarg, &end, 10); if (*end || !*optarg) dcov = -1; break;
         case O_DMR_DELTA: dmr_opt = 1; ddelta = strtol(optarg, &end, 10); if (*end || !*optarg) ddelta = -1; break;
-        case O_DMR_GAP: dmr_opt = 1; dgap = strtol(optarg, &end, 10); if (*end || !*optarg) dgap = -1; break;
+        case O_DMR_GAP: dmr_opt = gap_opt = 1; dgap = strtol(optarg, &end, 10); if (*end || !*optarg) dgap = -1; break;
         case O_DMR_SITES: dmr_opt = 1; dsites = strtol(optarg, &end, 10); if (*end || !*optarg) dsites = -1; break;
         case O_DMR_MAXP: dmr_opt = 1; dm.max_p = strtod(optarg, &end); if (*end || !*optarg) dm.max_p = -1.0; break;
         case O_DMR_BLOCKS: dmr_opt = 1; dm.blocks_path = optarg; break;
@@ -399,6 +417,7 @@ static int hapmeth(int argc, char **argv) {
         case O_ASSIGN: assign = 1; break;
         case O_TAGCHECK: tagcheck = 1; break;
         case O_DMR_HMM: hmm = 1; break;
+        case O_REGIONS: rg.bed_path = optarg; break;
         case O_DMR_HMM_SITE: hmm_opt = 1; hsite = strtod(optarg, &end); if (*end || !*optarg) hsite = -1.0; break;
         case O_DMR_HMM_SWITCH: hmm_opt = 1; hswitch = strtod(optarg, &end); if (*end || !*optarg) hswitch = -1.0; break;
         case O_ASSIGN_LLR: assign_opt = 1; allr = strtod(optarg, &end); if (*end || !*optarg) allr = -1.0; break;
@@ -417,7 +436,12 @@ static int hapmeth(int argc, char **argv) {
     if (op.load.qual_hi > 255 || op.load.qual_hi <= 127) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --hi (%d)\n", op.load.qual_hi); return 1; }
     if (csize <= 0) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] invalid chunk size\n"); return 1; }
     if (!op.out_prefix[0]) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] no output prefix given\n"); return 1; }
-    if (dmr_opt && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-* options need --dmr\n"); return 1; }
+    if (rg.bed_path && (dmr || hmm || hmm_opt || gap_opt)) {
+        fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --regions gives the regions: it excludes --dmr, --dmr-hmm* and --dmr-gap\n");
+        return 1;
+    }
+    const int have = dmr || rg.bed_path != NULL;       /* a source of regions */
+    if (dmr_opt && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-* options need --dmr or --regions\n"); return 1; }
     if (dcov < 1 || dcov > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-min-cov (1 .. 65535)\n"); return 1; }
     if (ddelta < 1 || ddelta > 100) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-delta (1 .. 100)\n"); return 1; }
     if (dgap < 1 || dgap > 0x7FFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-gap\n"); return 1; }
@@ -429,8 +453,8 @@ static int hapmeth(int argc, char **argv) {
         fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign-* options need --assign or --tag-check\n");
         return 1;
     }
-    if (assign && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign needs --dmr\n"); return 1; }
-    if (tagcheck && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --tag-check needs --dmr\n"); return 1; }
+    if (assign && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign needs --dmr or --regions\n"); return 1; }
+    if (tagcheck && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --tag-check needs --dmr or --regions\n"); return 1; }
     if (hmm_opt && !hmm) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-hmm-* options need --dmr-hmm\n"); return 1; }
     if (hmm && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-hmm needs --dmr\n"); return 1; }
     if (!(hsite >= 0.0 && hsite <= 64.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-hmm-site-cost (0 .. 64)\n"); return 1; }
@@ -459,8 +483,10 @@ static int hapmeth(int argc, char **argv) {
     pf_hapmeth_hmm_t hm;
     hm.cfg.site_cost_q16 = (int32_t)llround(hsite * 65536.0); hm.cfg.switch_q16 = (int32_t)llround(hswitch * 65536.0);
     pf_hapmeth_hmm_stats_t hst;
-    const int rc = pf_hapmeth_run_hmm(&op, dmr ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
-                                      assign || tagcheck ? &am : NULL, tagcheck ? &tm : NULL, &st, &dst, &hst, &pst, &ast, &tst);
+    pf_hapmeth_regions_stats_t rst;
+    const int rc = pf_hapmeth_run_regions(&op, have ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
+                                          assign || tagcheck ? &am : NULL, tagcheck ? &tm : NULL, rg.bed_path ? &rg : NULL,
+                                          &st, &dst, &hst, &pst, &ast, &tst, &rst);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;
@@ -468,6 +494,9 @@ static int hapmeth(int argc, char **argv) {
     fprintf(stderr, "[M::main] %llu sites written to %s.hapmeth.bed\n", (unsigned long long)st.n_sites, op.out_prefix);
     if (dmr)
         fprintf(stderr, "[M::main] %llu regions written to %s.hapmeth.dmr.bed\n", (unsigned long long)dst.n_regions,
+                op.out_prefix);
+    if (rg.bed_path)
+        fprintf(stderr, "[M::main] %llu regions written to %s.hapmeth.regions.bed\n", (unsigned long long)rst.n_regions,
                 op.out_prefix);
     if (pm.n_perm)
         fprintf(stderr, "[M::main] %llu of them with a permutation p-value\n", (unsigned long long)pst.n_tested);

@@ -49,6 +49,8 @@
 #endif
 #define PF_DMR_THREADS 256          /* each thread folds PF_DMR_BLOCK / PF_DMR_THREADS consecutive sites */
 #define PF_DMR_WAVES (PF_DMR_THREADS / PF_WAVE)
+#define PF_REG_BLOCK 1024           /* sites per workgroup of pf_region_sums' kernels (PF_DMR_THREADS threads), and the
+                                      PF_REG_BLOCK=<n> override's upper bound */
 #define PF_PERM_THREADS 256         /* the permutation test's workgroup (PF_PERM_THREADS=<64|256|1024> overrides it) */
 #define PF_PERM_THREADS_MAX 1024
 #define PF_PERM_READS 4096          /* participating reads per window held in LDS (PF_PERM_MAX_READS): 8 B each */

@@ -34,6 +34,7 @@
 #include <chrono>
 #include <vector>
 #include "pf_device.h"
+#include "pf_site.h"
 #include "../../include/pomfret_amd.h"
 
 struct pf_ctx;
@@ -203,10 +204,8 @@ __device__ __forceinline__ dmr_agg site_agg(const dmr_args &a, uint32_t i, uint3
     if (i > 0u && a.pos[i - 1] >= p) st |= 1u;
     if ((m1 | u1 | m2 | u2) > 0xFFFFu) { st |= 2u; return r; }
     const uint32_t n1 = m1 + u1, n2 = m2 + u2;
-    if (n1 < a.min_cov || n2 < a.min_cov) return r;
-    const int64_t d = ((int64_t)m1 * n2 - (int64_t)m2 * n1) * 100;
-    const int64_t t = (int64_t)a.min_delta_pct * n1 * n2;
-    const uint32_t sg = d >= t ? 1u : (-d >= t ? 2u : 0u);
+    if (!site_informative(n1, n2, a.min_cov)) return r;
+    const uint32_t sg = site_sign(m1, n1, m2, n2, a.min_delta_pct);
     uint32_t lo = 0, hi = a.n_brk;                           // breaks <= p
     while (lo < hi) {
         const uint32_t mid = lo + (hi - lo) / 2;

@@ -40,8 +40,15 @@
  *                     region's tagged reads leave-one-out (pf_batch_tagcheck);
  *   pf_hapmeth_run_hmm: pf_hapmeth_run_tagcheck, and with --dmr-hmm the regions
  *                     of a contig come from one pf_dmr_hmm_regions call over
- *                     the informative sites its jobs left on the host.
+ *                     the informative sites its jobs left on the host;
+ *   pf_bh_adjust, pf_write_regions: Benjamini-Hochberg q-values of a run's
+ *                     tested regions, and {prefix}.hapmeth.regions.bed (host only);
+ *   pf_hapmeth_run_regions: pf_hapmeth_run_hmm, and with --regions the regions
+ *                     come from a BED: each job's sites through pf_region_sums,
+ *                     the records added per region, the second pass on the
+ *                     eligible ones, the file written at the run's end.
  */
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -319,6 +326,103 @@ int pf_write_tagcheck_regions(const char *path, const char *chrom, const pf_tagc
     return PF_OK;
 }
 
+/* ---- given regions: the q-values and the writer */
+typedef struct { uint32_t hits; uint64_t i; } bh_ent_t;
+
+static int cmp_bh(const void *a, const void *b) {
+    const bh_ent_t *x = (const bh_ent_t *)a, *y = (const bh_ent_t *)b;
+    if (x->hits != y->hits) return x->hits < y->hits ? -1 : 1;
+    return x->i < y->i ? -1 : x->i > y->i;
+}
+
+int pf_bh_adjust(const uint32_t *hits, const uint8_t *tested, uint64_t n, uint32_t n_perm, double *q) {
+    if (n && (!hits || !tested || !q)) return PF_ERR_ARG;
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        q[i] = NAN;
+        if (tested[i]) m++;
+    }
+    if (!m) return PF_OK;
+    bh_ent_t *v = (bh_ent_t *)malloc(m * sizeof *v);
+    if (!v) return PF_ERR_NOMEM;
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < n; i++)
+        if (tested[i]) { v[k].hits = hits[i]; v[k].i = i; k++; }
+    qsort(v, m, sizeof *v, cmp_bh);
+    /* from the largest hits down: a group of equal hits [a, b) has rank b, and
+     * the minimum over everything at or above it is the running one */
+    double run = 0.0;
+    int have = 0;
+    for (uint64_t b = m; b > 0;) {
+        uint64_t a = b - 1;
+        while (a > 0 && v[a - 1].hits == v[b - 1].hits) a--;
+        const double p = ((double)v[a].hits + 1.0) / ((double)n_perm + 1.0);
+        const double x = (p * (double)m) / (double)b;
+        if (!have || x < run) run = x;
+        have = 1;
+        for (uint64_t j = a; j < b; j++) q[v[j].i] = run < 1.0 ? run : 1.0;
+        b = a;
+    }
+    free(v);
+    return PF_OK;
+}
+
+int pf_write_regions(const char *path, const pf_region_rec_t *rec, uint64_t n, int perm, uint32_t n_perm,
+                     uint64_t *n_tested) {
+    if (n_tested) *n_tested = 0;
+    if (!path || (n && !rec)) return PF_ERR_ARG;
+    double *q = NULL;
+    if (perm && n) {
+        uint32_t *hits = (uint32_t *)malloc(4ull * n);
+        uint8_t *tested = (uint8_t *)malloc(n);
+        q = (double *)malloc(8ull * n);
+        int rc = hits && tested && q ? PF_OK : PF_ERR_NOMEM;
+        for (uint64_t i = 0; i < n && !rc; i++) {
+            hits[i] = rec[i].hits;
+            tested[i] = (rec[i].flags & PF_REGION_ELIGIBLE) && rec[i].status == 0;
+        }
+        if (!rc) rc = pf_bh_adjust(hits, tested, n, n_perm, q);
+        free(hits);
+        free(tested);
+        if (rc) { free(q); return rc; }
+    }
+    FILE *fp = fopen(path, "w");
+    if (!fp) { free(q); return -1; }
+    fprintf(fp, "#chrom\tstart\tend\tname\tn_cpg\tn_sites\tn_h1gt\tn_h2gt\tdir\th1_meth\th1_unmeth\th2_meth\th2_unmeth\tdelta"
+            "\tpooled_p\tllr_bits\tblock%s\n", perm ? "\treads_h1\treads_h2\tperm_p\tperm_q" : "");
+    for (uint64_t i = 0; i < n; i++) {
+        const pf_region_rec_t *r = rec + i;
+        const uint64_t m1 = r->s.sum[0], u1 = r->s.sum[1], m2 = r->s.sum[2], u2 = r->s.sum[3];
+        const unsigned __int128 lhs = (unsigned __int128)m1 * (m2 + u2), rhs = (unsigned __int128)m2 * (m1 + u1);
+        const double delta = (m1 + u1 ? (double)m1 / (double)(m1 + u1) : 0.0) - (m2 + u2 ? (double)m2 / (double)(m2 + u2) : 0.0);
+        fprintf(fp, "%s\t%u\t%u\t%s\t%u\t%u\t%u\t%u\t%s\t%llu\t%llu\t%llu\t%llu\t%.4f\t", r->chrom ? r->chrom : ".", r->start,
+                r->end, r->name ? r->name : ".", r->s.n_cpg, r->s.n_sites, r->s.n_pos, r->s.n_neg,
+                lhs > rhs ? "h1>h2" : lhs < rhs ? "h1<h2" : ".", (unsigned long long)m1, (unsigned long long)u1,
+                (unsigned long long)m2, (unsigned long long)u2, delta);
+        if ((m1 | u1 | m2 | u2) > (uint64_t)INT32_MAX) fputc('.', fp);
+        else {
+            double two = 1.0;
+            (void)pf_fisher_exact((int)m1, (int)u1, (int)m2, (int)u2, NULL, NULL, &two);
+            fprintf(fp, "%.6g", two);
+        }
+        fprintf(fp, "\t%.3f\t%s", (double)r->s.evidence / 65536.0, (r->flags & PF_REGION_SPLIT) ? "split" : "ok");
+        if (perm) {
+            if (!(r->flags & PF_REGION_ELIGIBLE)) fprintf(fp, "\t.\t.\t.\t.");
+            else if (r->status != 0) fprintf(fp, "\t%u\t%u\t.\t.", r->reads[0], r->reads[1]);
+            else {
+                fprintf(fp, "\t%u\t%u\t%.6g\t%.6g", r->reads[0], r->reads[1],
+                        ((double)r->hits + 1.0) / ((double)n_perm + 1.0), q[i]);
+                if (n_tested) ++*n_tested;
+            }
+        }
+        fputc('\n', fp);
+    }
+    free(q);
+    const int bad = ferror(fp);
+    if (fclose(fp) != 0 || bad) return -1;
+    return PF_OK;
+}
+
 /* "chrom" or "chrom:beg-end" / "chrom:beg" (1-based inclusive, commas allowed)
  * -> tid and the 0-based [*s, *e); a name that holds ':' itself is tried whole
  * first */
@@ -387,6 +491,16 @@ typedef struct {
     uint32_t *hpos, *hcnt;     /* the current contig's informative sites: position, six counts */
     uint64_t hn, hcap;
     pf_hapmeth_hmm_stats_t hst;
+    /* --regions */
+    const pf_hapmeth_regions_t *regions;
+    pf_region_list_t *rlist;
+    char *rpath;
+    pf_region_rec_t *rec;      /* the run's kept regions, in the file's order */
+    size_t nrec, mrec;
+    uint32_t *ks, *ke, *kmax;  /* the current contig's kept regions: start, end, the largest end so far */
+    uint64_t kn;
+    size_t rec0;               /* rec + rec0: the current contig's */
+    pf_hapmeth_regions_stats_t rst;
 } hm_t;
 
 /* the fetch of one job, the same in both passes: the records of the windows
@@ -457,6 +571,79 @@ static int hm_model(hm_t *H, pf_dmr_t **fin) {
     return PF_OK;
 }
 
+/* --regions: the contig's regions that lie in [s, e) (all of them without
+ * opts.region) join the run's records with zero sums; H->brk is the contig's */
+static int hm_regions_begin(hm_t *H, int32_t tid, const char *chrom, uint32_t s, uint32_t e) {
+    const uint32_t *rs, *re;
+    const char *const *rn;
+    uint64_t n;
+    int rc = pf_regions_contig(H->rlist, (uint32_t)tid, &rs, &re, &rn, &n);
+    if (rc) return rc;
+    free(H->ks); free(H->ke); free(H->kmax);
+    H->ks = (uint32_t *)malloc(4ull * (n ? n : 1));
+    H->ke = (uint32_t *)malloc(4ull * (n ? n : 1));
+    H->kmax = (uint32_t *)malloc(4ull * (n ? n : 1));
+    H->kn = 0;
+    H->rec0 = H->nrec;
+    if (!H->ks || !H->ke || !H->kmax) return PF_ERR_NOMEM;
+    for (uint64_t i = 0; i < n; i++) {
+        if (H->o->region && (rs[i] < s || re[i] > e)) { H->rst.n_outside++; continue; }
+        if (H->nrec == H->mrec) {
+            const size_t nm = H->mrec ? H->mrec * 2 : 256;
+            pf_region_rec_t *p = (pf_region_rec_t *)realloc(H->rec, nm * sizeof *p);
+            if (!p) return PF_ERR_NOMEM;
+            H->rec = p;
+            H->mrec = nm;
+        }
+        pf_region_rec_t *r = H->rec + H->nrec++;
+        memset(r, 0, sizeof *r);
+        r->chrom = chrom; r->name = rn[i]; r->start = rs[i]; r->end = re[i];
+        uint32_t lo = 0, hi = H->n_brk;                      /* breaks <= start */
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (H->brk[mid] <= rs[i]) lo = mid + 1; else hi = mid;
+        }
+        if (lo < H->n_brk && H->brk[lo] < re[i]) { r->flags |= PF_REGION_SPLIT; H->rst.n_split++; }
+        H->ks[H->kn] = rs[i];
+        H->ke[H->kn] = re[i];
+        H->kmax[H->kn] = H->kn && H->kmax[H->kn - 1] > re[i] ? H->kmax[H->kn - 1] : re[i];
+        H->kn++;
+    }
+    return PF_OK;
+}
+
+/* --regions: the job's windows span [a, b); the contig's regions that can
+ * hold a site of it -- a superset: start < b, and some region up to it ends
+ * past a -- are summed over the job's sites and added to their records */
+static int hm_regions_job(hm_t *H, const pf_pileup_t *pile, uint32_t n, uint32_t a, uint32_t b) {
+    uint64_t lo = 0, hi = H->kn;
+    while (lo < hi) {                                        /* starts < b */
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (H->ks[mid] < b) lo = mid + 1; else hi = mid;
+    }
+    const uint64_t i1 = lo;
+    lo = 0; hi = i1;
+    while (lo < hi) {                                        /* largest end so far <= a */
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (H->kmax[mid] <= a) lo = mid + 1; else hi = mid;
+    }
+    const uint64_t i0 = lo;
+    if (i0 >= i1) return PF_OK;
+    pf_regions_t *part = NULL;
+    int rc = pf_region_sums(H->ctx, pile, 0, n, &H->dmr->cfg, H->ks + i0, H->ke + i0, i1 - i0, 0, &part);
+    if (rc) return rc;
+    for (uint64_t k = 0; k < part->n; k++) {
+        pf_region_sum_t *d = &H->rec[H->rec0 + i0 + k].s;
+        const pf_region_sum_t *x = part->r + k;
+        d->n_cpg += x->n_cpg; d->n_sites += x->n_sites; d->n_pos += x->n_pos; d->n_neg += x->n_neg;
+        for (int q = 0; q < 4; q++) d->sum[q] += x->sum[q];
+        d->evidence += x->evidence;
+    }
+    H->rst.ms_kernels += part->ms_kernels;
+    pf_regions_free(part);
+    return PF_OK;
+}
+
 /* one job: the windows ws/we[0, n) of chrom */
 static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, const uint32_t *we) {
     pf_dbatch_t *db = NULL;
@@ -474,7 +661,8 @@ static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, co
         H->st.ms_kernels += pile->ms_kernels;
     }
     if (!rc && H->hmm) rc = hm_keep(H, pile);
-    if (!rc && H->dmr && !H->hmm) {
+    if (!rc && H->regions) rc = hm_regions_job(H, pile, n, ws[0], we[n - 1]);
+    if (!rc && H->dmr && !H->hmm && !H->regions) {
         pf_dmr_t *part = NULL;
         rc = pf_dmr_regions(H->ctx, pile, 0, n, &H->dmr->cfg, H->brk, H->n_brk, &part);
         if (!rc) rc = pf_dmr_acc_add(H->acc, part);
@@ -677,6 +865,49 @@ static int hm_flush(hm_t *H, const char *chrom) {
     return rc;
 }
 
+/* --regions: the contig's sums are complete; its eligible regions go through
+ * the second pass as the windows [start, end) */
+static int hm_regions_flush(hm_t *H, const char *chrom) {
+    if (!H->perm && !H->assign && !H->tagcheck) return PF_OK;
+    pf_region_rec_t *rec = H->rec + H->rec0;
+    const uint64_t n = H->kn;
+    pf_dmr_t fin;
+    memset(&fin, 0, sizeof fin);
+    pf_dmr_run_t *runs = (pf_dmr_run_t *)calloc(n ? n : 1, sizeof *runs);
+    uint64_t *of = (uint64_t *)malloc(8ull * (n ? n : 1));
+    if (!runs || !of) { free(runs); free(of); return PF_ERR_NOMEM; }
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        const pf_region_rec_t *r = rec + i;
+        if ((r->flags & PF_REGION_SPLIT) || r->s.n_sites < H->dmr->cfg.min_sites || r->start >= r->end ||
+            r->end - r->start > PF_REGION_TEST_MAX_SPAN ||
+            (r->s.sum[0] | r->s.sum[1] | r->s.sum[2] | r->s.sum[3]) > (uint64_t)INT32_MAX)
+            continue;
+        double two = 1.0;
+        (void)pf_fisher_exact((int)r->s.sum[0], (int)r->s.sum[1], (int)r->s.sum[2], (int)r->s.sum[3], NULL, NULL, &two);
+        if (two > H->dmr->max_p) continue;
+        runs[k].start = r->start; runs[k].end = r->end; runs[k].n_sites = r->s.n_sites; runs[k].sign = 1;
+        for (int q = 0; q < 4; q++) runs[k].sum[q] = r->s.sum[q];
+        of[k++] = i;
+    }
+    fin.n_runs = k;
+    fin.runs = runs;
+    pf_perm_t *P = NULL;
+    int rc = hm_second(H, chrom, &fin, &P);                  /* takes every run: each passes max_p */
+    for (uint64_t j = 0; j < k && !rc; j++) {
+        pf_region_rec_t *r = rec + of[j];
+        r->flags |= PF_REGION_ELIGIBLE;
+        if (P) {
+            r->reads[0] = P->n_reads[2 * j]; r->reads[1] = P->n_reads[2 * j + 1];
+            r->hits = P->hits[j]; r->status = P->status[j];
+        }
+    }
+    pf_perm_free(P);
+    free(runs);
+    free(of);
+    return rc;
+}
+
 /* [s, e) of contig tid in windows of `chunk` bases, jobs of at most jw windows */
 static int hm_span(hm_t *H, int32_t tid, uint32_t s, uint32_t e, uint32_t chunk, uint32_t jw, uint32_t *ws, uint32_t *we) {
     const char *chrom = pf_bam_target_name(H->bam, tid);
@@ -686,7 +917,10 @@ static int hm_span(hm_t *H, int32_t tid, uint32_t s, uint32_t e, uint32_t chunk,
         rc = hm_breaks(H, chrom);
         if (rc) return rc;
         H->hn = 0;
-        if (!H->hmm) {
+        if (H->regions) {
+            rc = hm_regions_begin(H, tid, chrom, s, e);
+            if (rc) return rc;
+        } else if (!H->hmm) {
             H->acc = pf_dmr_acc_new(&H->dmr->cfg, H->brk, H->n_brk);
             if (!H->acc) return PF_ERR_NOMEM;
         }
@@ -703,7 +937,7 @@ static int hm_span(hm_t *H, int32_t tid, uint32_t s, uint32_t e, uint32_t chunk,
         if (++n == jw) { rc = hm_job(H, chrom, n, ws, we); n = 0; }
     }
     if (!rc && n) rc = hm_job(H, chrom, n, ws, we);
-    if (!rc && H->dmr) rc = hm_flush(H, chrom);
+    if (!rc && H->dmr) rc = H->regions ? hm_regions_flush(H, chrom) : hm_flush(H, chrom);
     return rc;
 }
 
@@ -739,6 +973,17 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
                        const pf_hapmeth_tagcheck_t *tagcheck, pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats,
                        pf_hapmeth_hmm_stats_t *hstats, pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats,
                        pf_hapmeth_tagcheck_stats_t *tstats) {
+    return pf_hapmeth_run_regions(o, dmr, hmm, perm, assign, tagcheck, NULL, stats, dstats, hstats, pstats, astats, tstats,
+                                  NULL);
+}
+
+int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                           const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                           const pf_hapmeth_tagcheck_t *tagcheck, const pf_hapmeth_regions_t *regions,
+                           pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats, pf_hapmeth_hmm_stats_t *hstats,
+                           pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats,
+                           pf_hapmeth_tagcheck_stats_t *tstats, pf_hapmeth_regions_stats_t *rstats) {
+    if (rstats) memset(rstats, 0, sizeof *rstats);
     if (hstats) memset(hstats, 0, sizeof *hstats);
     if (tstats) memset(tstats, 0, sizeof *tstats);
     const pf_hapmeth_assign_t *rule = assign;
@@ -755,8 +1000,10 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
     if (hmm && (!dmr || hmm->cfg.site_cost_q16 < 0 || hmm->cfg.site_cost_q16 > 64 * 65536 || hmm->cfg.switch_q16 < 0 ||
                 hmm->cfg.switch_q16 > 64 * 65536))
         return PF_ERR_ARG;
+    if (regions && (!dmr || hmm || !regions->bed_path)) return PF_ERR_ARG;
     hm_t H;
     memset(&H, 0, sizeof H);
+    H.regions = regions;
     H.o = o;
     H.dmr = dmr;
     H.perm = perm;
@@ -785,6 +1032,26 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
     }
     uint32_t *ws = NULL, *we = NULL;
     int made = 0, dmade = 0, amade = 0, tmade = 0, trmade = 0;
+    if (!rc && regions) {
+        const int32_t nt = pf_bam_n_targets(H.bam);
+        const char **names = (const char **)malloc(sizeof(char *) * (size_t)(nt > 0 ? nt : 1));
+        if (!names) rc = PF_ERR_NOMEM;
+        for (int32_t t = 0; t < nt && !rc; t++) names[t] = pf_bam_target_name(H.bam, t);
+        if (!rc) {
+            rc = pf_regions_load(regions->bed_path, (uint32_t)(nt > 0 ? nt : 0), names, &H.rlist);
+            if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot read the regions of %s\n", regions->bed_path);
+        }
+        free(names);
+        if (!rc) {
+            H.rst.n_unknown_contig = pf_regions_unknown(H.rlist);
+            for (int32_t t = 0; t < nt; t++) {               /* the contigs the run does not visit */
+                const uint32_t *a, *b;
+                const char *const *c;
+                uint64_t n = 0;
+                if ((t < tid0 || t >= tid1) && !pf_regions_contig(H.rlist, (uint32_t)t, &a, &b, &c, &n)) H.rst.n_outside += n;
+            }
+        }
+    }
     if (!rc && dmr && dmr->blocks_path) {
         rc = pf_interval_gaps(dmr->blocks_path, PF_INTERVALS_GTF, 0, &H.blocks);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot read the phase blocks of %s\n", dmr->blocks_path);
@@ -800,15 +1067,17 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
         H.apath = (char *)malloc(l);
         H.tpath = (char *)malloc(l);
         H.trpath = (char *)malloc(l);
+        H.rpath = (char *)malloc(l);
         ws = (uint32_t *)malloc(4ull * jw);
         we = (uint32_t *)malloc(4ull * jw);
-        if (!H.path || !H.dpath || !H.apath || !H.tpath || !H.trpath || !ws || !we) rc = PF_ERR_NOMEM;
+        if (!H.path || !H.dpath || !H.apath || !H.tpath || !H.trpath || !H.rpath || !ws || !we) rc = PF_ERR_NOMEM;
         else {
             snprintf(H.path, l, "%s.hapmeth.bed", o->out_prefix);
             snprintf(H.dpath, l, "%s.hapmeth.dmr.bed", o->out_prefix);
             snprintf(H.apath, l, "%s.hapmeth.assign.tsv", o->out_prefix);
             snprintf(H.tpath, l, "%s.hapmeth.tagcheck.tsv", o->out_prefix);
             snprintf(H.trpath, l, "%s.hapmeth.tagcheck.regions.tsv", o->out_prefix);
+            snprintf(H.rpath, l, "%s.hapmeth.regions.bed", o->out_prefix);
         }
     }
     if (!rc) {
@@ -816,7 +1085,7 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.path);
         else made = 1;
     }
-    if (!rc && dmr) {
+    if (!rc && dmr && !regions) {
         pf_perm_t none;                                  /* with --dmr-perm the header names its columns */
         memset(&none, 0, sizeof none);
         rc = write_dmr(H.dpath, NULL, NULL, perm ? &none : NULL, 1.0, 1, NULL, NULL);
@@ -842,6 +1111,19 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
         if (!o->region) { s = 0; e = pf_bam_target_len(H.bam, t); }
         rc = hm_span(&H, t, s, e, chunk, jw, ws, we);
     }
+    int rmade = 0;
+    if (!rc && regions) {                              /* at the end: perm_q needs every region */
+        uint64_t tested = 0;
+        rmade = 1;
+        rc = pf_write_regions(H.rpath, H.rec, H.nrec, perm != NULL, perm ? perm->n_perm : 0, &tested);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.rpath);
+        H.rst.n_regions = H.nrec;
+        if (perm) {
+            H.rst.n_tested = H.pst.n_tested = tested;
+            H.rst.n_untested = H.pst.n_untested = H.nrec - tested;
+        }
+    }
+    if (rc && rmade) (void)unlink(H.rpath);
     if (rc && made) (void)unlink(H.path);              /* no truncated output behind a failure */
     if (rc && dmade) (void)unlink(H.dpath);
     if (rc && amade) (void)unlink(H.apath);
@@ -852,7 +1134,12 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
                 "%llu sites, pileup kernels %.3f ms\n", (unsigned long long)H.st.n_windows,
                 (unsigned long long)H.st.n_skipped, (unsigned long long)H.st.n_records,
                 (unsigned long long)H.st.n_sites, H.st.ms_kernels);
-    if (!rc && o->verbose && dmr)
+    if (!rc && o->verbose && regions)
+        fprintf(stderr, "[M::pf_hapmeth_main] given regions: %llu written (%llu split by a phase block), %llu on contigs "
+                "the BAM does not have, %llu outside the range, region kernels %.3f ms\n",
+                (unsigned long long)H.rst.n_regions, (unsigned long long)H.rst.n_split,
+                (unsigned long long)H.rst.n_unknown_contig, (unsigned long long)H.rst.n_outside, H.rst.ms_kernels);
+    if (!rc && o->verbose && dmr && !regions)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu informative sites, %llu regions, region kernels %.3f ms\n",
                 (unsigned long long)H.dst.n_informative, (unsigned long long)H.dst.n_regions, H.dst.ms_kernels);
     if (!rc && o->verbose && hmm)
@@ -885,6 +1172,7 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
     if (astats) *astats = H.ast;
     if (tstats) *tstats = H.tst;
     if (hstats) *hstats = H.hst;
+    if (rstats) *rstats = H.rst;
     free(ws);
     free(we);
     free(H.path);
@@ -895,6 +1183,12 @@ int pf_hapmeth_run_hmm(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, 
     free(H.brk);
     free(H.hpos);
     free(H.hcnt);
+    free(H.rpath);
+    free(H.rec);
+    free(H.ks);
+    free(H.ke);
+    free(H.kmax);
+    pf_region_list_free(H.rlist);
     pf_dmr_acc_free(H.acc);
     pf_gaps_free(H.blocks);
     if (H.ctx) pf_ctx_destroy(H.ctx);

@@ -43,8 +43,12 @@
  * starting at abs_start, when start - prev > chunk (uint32) emit
  * [i, i + chunk) for i = prev; i + stride < start; i += stride (uint32);
  * then prev = end.
+ *
+ * pf_regions_load: the BED of `hapmeth --regions` (no reference counterpart);
+ * unlike the loaders above it reads a last line that has no newline.
  */
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include <zlib.h>
@@ -521,8 +525,9 @@ static int known_finish(struct pf_known_own *o) {
     return PF_OK;
 }
 
-/* every complete line of a (gzipped) text file through fn(arg, line, len) */
-static int each_line(const char *path, int (*fn)(void *, const char *, size_t), void *arg) {
+/* every complete line of a (gzipped) text file through fn(arg, line, len);
+ * tail: also a last line that has no newline */
+static int each_line_tail(const char *path, int (*fn)(void *, const char *, size_t), void *arg, int tail) {
     gzFile fp = gzopen(path, "rb");
     if (!fp) return -1;
     size_t cap = 1 << 16, len = 0;
@@ -549,9 +554,14 @@ static int each_line(const char *path, int (*fn)(void *, const char *, size_t), 
         memmove(buf, buf + start, len - start);
         len -= start;
     }
+    if (!rc && tail && len) rc = fn(arg, buf, len);
     gzclose(fp);
     free(buf);
     return rc;
+}
+
+static int each_line(const char *path, int (*fn)(void *, const char *, size_t), void *arg) {
+    return each_line_tail(path, fn, arg, 0);
 }
 
 /* one pass for several contigs: a line goes to the table of the contig its
@@ -768,3 +778,148 @@ int pf_mask_contig(const pf_mask_t *m, uint32_t c, const uint32_t **pos, uint64_
     *pos = *n ? m->pos + m->off[c] : NULL;
     return PF_OK;
 }
+
+/* ------------------------------------------------------------------ */
+/* Caller-given regions (`hapmeth --regions`): a BED's lines per contig of
+ * the run, stably sorted by (start, end).  Lines are collected in file order
+ * with their contig, then sorted by (contig, start, end, file order). */
+
+struct pf_region_list {
+    uint32_t n_contigs;
+    uint64_t *off;          /* [n_contigs+1] */
+    uint32_t *start, *end;  /* [n] */
+    const char **name;      /* [n] into pool */
+    char *pool;
+    uint64_t n_unknown;
+};
+
+typedef struct { uint32_t contig, start, end; uint64_t order, name_off; } reg_line_t;
+
+typedef struct {
+    uint32_t n;
+    const char *const *names;
+    const char *path;
+    uint64_t line, n_unknown;
+    reg_line_t *v;
+    size_t nv, mv;
+    char *pool;
+    size_t np, mp;
+} reg_acc_t;
+
+static int reg_bed_line(void *arg, const char *s, size_t l) {
+    reg_acc_t *R = (reg_acc_t *)arg;
+    R->line++;
+    if (l > 0 && s[l - 1] == '\r') l--;
+    if (l == 0 || s[0] == '#' || (l >= 5 && !memcmp(s, "track", 5)) || (l >= 7 && !memcmp(s, "browser", 7))) return 0;
+    const char *tok[4];
+    size_t tl[4];
+    int nt = 0;
+    for (size_t i = 0; i < l && nt < 4;) {
+        while (i < l && (s[i] == '\t' || s[i] == ' ')) i++;
+        if (i >= l) break;
+        tok[nt] = s + i;
+        const size_t st = i;
+        while (i < l && s[i] != '\t' && s[i] != ' ') i++;
+        tl[nt++] = i - st;
+    }
+    if (nt == 0) return 0;
+    uint64_t a = 0, b = 0;
+    if (nt < 3) {
+        fprintf(stderr, "[E::pf_regions_load] %s line %llu: fewer than three columns\n", R->path, (unsigned long long)R->line);
+        return PF_ERR_ARG;
+    }
+    if (mask_num(tok[1], tl[1], &a) || mask_num(tok[2], tl[2], &b)) {
+        fprintf(stderr, "[E::pf_regions_load] %s line %llu: start or end is not a number\n", R->path,
+                (unsigned long long)R->line);
+        return PF_ERR_ARG;
+    }
+    if (a > b) {
+        fprintf(stderr, "[E::pf_regions_load] %s line %llu: start is above end\n", R->path, (unsigned long long)R->line);
+        return PF_ERR_ARG;
+    }
+    if (b > PF_MASK_POS_LIMIT) {
+        fprintf(stderr, "[E::pf_regions_load] %s line %llu: end is above 2^29\n", R->path, (unsigned long long)R->line);
+        return PF_ERR_LIMIT;
+    }
+    uint32_t c = 0;
+    while (c < R->n && !(strlen(R->names[c]) == tl[0] && memcmp(R->names[c], tok[0], tl[0]) == 0)) c++;
+    if (c == R->n) { R->n_unknown++; return 0; }             /* a contig the run does not have */
+    const char *nm = nt > 3 ? tok[3] : ".";
+    const size_t nl = nt > 3 ? tl[3] : 1;
+    if (grow((void **)&R->v, &R->mv, R->nv + 1, sizeof *R->v) || grow((void **)&R->pool, &R->mp, R->np + nl + 1, 1))
+        return PF_ERR_NOMEM;
+    reg_line_t *x = &R->v[R->nv];
+    x->contig = c; x->start = (uint32_t)a; x->end = (uint32_t)b; x->order = R->nv; x->name_off = R->np;
+    memcpy(R->pool + R->np, nm, nl);
+    R->pool[R->np + nl] = 0;
+    R->np += nl + 1;
+    R->nv++;
+    return 0;
+}
+
+static int cmp_reg_line(const void *a, const void *b) {
+    const reg_line_t *x = (const reg_line_t *)a, *y = (const reg_line_t *)b;
+    if (x->contig != y->contig) return x->contig < y->contig ? -1 : 1;
+    if (x->start != y->start) return x->start < y->start ? -1 : 1;
+    if (x->end != y->end) return x->end < y->end ? -1 : 1;
+    return x->order < y->order ? -1 : x->order > y->order;
+}
+
+void pf_region_list_free(pf_region_list_t *l) {
+    if (!l) return;
+    free(l->off);
+    free(l->start);
+    free(l->end);
+    free(l->name);
+    free(l->pool);
+    free(l);
+}
+
+int pf_regions_load(const char *bed_path, uint32_t n_contigs, const char *const *names, pf_region_list_t **out) {
+    if (!bed_path || !out || (n_contigs && !names)) return PF_ERR_ARG;
+    *out = NULL;
+    for (uint32_t c = 0; c < n_contigs; c++) if (!names[c]) return PF_ERR_ARG;
+    reg_acc_t R;
+    memset(&R, 0, sizeof R);
+    R.n = n_contigs; R.names = names; R.path = bed_path;
+    pf_region_list_t *L = (pf_region_list_t *)calloc(1, sizeof *L);
+    int rc = L ? each_line_tail(bed_path, reg_bed_line, &R, 1) : PF_ERR_NOMEM;
+    if (!rc) {
+        if (R.nv) qsort(R.v, R.nv, sizeof *R.v, cmp_reg_line);
+        L->n_contigs = n_contigs;
+        L->n_unknown = R.n_unknown;
+        L->off = (uint64_t *)calloc((size_t)n_contigs + 1, sizeof(uint64_t));
+        L->start = (uint32_t *)malloc((R.nv ? R.nv : 1) * sizeof(uint32_t));
+        L->end = (uint32_t *)malloc((R.nv ? R.nv : 1) * sizeof(uint32_t));
+        L->name = (const char **)malloc((R.nv ? R.nv : 1) * sizeof(char *));
+        if (!L->off || !L->start || !L->end || !L->name) rc = PF_ERR_NOMEM;
+    }
+    if (!rc) {
+        L->pool = R.pool;                                    /* handed over */
+        R.pool = NULL;
+        for (size_t i = 0; i < R.nv; i++) {
+            L->start[i] = R.v[i].start;
+            L->end[i] = R.v[i].end;
+            L->name[i] = L->pool + R.v[i].name_off;
+            L->off[R.v[i].contig + 1]++;
+        }
+        for (uint32_t c = 0; c < n_contigs; c++) L->off[c + 1] += L->off[c];
+    }
+    free(R.v);
+    free(R.pool);
+    if (rc) { pf_region_list_free(L); return rc; }
+    *out = L;
+    return PF_OK;
+}
+
+int pf_regions_contig(const pf_region_list_t *l, uint32_t c, const uint32_t **start, const uint32_t **end,
+                      const char *const **name, uint64_t *n) {
+    if (!l || !start || !end || !name || !n || c >= l->n_contigs) return PF_ERR_ARG;
+    *n = l->off[c + 1] - l->off[c];
+    *start = *n ? l->start + l->off[c] : NULL;
+    *end = *n ? l->end + l->off[c] : NULL;
+    *name = *n ? l->name + l->off[c] : NULL;
+    return PF_OK;
+}
+
+uint64_t pf_regions_unknown(const pf_region_list_t *l) { return l ? l->n_unknown : 0; }

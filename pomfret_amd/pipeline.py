@@ -36,7 +36,8 @@ from ._lib import (INTERVALS_GTF, INTERVALS_TSV, INTERVALS_VCF, PomfretError, _b
 from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfHapmethDmrStats, PfHapmethOpts,
                   AssignConfig, HAPMETH_TAGCHECK_RULE_ONLY, PfAssign, PfHapmethAssign, PfHapmethAssignStats,
                   PfHapmethTagcheck, PfHapmethTagcheckStats, PfTagcheck, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup,
-                  HmmConfig, PfHapmethHmm, PfHapmethHmmStats)
+                  HmmConfig, PfHapmethHmm, PfHapmethHmmStats, PfHapmethRegions, PfHapmethRegionsStats, PfRegionRec,
+                  REGION_ELIGIBLE, REGION_SPLIT)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
 JOB_WINDOWS, JOB_HAPTAG = 0, 1
@@ -137,6 +138,21 @@ def _bind():
                                      C.POINTER(PfHapmethStats), C.POINTER(PfHapmethDmrStats), C.POINTER(PfHapmethHmmStats),
                                      C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
                                      C.POINTER(PfHapmethTagcheckStats)]
+    L.pf_hapmeth_run_regions.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethHmm),
+                                         C.POINTER(PfHapmethPerm), C.POINTER(PfHapmethAssign), C.POINTER(PfHapmethTagcheck),
+                                         C.POINTER(PfHapmethRegions), C.POINTER(PfHapmethStats),
+                                         C.POINTER(PfHapmethDmrStats), C.POINTER(PfHapmethHmmStats),
+                                         C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
+                                         C.POINTER(PfHapmethTagcheckStats), C.POINTER(PfHapmethRegionsStats)]
+    L.pf_regions_load.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(vp)]
+    L.pf_regions_contig.argtypes = [vp, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),
+                                    C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_uint64)]
+    L.pf_regions_unknown.argtypes = [vp]
+    L.pf_regions_unknown.restype = C.c_uint64
+    L.pf_region_list_free.argtypes = [vp]
+    L.pf_bh_adjust.argtypes = [vp, vp, C.c_uint64, C.c_uint32, vp]
+    L.pf_write_regions.argtypes = [C.c_char_p, C.POINTER(PfRegionRec), C.c_uint64, C.c_int, C.c_uint32,
+                                   C.POINTER(C.c_uint64)]
     L.pf_tags_new.restype = vp
     L.pf_tags_free.argtypes = [vp]
     L.pf_tags_size.argtypes = [vp]
@@ -502,7 +518,7 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
                   job_windows: int = 0, dmr: Optional[DmrConfig] = None, dmr_max_p: float = 1.0,
                   dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1,
                   assign: Optional[AssignConfig] = None, tag_check=False,
-                  dmr_hmm: Optional[HmmConfig] = None) -> Dict:
+                  dmr_hmm: Optional[HmmConfig] = None, regions: Optional[str] = None) -> Dict:
     """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
@@ -545,8 +561,25 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     the per-CpG threshold; dmr.min_delta_pct then applies to a region's pooled
     difference.  The region file keeps its name and columns and everything
     after it works on these regions.  Adds n_chains and hmm_ms_kernels to the
-    dict (dmr_ms_kernels counts the model's kernels too)."""
+    dict (dmr_ms_kernels counts the model's kernels too).
+    regions: a BED path (`--regions`) makes the caller's regions the source
+    instead: out_prefix + .hapmeth.regions.bed gets one line per region of the
+    BED (pf_write_regions has the columns), no .hapmeth.dmr.bed is written, and
+    dmr (DmrConfig's defaults when None) gives min_cov, min_delta_pct and
+    min_sites; max_gap is not used and dmr_hmm is refused.  dmr_perm, assign
+    and tag_check work on the eligible regions (not split by a dmr_blocks
+    block, min_sites informative CpGs, pooled_p <= dmr_max_p, at most
+    1,000,000 bases); dmr_perm adds reads_h1, reads_h2, perm_p and perm_q, the
+    Benjamini-Hochberg q-value over the run's tested regions.  Adds
+    regions_path, n_regions, n_regions_unknown_contig, n_regions_outside (not
+    wholly inside `region`), n_regions_split, n_tested, n_untested and
+    regions_ms_kernels to the dict, in place of the dmr entries."""
     L = _bind()
+    if regions is not None:
+        if dmr_hmm is not None:
+            raise PomfretError("hapmeth_files: regions gives the regions: it excludes dmr_hmm")
+        if dmr is None:
+            dmr = DmrConfig()
     if dmr_perm and dmr is None:
         raise PomfretError("hapmeth_files: dmr_perm needs dmr")
     if assign is not None and dmr is None:
@@ -568,7 +601,18 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         dst = PfHapmethDmrStats()
         pm = PfHapmethPerm(int(dmr_perm), int(dmr_seed))
         pst = PfHapmethPermStats()
-        if dmr_hmm is not None:
+        if regions is not None:
+            rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
+            am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
+            tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
+            rg = PfHapmethRegions(regions.encode())
+            hst, ast, tst, rst = PfHapmethHmmStats(), PfHapmethAssignStats(), PfHapmethTagcheckStats(), PfHapmethRegionsStats()
+            _check(L.pf_hapmeth_run_regions(C.byref(o), C.byref(d), None, C.byref(pm) if dmr_perm else None,
+                                            C.byref(am) if assign is not None or tag_check else None,
+                                            C.byref(tm) if tag_check else None, C.byref(rg), C.byref(st), C.byref(dst),
+                                            C.byref(hst), C.byref(pst), C.byref(ast), C.byref(tst), C.byref(rst)),
+                   "pf_hapmeth_run_regions")
+        elif dmr_hmm is not None:
             rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
             am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
             tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
@@ -597,8 +641,14 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     res = dict(path=out_prefix + ".hapmeth.bed", n_windows=int(st.n_windows), n_skipped=int(st.n_skipped),
                n_records=int(st.n_records), n_sites=int(st.n_sites), ms_kernels=float(st.ms_kernels))
     if dmr is not None:
-        res.update(dmr_path=out_prefix + ".hapmeth.dmr.bed", n_regions=int(dst.n_regions),
-                   n_informative=int(dst.n_informative), dmr_ms_kernels=float(dst.ms_kernels))
+        if regions is not None:
+            res.update(regions_path=out_prefix + ".hapmeth.regions.bed", n_regions=int(rst.n_regions),
+                       n_regions_unknown_contig=int(rst.n_unknown_contig), n_regions_outside=int(rst.n_outside),
+                       n_regions_split=int(rst.n_split), n_tested=int(rst.n_tested), n_untested=int(rst.n_untested),
+                       regions_ms_kernels=float(rst.ms_kernels))
+        else:
+            res.update(dmr_path=out_prefix + ".hapmeth.dmr.bed", n_regions=int(dst.n_regions),
+                       n_informative=int(dst.n_informative), dmr_ms_kernels=float(dst.ms_kernels))
         if dmr_hmm is not None:
             res.update(n_chains=int(hst.n_chains), hmm_ms_kernels=float(hst.ms_kernels))
         if dmr_perm:
@@ -680,6 +730,66 @@ def write_dmr_perm(path: str, chrom: str, dmr: Dict, perm: Dict, max_p: float = 
                hits.ctypes.data_as(u32p), stat.ctypes.data_as(u32p), 0.0)
     _check(L.pf_write_dmr_perm(path.encode(), chrom.encode(), C.byref(d), C.byref(p), float(max_p), int(bool(header))),
            "pf_write_dmr_perm")
+
+
+def regions_load(bed: str, names) -> Dict:
+    """The regions of a `--regions` BED for the contigs `names`
+    (pf_regions_load, host only; include/pomfret_amd.h has the format):
+    dict(contigs=[dict(start, end, name) per contig of names, each stably
+    sorted by (start, end)], n_unknown_contig)."""
+    L = _bind()
+    arr = (C.c_char_p * max(len(names), 1))(*[n.encode() for n in names])
+    h = C.c_void_p()
+    _check(L.pf_regions_load(bed.encode(), len(names), arr, C.byref(h)), "pf_regions_load")
+    try:
+        out = []
+        for c in range(len(names)):
+            s, e = C.POINTER(C.c_uint32)(), C.POINTER(C.c_uint32)()
+            nm, n = C.POINTER(C.c_char_p)(), C.c_uint64()
+            _check(L.pf_regions_contig(h, c, C.byref(s), C.byref(e), C.byref(nm), C.byref(n)), "pf_regions_contig")
+            k = int(n.value)
+            out.append(dict(start=[int(s[i]) for i in range(k)], end=[int(e[i]) for i in range(k)],
+                            name=[nm[i].decode() for i in range(k)]))
+        return dict(contigs=out, n_unknown_contig=int(L.pf_regions_unknown(h)))
+    finally:
+        L.pf_region_list_free(h)
+
+
+def bh_adjust(hits, tested, n_perm: int) -> np.ndarray:
+    """Benjamini-Hochberg q-values of the tested entries from the permutation
+    test's hits (pf_bh_adjust, host only): p = (hits + 1) / (n_perm + 1); NaN
+    for an untested entry."""
+    L = _bind()
+    h = np.ascontiguousarray(hits, np.uint32).ravel()
+    t = np.ascontiguousarray(tested, np.uint8).ravel()
+    if h.size != t.size:
+        raise PomfretError("bh_adjust: hits and tested differ in length")
+    q = np.zeros(max(h.size, 1), np.float64)
+    _check(L.pf_bh_adjust(h.ctypes.data, t.ctypes.data, h.size, int(n_perm), q.ctypes.data), "pf_bh_adjust")
+    return q[:h.size]
+
+
+def write_regions(path: str, recs, perm: bool = False, n_perm: int = 0) -> int:
+    """{prefix}.hapmeth.regions.bed from records (pf_write_regions, host only).
+    recs: dicts of chrom, start, end, name, n_cpg, n_sites, n_pos, n_neg, sum
+    [4], evidence, and optionally split (bool) and test = (reads_h1, reads_h2,
+    hits, status) for a region the second pass took.  perm: the four
+    permutation columns as well.  Returns the records with a numeric perm_p."""
+    L = _bind()
+    arr = (PfRegionRec * max(len(recs), 1))()
+    for k, r in enumerate(recs):
+        x = arr[k]
+        x.chrom, x.name, x.start, x.end = r["chrom"].encode(), r["name"].encode(), int(r["start"]), int(r["end"])
+        x.s.n_cpg, x.s.n_sites, x.s.n_pos, x.s.n_neg = int(r["n_cpg"]), int(r["n_sites"]), int(r["n_pos"]), int(r["n_neg"])
+        for j in range(4):
+            x.s.sum[j] = int(r["sum"][j])
+        x.s.evidence = int(r["evidence"])
+        x.flags = (REGION_SPLIT if r.get("split") else 0) | (REGION_ELIGIBLE if r.get("test") is not None else 0)
+        if r.get("test") is not None:
+            x.reads[0], x.reads[1], x.hits, x.status = (int(v) for v in r["test"])
+    n = C.c_uint64()
+    _check(L.pf_write_regions(path.encode(), arr, len(recs), int(bool(perm)), int(n_perm), C.byref(n)), "pf_write_regions")
+    return int(n.value)
 
 
 def write_assign(path: str, chrom: str, res: Optional[Dict], win_start, win_end, qnames, rec_of_read=None,
