@@ -59,9 +59,10 @@
 #define PF_IO_SITES 72            /* u64 site slots the windows need (scan)  */
 
 /* K0's fields of one record, one 128-byte row per wave slot (slots in the
- * order[] order, longest reads first), so that a wave starts its record with
- * one coalesced load instead of one cache line per field array at a random
- * record index (round 4). */
+ * order[] order, longest reads first), so that a wave finds its record in
+ * two cache lines instead of one per field array at a random record index
+ * (round 4).  The slot is uniform across the wave and the row is read-only
+ * during the launch: K0 reads each field by a scalar load where it uses it. */
 struct pf_k0_hdr {
     uint64_t mm_off, ml_off, seq_off, cig_off, stage_off, scr_off;   /* words 0-11 */
     uint32_t mm_len, ml_len, ncig, stage_len;                        /* 12-15 */
@@ -77,7 +78,8 @@ struct pf_load_dev {
     uint32_t min_mapq, min_len;
     uint32_t lo, hi;                 /* uint8_t in the reference (799) */
     uint32_t force_seq;              /* test override: every record through the sequential path */
-    uint32_t diag;                   /* measurement only (PF_K0_DIAG): 1 = trigger placement reads no SEQ word */
+    uint32_t diag;                   /* measurement only (PF_K0_DIAG): 4 / 2 / 5 / 3 stop after a phase; 1 = trigger
+                                        placement reads no SEQ word (builds with -DPF_K0_DIAG1=1 only) */
     const uint32_t *order;           /* [n_recs] record of each wave slot: longest reads first */
     const pf_k0_hdr *hdr;            /* [n_recs] K0's fields of each wave slot's record */
     const uint32_t *rec_win;         /* [n_recs] window of each record */

@@ -56,7 +56,7 @@ DEV unsigned long long k0_now() {
     return t;
 }
 #define K0_STAMP(i) do { const unsigned long long t_ = k0_now(); \
-    if (d.ctr && lane == 0) atomicAdd(&d.ctr[8 + (i)], t_ - k0_t); k0_t = t_; } while (0)
+    if (d->ctr && lane == 0) atomicAdd(&d->ctr[8 + (i)], t_ - k0_t); k0_t = t_; } while (0)
 #define K0_T0 unsigned long long k0_t = k0_now()
 #else
 #define K0_STAMP(i) do { } while (0)
@@ -127,6 +127,17 @@ DEV unsigned long long k0_now() {
 #ifndef PF_K0_EMITDPP
 #define PF_K0_EMITDPP 1
 #endif
+// PF_K0_DIAG=1 (measurement only: the trigger placement reads no SEQ word)
+// is compiled in on request alone: the test sat in the SEQ pass's inner loop
+// and held a VGPR and an SGPR pair across it in every build
+#ifndef PF_K0_DIAG1
+#define PF_K0_DIAG1 0
+#endif
+#if PF_K0_DIAG1
+#define K0_DIAG1(d) ((d)->diag == 1u)
+#else
+#define K0_DIAG1(d) false
+#endif
 #ifndef PF_K0_WPE
 #define PF_K0_WPE 8                        // pf_k0_load's waves per SIMD (register budget: 512 / WPE VGPRs)
 #endif
@@ -139,6 +150,24 @@ DEV uint32_t below_cnt(uint64_t b) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u));
 }
 DEV uint32_t rdl(uint32_t x, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)x, (int)l); }
+
+// The kernel's argument block and a record's header row are wave-uniform and
+// read-only for the whole launch, so K0 reads their fields where it uses
+// them, by scalar loads (the constant address space: s_load whatever stores
+// lie between).  Loaded once at the kernel's entry they were live across
+// every phase: the compiler parked them in VGPR lanes (v_writelane) and
+// fetched them back one v_readlane at a time.  k0_late() at a phase boundary
+// is an identity the compiler cannot see through, so the loads behind it
+// stay behind it.  Only loads go through these pointers.
+#define K0_CONST __attribute__((address_space(4)))
+typedef const K0_CONST pf_load_dev *K0Args;
+typedef const K0_CONST pf_k0_hdr *K0HdrP;
+DEV K0Args k0_args() { return (K0Args)__builtin_amdgcn_kernarg_segment_ptr(); }
+template <typename P>
+DEV P k0_late(P p) {
+    asm volatile("" : "+s"(p));
+    return p;
+}
 
 DEV void wsync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -692,7 +721,7 @@ DEV uint32_t u16_at(uint4 q, uint32_t e) {
 DEV uint64_t valid_nibbles(uint32_t nv) { return nv >= 16 ? 0x1111111111111111ull : ((1ull << (4 * nv)) - 1) & 0x1111111111111111ull; }
 
 template <typename TP>
-DEV uint32_t k0_seq_pass(const pf_load_dev &d, K0W &L, const uint8_t *seq, uint32_t len, bool rev, const K0Tgt &t,
+DEV uint32_t k0_seq_pass(K0Args d, K0W &L, const uint8_t *seq, uint32_t len, bool rev, const K0Tgt &t,
                          TP TB, uint32_t lane, bool &implicit, uint32_t &tb_off) {
     // Blocks of 1024 16-base words (16384 bases), read by 8 coalesced
     // wave-instructions of 1 KiB (lane L holds words 2L, 2L+1 of each 128-word
@@ -716,11 +745,14 @@ DEV uint32_t k0_seq_pass(const pf_load_dev &d, K0W &L, const uint8_t *seq, uint3
     for (uint32_t bb = 0; bb < nblk && ti < nd; bb++) {
         const uint32_t b = rev ? nblk - 1 - bb : bb;
         uint4 v[ROWS];
+        // the lane's words left in the read, once per block: each row's "past
+        // the read?" test is then a compare with a constant
+        const uint32_t w0 = b * BW + 2 * lane;
+        const int32_t left = (int32_t)(nwords - w0);
+        const uint4 *rowp = sq4 + (w0 >> 1);
 #pragma unroll
-        for (uint32_t i = 0; i < ROWS; i++) {
-            const uint32_t w = b * BW + i * RW + 2 * lane;
-            v[i] = w < nwords ? sq4[w >> 1] : make_uint4(0, 0, 0, 0);
-        }
+        for (uint32_t i = 0; i < ROWS; i++)
+            v[i] = (int32_t)(i * RW) < left ? rowp[i * (RW / 2)] : make_uint4(0, 0, 0, 0);
         uint32_t pref[ROWS];
         uint32_t run = 0;
         // target counts per lane (word pair) of two rows at a time, one wave
@@ -805,7 +837,7 @@ DEV uint32_t k0_seq_pass(const pf_load_dev &d, K0W &L, const uint8_t *seq, uint3
         wsync();
         // PF_K0_DIAG=5 (measurement only): the count and the trigger-range
         // search without the placement
-        for (uint32_t j0 = ti; j0 < (d.diag == 5u ? ti : tend); j0 += 64) {
+        for (uint32_t j0 = ti; j0 < (d->diag == 5u ? ti : tend); j0 += 64) {
             const uint32_t j = j0 + lane;
             const bool act = j < tend;
             uint32_t e = 0, i = 8, Lw = 0, hw = 0, k = 0;
@@ -851,7 +883,7 @@ DEV uint32_t k0_seq_pass(const pf_load_dev &d, K0W &L, const uint8_t *seq, uint3
                 nv = sq2[wn];
             }
             if (act) {
-                const uint64_t xw = d.diag == 1u ? 0x2222222222222222ull : nibswap(((uint64_t)xv.y << 32) | xv.x);
+                const uint64_t xw = K0_DIAG1(d) ? 0x2222222222222222ull : nibswap(((uint64_t)xv.y << 32) | xv.x);
                 const uint64_t xn = nibswap(((uint64_t)nv.y << 32) | nv.x);
 #elif PF_K0_NBRARE
             // The trigger's word comes from the registers of the lane that
@@ -873,7 +905,7 @@ DEV uint32_t k0_seq_pass(const pf_load_dev &d, K0W &L, const uint8_t *seq, uint3
                 }
             }
             const uint32_t w = b * BW + i * RW + 2 * Lw + hw;
-            const uint64_t xw = d.diag == 1u ? 0x2222222222222222ull : nibswap(((uint64_t)x1 << 32) | x0);
+            const uint64_t xw = K0_DIAG1(d) ? 0x2222222222222222ull : nibswap(((uint64_t)x1 << 32) | x0);
             const uint32_t bi = act ? sel_nibble(zero_nibbles(xw ^ pat), k) : 0u;
             // The context base: inside the word, or -- for the word's last base
             // (forward) / first base (reverse) -- the neighbour word's first /
@@ -963,7 +995,7 @@ DEV uint32_t k0_seq_pass(const pf_load_dev &d, K0W &L, const uint8_t *seq, uint3
             }
             if (act) {
                 const uint32_t w = b * BW + i * RW + 2 * Lw + hw;
-                const uint64_t xw = d.diag == 1u ? 0x2222222222222222ull : nibswap(((uint64_t)x1 << 32) | x0);
+                const uint64_t xw = K0_DIAG1(d) ? 0x2222222222222222ull : nibswap(((uint64_t)x1 << 32) | x0);
                 const uint64_t xn = nibswap(((uint64_t)n1 << 32) | n0);
 #endif
 #if !PF_K0_NBRARE || PF_K0_SEQ_REREAD
@@ -982,7 +1014,7 @@ DEV uint32_t k0_seq_pass(const pf_load_dev &d, K0W &L, const uint8_t *seq, uint3
 #endif
                     if (ctx) {
                         const uint32_t q = e >> 24;
-                        key = (p << 2) | (q < d.lo ? 1u : q >= d.hi ? 0u : 2u);
+                        key = (p << 2) | (q < d->lo ? 1u : q >= d->hi ? 0u : 2u);
                     } else imp = true;
                 }
             }
@@ -1034,9 +1066,11 @@ DEV void k0_emit_one(K0Out &o, uint32_t v, uint32_t cat, bool implicit) {
         return;
     }
     if (MODE) { o.pos[o.n] = v; o.cat[o.n] = (uint8_t)cat; }
-    if (o.n == 0) o.first = v;
-    else if (v < o.last) o.sorted = 0;
-    if (v >= (1u << 29)) o.lim = 1;
+    // selects, not branches: two stores under exclusive conditions became one
+    // store to a run-time index of a private pair (8 bytes of scratch per lane)
+    o.first = o.n == 0 ? v : o.first;
+    o.sorted = (o.n != 0 && v < o.last) ? 0u : o.sorted;
+    o.lim = v >= (1u << 29) ? 1u : o.lim;
     o.last = v;
     o.n++;
 }
@@ -1050,7 +1084,7 @@ DEV void k0_bcast(K0Out &o, const K0Out &s) {
 // `imp` marking implicit calls): parallel unless one repeats the previous
 // push's position, then lane 0 replays them through k0_emit_one.
 template <int MODE>
-DEV void k0_emit_lanes(const pf_load_dev &d, K0Out &o, bool keep, uint32_t v, uint32_t cat, bool imp,
+DEV void k0_emit_lanes(K0Args d, K0Out &o, bool keep, uint32_t v, uint32_t cat, bool imp,
                        uint32_t lane, uint32_t *sv, uint8_t *sc) {
     const uint64_t bk = __ballot(keep);
     if (!bk) return;
@@ -1076,7 +1110,7 @@ DEV void k0_emit_lanes(const pf_load_dev &d, K0Out &o, bool keep, uint32_t v, ui
     // below its predecessor, a position past 2^29
     if (__ballot(keep && ((has_prev && v <= vprev) || v >= (1u << 29)))) {
         if (__ballot(keep && has_prev && v == vprev)) {
-            if (d.ctr && lane == 0) atomicAdd(&d.ctr[PF_K0C_DUPCHUNK], 1ull);
+            if (d->ctr && lane == 0) atomicAdd(&d->ctr[PF_K0C_DUPCHUNK], 1ull);
             if (keep) { sv[idx] = v; sc[idx] = (uint8_t)(cat | (imp ? 0x80u : 0u)); }
             wsync();
             K0Out s = o;
@@ -1182,7 +1216,7 @@ DEV uint32_t k0_tlb(TP TB, uint32_t n, uint32_t x) {
 // Explicit triggers with p <= a_end and CpGs in [a_cur, a_end) that the
 // reference's scan visits, merged in push order, then emitted.
 template <int MODE, typename TP>
-DEV_COLD void k0_chunk_implicit(const pf_load_dev &d, K0W &L, uint32_t nv, uint32_t c0, uint32_t a_cur, uint32_t a_end,
+DEV_COLD void k0_chunk_implicit(K0Args d, K0W &L, uint32_t nv, uint32_t c0, uint32_t a_cur, uint32_t a_end,
                            uint32_t i_ref, uint32_t cgoffset, bool rev, TP TB, uint32_t nT, uint32_t &tc,
                            const uint8_t *seq, uint32_t len, uint32_t lane, K0Out &o) {
     K0Merge &M = L.u.mg;
@@ -1290,7 +1324,7 @@ DEV uint32_t k0_refc(uint32_t c) {
 }
 
 template <int MODE, typename TP>
-DEV bool k0_walk(const pf_load_dev &d, K0W &L, const uint32_t *cig, uint32_t ncig, uint32_t qs, bool rev, TP TB,
+DEV bool k0_walk(K0Args d, K0W &L, const uint32_t *cig, uint32_t ncig, uint32_t qs, bool rev, TP TB,
                  uint32_t nT, const uint8_t *seq, uint32_t len, bool implicit, uint32_t lane, K0Out &o,
                  uint32_t &racc) {
     const uint32_t cgoffset = rev ? 0xFFFFFFFFu : 0u;
@@ -1403,27 +1437,9 @@ DEV bool k0_walk(const pf_load_dev &d, K0W &L, const uint32_t *cig, uint32_t nci
     return true;
 }
 
-// a record's fields, read from its wave slot's row (pf_k0_hdr) with one
-// coalesced load and moved to scalar registers
-struct K0Rec {
-    uint32_t r, len, flag, mapq, pos, win, mlen, mln, ncig, slen, scr_len;
-    float de;
-    uint64_t mm_off, ml_off, seq_off, cig_off, s_lo, scr_off;
-};
-DEV K0Rec k0_rec(const pf_load_dev &d, uint32_t slot, uint32_t lane) {
-    const uint32_t *hw = reinterpret_cast<const uint32_t *>(d.hdr + slot);
-    const uint32_t v = hw[lane & 31u];
-    auto w32 = [&](uint32_t k) { return rdl(v, k); };
-    auto w64 = [&](uint32_t k) { return ((uint64_t)rdl(v, k + 1) << 32) | rdl(v, k); };
-    K0Rec R;
-    R.mm_off = w64(0); R.ml_off = w64(2); R.seq_off = w64(4); R.cig_off = w64(6); R.s_lo = w64(8); R.scr_off = w64(10);
-    R.mlen = w32(12); R.mln = w32(13); R.ncig = w32(14); R.slen = w32(15);
-    R.scr_len = w32(16); R.len = w32(17); R.pos = w32(18); R.r = w32(19);
-    R.de = __uint_as_float(w32(20)); R.win = w32(21);
-    const uint32_t fm = w32(22);
-    R.flag = fm & 0xFFFFu; R.mapq = fm >> 16;
-    return R;
-}
+// a record's fields: its wave slot's row (pf_k0_hdr), read by scalar loads
+// where each phase needs them (the slot is uniform across the wave)
+DEV K0HdrP k0_rec(K0Args d, uint32_t slot) { return (K0HdrP)(d->hdr + slot); }
 
 // Several C m entries (a duplex-style tag, or C+m twice): every entry's rank
 // list (the same C's counted: the ranks compare), each call's ML value in its
@@ -1436,20 +1452,20 @@ DEV K0Rec k0_rec(const pf_load_dev &d, uint32_t slot, uint32_t lane) {
 // TB receives the merged list in the single-entry layout.  Rare (no config
 // has such tags): one wave, binary searches per call.
 template <typename TP>
-DEV bool k0_merge_targets(const pf_load_dev &d, K0W &L, const K0Tgts &T, uint32_t N, bool rev, TP TB,
+DEV bool k0_merge_targets(K0Args d, K0W &L, const K0Tgts &T, uint32_t N, bool rev, TP TB,
                           const uint32_t *gw, const uint8_t *mmg, uint32_t mis, const uint8_t *ml, uint32_t mln,
                           uint32_t lane, uint32_t &nd_out, bool &past, bool &ovf) {
     nd_out = 0;
     ovf = false;
     unsigned long long t0 = 0;
-    if (lane == 0) t0 = atomicAdd(d.stage_ctr, 2ull * N);
-    const uint64_t cb = d.stage_off[d.n_recs] + (((uint64_t)uni((uint32_t)(t0 >> 32)) << 32) | uni((uint32_t)t0));
-    if (cb + 2ull * N > d.stage_cap) {
-        if (lane == 0) atomicOr(d.status, PF_ST_STAGE_OVF);
+    if (lane == 0) t0 = atomicAdd(d->stage_ctr, 2ull * N);
+    const uint64_t cb = d->stage_off[d->n_recs] + (((uint64_t)uni((uint32_t)(t0 >> 32)) << 32) | uni((uint32_t)t0));
+    if (cb + 2ull * N > d->stage_cap) {
+        if (lane == 0) atomicOr(d->status, PF_ST_STAGE_OVF);
         ovf = true;
         return false;
     }
-    uint32_t *tmp = d.stage_pos + cb, *mrg = tmp + N;
+    uint32_t *tmp = d->stage_pos + cb, *mrg = tmp + N;
     k0_dw_table(L.u.mg.mV, lane);
     wsync();
     bool pst = false;
@@ -1520,7 +1536,7 @@ DEV bool k0_merge_targets(const pf_load_dev &d, K0W &L, const K0Tgts &T, uint32_
 }
 
 template <bool MULTI, typename TP>
-DEV void k0_record(const pf_load_dev &d, K0W &L, const K0Rec &R, uint32_t lane, TP TB, uint32_t cap, const K0Tgts &T,
+DEV void k0_record(K0Args d, K0W &L, K0HdrP h, uint32_t lane, TP TB, uint32_t cap, const K0Tgts &T,
                    bool okm) {
     K0Tgt t = T.t0;
     bool multi = false;
@@ -1529,15 +1545,10 @@ DEV void k0_record(const pf_load_dev &d, K0W &L, const K0Rec &R, uint32_t lane, 
         multi = T.n > 1;
         for (uint32_t e = 1; e < T.n; e++) ndsum += k0_tgt_get(T, e).nd;
     }
-    const uint32_t r = R.r;
-    const uint32_t len = R.len;
-    const bool rev = (R.flag & 16u) != 0;
-    const uint8_t *mmg = d.mm + R.mm_off;
-    const uint8_t *ml = d.ml + R.ml_off;
-    const uint32_t mln = R.mln;
-    const uint8_t *seq = d.seq + R.seq_off;
-    const uint32_t *cig = d.cigar + R.cig_off;
-    const uint32_t ncig = R.ncig;
+    const bool rev = (h->flag_mapq & 16u) != 0;
+    const uint8_t *mmg = d->mm + h->mm_off;
+    const uint8_t *ml = d->ml + h->ml_off;
+    const uint32_t mln = h->ml_len;
 
     bool okmm = okm;
     uint32_t nT = 0, mlq0 = 0xFFFFFFFFu, mlq1 = 0xFFFFFFFFu;
@@ -1569,13 +1580,13 @@ DEV void k0_record(const pf_load_dev &d, K0W &L, const K0Rec &R, uint32_t lane, 
     bool past = false;
     if constexpr (MULTI) {
         if (okmm && multi) {
-            if (d.ctr && lane == 0) atomicAdd(&d.ctr[PF_K0C_MULTICM], 1ull);
+            if (d->ctr && lane == 0) atomicAdd(&d->ctr[PF_K0C_MULTICM], 1ull);
             bool ovf = false;
             uint32_t ndm = 0;
             const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(mmg) & 3u);
             okmm = k0_merge_targets(d, L, T, ndsum, rev, TB, reinterpret_cast<const uint32_t *>(mmg - mis), mmg, mis,
                                     ml, mln, lane, ndm, past, ovf);
-            if (ovf) { if (lane == 0) d.rec_n[r] = PF_NONE; return; }
+            if (ovf) { if (lane == 0) d->rec_n[h->rec] = PF_NONE; return; }
             t.nd = ndm;
         }
     }
@@ -1593,17 +1604,29 @@ DEV void k0_record(const pf_load_dev &d, K0W &L, const K0Rec &R, uint32_t lane, 
         wsync();
     }
     K0_STAMP(0);
-    if (d.diag == 2u) { if (lane == 0) d.rec_n[r] = PF_NONE; return; }
+    // ---- SEQ pass: its fields of the arguments and of the row from here
+    d = k0_late(d);
+    h = k0_late(h);
+    if (d->diag == 2u) { if (lane == 0) d->rec_n[h->rec] = PF_NONE; return; }
+    const uint8_t *seq = d->seq + h->seq_off;
+    const uint32_t len = h->l_qseq;
     uint32_t tb_off = 0;
     if (okmm && t.nd && !past) nT = k0_seq_pass(d, L, seq, len, rev, t, TB, lane, implicit, tb_off);
     TB = TB + uni(tb_off);                            // the compacted triggers start here
     K0_STAMP(1);
-    if (d.diag == 3u || d.diag == 5u) { if (lane == 0) d.rec_n[r] = PF_NONE; return; }
-    if (!okmm && d.ctr && lane == 0) atomicAdd(&d.ctr[PF_K0C_BADMM], 1ull);
+    // ---- CIGAR walk: the record's late fields are read here, not carried
+    // across the MM and SEQ phases
+    d = k0_late(d);
+    h = k0_late(h);
+    const uint32_t r = h->rec;
+    if (d->diag == 3u || d->diag == 5u) { if (lane == 0) d->rec_n[r] = PF_NONE; return; }
+    const uint32_t ncig = h->ncig;
+    const uint32_t *cig = d->cigar + h->cig_off;
+    if (!okmm && d->ctr && lane == 0) atomicAdd(&d->ctr[PF_K0C_BADMM], 1ull);
     nT = uni(nT);
 
     if (ncig == 0 || nT == 0) {                       // get_mod_poss_on_ref returns 0: read dropped
-        if (lane == 0) d.rec_n[r] = PF_NONE;
+        if (lane == 0) d->rec_n[r] = PF_NONE;
         return;
     }
     // The record's call slice in the staging arena: its static slice (the
@@ -1613,30 +1636,29 @@ DEV void k0_record(const pf_load_dev &d, K0W &L, const K0Rec &R, uint32_t lane, 
     // the arena's tail.  A full tail flags the batch: the bump pointer keeps
     // counting, so it ends at the size the run needs, and the host grows the
     // arena to that and re-runs.
-    const uint64_t s_lo = R.s_lo, s_hi = R.s_lo + R.slen;
-    uint64_t cb = s_lo;
-    if (implicit || (uint64_t)nT > s_hi - s_lo) {
+    uint64_t cb = h->stage_off;
+    if (implicit || nT > h->stage_len) {
         const uint64_t need = (uint64_t)nT + (uint64_t)(len + 1) / 2;
         unsigned long long t = 0;
-        if (lane == 0) t = atomicAdd(d.stage_ctr, (unsigned long long)need);
-        cb = d.stage_off[d.n_recs] + (((uint64_t)uni((uint32_t)(t >> 32)) << 32) | uni((uint32_t)t));
-        if (cb + need > d.stage_cap) {
-            if (lane == 0) { atomicOr(d.status, PF_ST_STAGE_OVF); d.rec_n[r] = PF_NONE; }
+        if (lane == 0) t = atomicAdd(d->stage_ctr, (unsigned long long)need);
+        cb = d->stage_off[d->n_recs] + (((uint64_t)uni((uint32_t)(t >> 32)) << 32) | uni((uint32_t)t));
+        if (cb + need > d->stage_cap) {
+            if (lane == 0) { atomicOr(d->status, PF_ST_STAGE_OVF); d->rec_n[r] = PF_NONE; }
             return;
         }
     }
     K0Out o;
     o.n = 0; o.first = 0; o.last = 0; o.sorted = 1; o.lim = 0;
-    o.pos = d.stage_pos + cb;
-    o.cat = d.stage_cat + cb;
-    if (implicit && d.ctr && lane == 0) atomicAdd(&d.ctr[PF_K0C_IMPLICIT], 1ull);
+    o.pos = d->stage_pos + cb;
+    o.cat = d->stage_cat + cb;
+    if (implicit && d->ctr && lane == 0) atomicAdd(&d->ctr[PF_K0C_IMPLICIT], 1ull);
 
-    const uint32_t qs = R.pos;
+    const uint32_t qs = h->pos;
     const bool stale = (cig[0] & 15u) == 4u && (TB[nT - 1] >> 2) <= (cig[0] >> 4);
     bool fatal = false, walked = false;
     uint32_t racc = 0;                                // this lane's share of bam_endpos (the wave walk)
-    if (stale || d.force_seq) {
-        if (d.ctr && lane == 0) atomicAdd(&d.ctr[PF_K0C_SEQPATH], 1ull);
+    if (stale || d->force_seq) {
+        if (d->ctr && lane == 0) atomicAdd(&d->ctr[PF_K0C_SEQPATH], 1ull);
         K0Out s = o;
         bool f = false;
         if (lane == 0) k0_walk_seq<1>(cig, ncig, qs, rev, TB, nT, implicit ? seq : nullptr, len, s, f);
@@ -1648,13 +1670,13 @@ DEV void k0_record(const pf_load_dev &d, K0W &L, const K0Rec &R, uint32_t lane, 
     }
     K0_STAMP(2);
     if (fatal) {
-        if (lane == 0) { atomicOr(d.status, PF_ST_FATAL_CIGAR); d.rec_n[r] = PF_NONE; }
+        if (lane == 0) { atomicOr(d->status, PF_ST_FATAL_CIGAR); d->rec_n[r] = PF_NONE; }
         return;
     }
-    if (o.lim && lane == 0) atomicOr(d.status, PF_ST_POS_LIMIT);
+    if (o.lim && lane == 0) atomicOr(d->status, PF_ST_POS_LIMIT);
     // ---- the calls in (pos, cat) order, then the record's scalars
     if (!o.sorted && o.n > 1) {
-        if (d.ctr && lane == 0) atomicAdd(&d.ctr[PF_K0C_UNSORTED], 1ull);
+        if (d->ctr && lane == 0) atomicAdd(&d->ctr[PF_K0C_UNSORTED], 1ull);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         if (lane == 0) {                              // insertion sort by (pos, cat): rare, short
             for (uint32_t i = 1; i < o.n; i++) {
@@ -1680,87 +1702,88 @@ DEV void k0_record(const pf_load_dev &d, K0W &L, const K0Rec &R, uint32_t lane, 
     if (lane < 8) {                                   // the record's row: one 32-byte store
         const uint32_t v = lane == 0 ? qs : lane == 1 ? qs + rlen : lane == 2 ? o.first : lane == 3 ? o.last
                          : lane == 4 ? (uint32_t)cb : lane == 5 ? (uint32_t)(cb >> 32) : 0u;
-        d.rec_out[8ull * r + lane] = v;
+        d->rec_out[8ull * r + lane] = v;
     }
     if (lane == 63) {
-        d.rec_n[r] = o.n;
-        const uint32_t w = R.win;
-        atomicAdd(&d.win_kept[w], 1u);
-        atomicAdd(&d.win_calls[w], o.n);
+        d->rec_n[r] = o.n;
+        const uint32_t w = h->rec_win;
+        atomicAdd(&d->win_kept[w], 1u);
+        atomicAdd(&d->win_calls[w], o.n);
     }
     K0_STAMP(3);
 }
 
 // a record whose trigger list is past the wave's LDS list: its HBM slice
 template <bool MULTI>
-DEV_HBM void k0_record_hbm(const pf_load_dev &d, K0W &L, const K0Rec &R, uint32_t lane, const K0Tgts &T, bool okm) {
-    k0_record<MULTI>(d, L, R, lane, d.scr + R.scr_off, R.scr_len, T, okm);
+DEV_HBM void k0_record_hbm(K0Args d, K0W &L, K0HdrP h, uint32_t lane, const K0Tgts &T, bool okm) {
+    k0_record<MULTI>(d, L, h, lane, d->scr + h->scr_off, h->scr_len, T, okm);
 }
 
 // One record on the wave: filters, the MM entries, the rest.  The main pass
 // hands a record with several C m entries to pf_k0_multi (rare; its merge
 // would cost the common path registers) and leaves its rec_n to it.
 template <bool MULTI>
-DEV void k0_one(const pf_load_dev &d, K0W &L, uint32_t slot, uint32_t lane) {
-    const K0Rec R = k0_rec(d, slot, lane);
-    const uint32_t r = R.r;
+DEV void k0_one(K0Args d, K0W &L, uint32_t slot, uint32_t lane) {
+    const K0HdrP h = k0_rec(d, slot);
     // filters (1079-1085)
-    const uint32_t flag = R.flag;
-    const bool drop = (flag & 4u) || (flag & 256u) || (flag & 2048u) || R.mapq < d.min_mapq ||
-                      R.len < 2u || R.len < d.min_len || (double)R.de > 0.1;
+    const uint32_t fm = h->flag_mapq, flag = fm & 0xFFFFu, len = h->l_qseq;
+    const bool drop = (flag & 4u) || (flag & 256u) || (flag & 2048u) || (fm >> 16) < d->min_mapq ||
+                      len < 2u || len < d->min_len || (double)h->de > 0.1;
     if (drop) {
-        if (lane == 0) d.rec_n[r] = PF_NONE;
+        if (lane == 0) d->rec_n[h->rec] = PF_NONE;
         return;
     }
     // PF_K0_DIAG=4/2/3 (measurement only, results invalid): stop after the
     // filters / the MM phase / the SEQ pass, so that phase costs are kernel-time
     // differences (the s_memtime build's counter atomics distort them)
-    if (d.diag == 4u) { if (lane == 0) d.rec_n[r] = PF_NONE; return; }
+    if (d->diag == 4u) { if (lane == 0) d->rec_n[h->rec] = PF_NONE; return; }
     // The tag's entries first: the C m entries' skip counts decide where the
     // trigger list lives -- the wave's LDS list when it fits (640), else the
     // record's HBM slice, which the upload sizes from the ML length (an upper
     // bound: dorado's h + m entries make it twice the m list, so round 2 sent
     // ~45 % of 60x records to HBM, with every rank, key and binary search of
     // their trigger lists an L2 round trip).
-    const uint8_t *mmg = d.mm + R.mm_off;
+    const uint8_t *mmg = d->mm + h->mm_off;
     const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(mmg) & 3u);
     K0Tgts T;
     T.xt = L.opE;                                     // free until the CIGAR walk (PF_K0_TW x 7 <= 64 words)
-    const bool okm = k0_mm_entries<MULTI>(reinterpret_cast<const uint32_t *>(mmg - mis), mmg, mis, R.mlen, R.mln, lane, T);
+    const bool okm = k0_mm_entries<MULTI>(reinterpret_cast<const uint32_t *>(mmg - mis), mmg, mis, h->mm_len, h->ml_len, lane, T);
     if (T.over) {                                     // more C m entries than this build merges
-        if (lane == 0) { atomicOr(d.status, PF_ST_MM_LIMIT); d.rec_n[r] = PF_NONE; }
+        if (lane == 0) { atomicOr(d->status, PF_ST_MM_LIMIT); d->rec_n[h->rec] = PF_NONE; }
         return;
     }
     if (!MULTI && okm && T.n > 1) {
-        if (lane == 0) d.multi_list[atomicAdd(d.multi_ctr, 1u)] = slot;
+        if (lane == 0) d->multi_list[atomicAdd(d->multi_ctr, 1u)] = slot;
         return;
     }
     uint32_t ndsum = T.t0.nd;
     if constexpr (MULTI)
         for (uint32_t e = 1; e < T.n; e++) ndsum += k0_tgt_get(T, e).nd;
-    if (R.scr_len == 0 || !okm || uni(ndsum) <= (uint32_t)PF_K0_TCAP)
-        k0_record<MULTI>(d, L, R, lane, L.T, (uint32_t)PF_K0_TCAP, T, okm);
-    else k0_record_hbm<MULTI>(d, L, R, lane, T, okm);
+    if (h->scr_len == 0 || !okm || uni(ndsum) <= (uint32_t)PF_K0_TCAP)
+        k0_record<MULTI>(d, L, h, lane, L.T, (uint32_t)PF_K0_TCAP, T, okm);
+    else k0_record_hbm<MULTI>(d, L, h, lane, T, okm);
 }
 
-__global__ __launch_bounds__(PF_K0_WAVES * 64) __attribute__((amdgpu_waves_per_eu(PF_K0_WPE))) void pf_k0_load(pf_load_dev d) {
+__global__ __launch_bounds__(PF_K0_WAVES * 64) __attribute__((amdgpu_waves_per_eu(PF_K0_WPE))) void pf_k0_load(pf_load_dev) {
     __shared__ K0W lds[PF_K0_WAVES];
+    const K0Args d = k0_args();                       // the argument block, read in place
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = uni(threadIdx.x >> 6);
     const uint32_t slot = blockIdx.x * PF_K0_WAVES + wv;
-    if (slot >= d.n_recs) return;
+    if (slot >= d->n_recs) return;
     k0_one<false>(d, lds[wv], slot, lane);
 }
 
 // The records pf_k0_load handed over (several C m entries): one wave each,
 // grid-stride over its list.
-__global__ __launch_bounds__(PF_K0_WAVES * 64) void pf_k0_multi(pf_load_dev d) {
+__global__ __launch_bounds__(PF_K0_WAVES * 64) void pf_k0_multi(pf_load_dev) {
     __shared__ K0W lds[PF_K0_WAVES];
+    const K0Args d = k0_args();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wv = uni(threadIdx.x >> 6);
-    const uint32_t n = *d.multi_ctr;
+    const uint32_t n = *d->multi_ctr;
     for (uint32_t i = blockIdx.x * PF_K0_WAVES + wv; i < n; i += gridDim.x * PF_K0_WAVES)
-        k0_one<true>(d, lds[wv], d.multi_list[i], lane);
+        k0_one<true>(d, lds[wv], d->multi_list[i], lane);
 }
 
 // ---------------------------------------------------------------------------
