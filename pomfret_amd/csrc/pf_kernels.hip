@@ -2416,45 +2416,62 @@ DEV void k3_insert_all(const K3Mem &m, uint32_t S, uint32_t n, uint32_t st, uint
 // tstart+step, ... < tend, accumulated into the exact fp64 sums (no record
 // rows: the sequential fold, needed for 0.05-0.5 % of picks, recomputes its
 // terms with k3_fold_direct).  Returns the push/positive count pair.
+// U slots of the fill (terms tb, tb + step, ...): the slot-list and `sum`
+// loads of all U in flight ahead of the dependent count loads
+template <bool SLDS, bool C8, int U>
+DEV void k3_fill_slots(const K3Mem &m, uint32_t f_lo, uint32_t f_kofs, uint32_t tb, uint32_t tend, uint32_t step,
+                       uint32_t &lcode, double &e0, double &e1) {
+    uint32_t sl[U], cv[U], sv[U];
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const uint32_t t = tb + u * step;
+        const bool ok = t < tend;
+        sl[u] = k3_slot_raw<SLDS>(m, ok ? f_kofs + t : 0u);
+        sv[u] = m.sum[ok ? f_lo + t : 0u];
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const uint32_t t = tb + u * step;
+        const bool ok = t < tend && sl[u] != (SLDS ? 0xFFFFu : PF_NONE);
+        const uint32_t c = k3_cnt_get<C8>(m, ok ? sl[u] : 0u);
+        cv[u] = ok ? c : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+        const uint32_t a0 = cv[u] & 0xffffu, a1 = cv[u] >> 16;
+        // the divisors: the site's hap totals (0 -> a zero reciprocal, so 0/h = 0)
+        const uint32_t h0 = sv[u] & 0xffffu, h1 = sv[u] >> 16;
+        const float q0 = div_u16_y((float)a0, (float)h0, h0 ? __builtin_amdgcn_rcpf((float)h0) : 0.f);
+        const float q1 = div_u16_y((float)a1, (float)h1, h1 ? __builtin_amdgcn_rcpf((float)h1) : 0.f);
+        // push/positive counts (:3505-3509, :3619-3624): pushed = key present
+        // (cv != 0) and hap total != 0; positive = cnt > 0, which implies
+        // pushed.  Both haps packed per u32 half: min(cnt, 1) and
+        // min(total, 1) in one v_pk_min_u16 each.
+        uint32_t posc, hm;
+        asm("v_pk_min_u16 %0, %1, %2" : "=v"(posc) : "v"(cv[u]), "s"(0x00010001u));
+        asm("v_pk_min_u16 %0, %1, %2" : "=v"(hm) : "v"(sv[u]), "s"(0x00010001u));
+        lcode += posc + (cv[u] ? hm : 0u);
+        e0 += (double)q0;
+        e1 += (double)q1;
+    }
+}
+
+// tw: the wave's lowest tstart; longest: the longest tend of the lanes that
+// hold a candidate (both wave-uniform; step: a power of two).  A slot whose
+// terms all lie at or past `longest` adds nothing in any lane (every term is
+// masked to zero), so the wave runs ceil((longest - tw) / step) slots: four at
+// a time, then two and one for what is left.  (A remainder of three as one
+// group of its own makes pf_k3_greedy spill six VGPRs to scratch; single
+// slots for the whole remainder measured 0.05 ms slower: DESIGN.md 8.)
 template <bool SLDS, bool C8 = false>
 DEV uint32_t k3_fill_sums(const K3Mem &m, uint32_t f_lo, uint32_t f_kofs, uint32_t tstart, uint32_t tend,
-                          uint32_t step, double &e0, double &e1) {
+                          uint32_t step, uint32_t tw, uint32_t longest, double &e0, double &e1) {
     uint32_t lcode = 0;
-    for (uint32_t tb = tstart; tb < tend; tb += 4 * step) {
-        uint32_t sl[4], cv[4], sv[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t t = tb + u * step;
-            const bool ok = t < tend;
-            sl[u] = k3_slot_raw<SLDS>(m, ok ? f_kofs + t : 0u);
-            sv[u] = m.sum[ok ? f_lo + t : 0u];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t t = tb + u * step;
-            const bool ok = t < tend && sl[u] != (SLDS ? 0xFFFFu : PF_NONE);
-            const uint32_t c = k3_cnt_get<C8>(m, ok ? sl[u] : 0u);
-            cv[u] = ok ? c : 0u;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const uint32_t a0 = cv[u] & 0xffffu, a1 = cv[u] >> 16;
-            // the divisors: the site's hap totals (0 -> a zero reciprocal, so 0/h = 0)
-            const uint32_t h0 = sv[u] & 0xffffu, h1 = sv[u] >> 16;
-            const float q0 = div_u16_y((float)a0, (float)h0, h0 ? __builtin_amdgcn_rcpf((float)h0) : 0.f);
-            const float q1 = div_u16_y((float)a1, (float)h1, h1 ? __builtin_amdgcn_rcpf((float)h1) : 0.f);
-            // push/positive counts (:3505-3509, :3619-3624): pushed = key present
-            // (cv != 0) and hap total != 0; positive = cnt > 0, which implies
-            // pushed.  Both haps packed per u32 half: min(cnt, 1) and
-            // min(total, 1) in one v_pk_min_u16 each.
-            uint32_t posc, hm;
-            asm("v_pk_min_u16 %0, %1, %2" : "=v"(posc) : "v"(cv[u]), "s"(0x00010001u));
-            asm("v_pk_min_u16 %0, %1, %2" : "=v"(hm) : "v"(sv[u]), "s"(0x00010001u));
-            lcode += posc + (cv[u] ? hm : 0u);
-            e0 += (double)q0;
-            e1 += (double)q1;
-        }
-    }
+    uint32_t left = longest > tw ? (longest - tw + step - 1) >> (31 - __clz(step)) : 0u;
+    uint32_t tb = tstart;
+    for (; left >= 4; left -= 4, tb += 4 * step) k3_fill_slots<SLDS, C8, 4>(m, f_lo, f_kofs, tb, tend, step, lcode, e0, e1);
+    if (left & 2) { k3_fill_slots<SLDS, C8, 2>(m, f_lo, f_kofs, tb, tend, step, lcode, e0, e1); tb += 2 * step; }
+    if (left & 1) k3_fill_slots<SLDS, C8, 1>(m, f_lo, f_kofs, tb, tend, step, lcode, e0, e1);
     return lcode;
 }
 
@@ -2932,7 +2949,11 @@ DEV void k3_greedy_slim(const pf_dev_batch &d, uint32_t w, uint32_t dir, uint32_
             const uint32_t f_len = (uint32_t)__shfl((int)c_len, (int)fc, 64);
             const uint32_t f_kofs = (uint32_t)__shfl((int)c_kofs, (int)fc, 64);
             double x0 = 0.0, x1 = 0.0;
-            const uint32_t lcode = k3_fill_sums<SLDS, C8>(m, f_lo, f_kofs, J, f_len, GS, x0, x1);
+            // the iteration's longest span bounds the slots (c_len is 0 in the lanes >= nc)
+            const uint32_t longest = wave_max_dpp(c_len);
+            K3_COUNT(12, longest);
+            K3_COUNT(13, nc);
+            const uint32_t lcode = k3_fill_sums<SLDS, C8>(m, f_lo, f_kofs, J, f_len, GS, wid * G, longest, x0, x1);
             if (fc < nc) {
                 atomicAdd(&lcp[par * 64 + fc], lcode);
                 atomicAdd(&accd[par * 128 + fc], x0);
@@ -3232,7 +3253,9 @@ DEV void k3_greedy_body(const pf_dev_batch &d, uint32_t w, uint32_t dir, uint32_
             K3_COUNT(13, ncs);
             K3_STAMP(9);
             double x0 = 0.0, x1 = 0.0;
-            lcode = k3_fill_sums<SLDS>(m, f_lo, f_kofs, J, f_len, GS, x0, x1);
+            // the lanes fc >= ncs hold no candidate: no terms, and outside the slot bound
+            const uint32_t f_lenx = fc < ncs ? f_len : 0u;
+            lcode = k3_fill_sums<SLDS>(m, f_lo, f_kofs, J, f_lenx, GS, wid * G, wave_max_dpp(f_lenx), x0, x1);
             K3_STAMP(10);
             // every lane adds into its candidate's totals: integer counts and
             // exact fp64 sums are order-free, and the G same-address lanes of
