@@ -243,6 +243,9 @@ int  pf_batch_read_recs(const pf_dbatch_t *db, uint32_t *rec_of_read, uint32_t n
  * the number of calls or < 0. */
 int64_t pf_batch_debug_calls(pf_dbatch_t *db, uint64_t *call_off, uint32_t *pos, uint8_t *cat,
                              uint32_t *first, uint32_t *last, uint64_t cap);
+/* Parity/debug for K0: runs it and copies every read's reference start and
+ * end (bam_endpos) as K0 wrote them (n >= pf_batch_n_reads). */
+int  pf_batch_debug_spans(pf_dbatch_t *db, uint32_t *start, uint32_t *end, uint32_t n);
 
 /* K0 counters since upload (count pass + every run), out[0..7]: records
  * walked by the sequential path, records whose calls needed a sort, records

@@ -74,6 +74,7 @@ def lib():
         L.pf_batch_read_recs.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.pf_batch_debug_calls.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_uint64]
         L.pf_batch_debug_calls.restype = C.c_int64
+        L.pf_batch_debug_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32]
         L.pf_batch_load_counters.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.pf_batch_debug_recs.argtypes = [C.c_void_p] * 16
         L.pf_bgzf_inflate.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
@@ -625,6 +626,14 @@ class DeviceBatch:
             _check(int(n), "pf_batch_debug_calls")
         R = self.n_reads
         return off[:R + 1], pos[:n], cat[:n], first[:R], last[:R]
+
+    def debug_spans(self):
+        """K0 output: (read_start, read_end) of every read, after a run of the loader."""
+        n = max(self.n_reads, 1)
+        start, end = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        _check(lib().pf_batch_debug_spans(self.handle, start.ctypes.data, end.ctypes.data, n), "pf_batch_debug_spans")
+        R = self.n_reads
+        return start[:R], end[:R]
 
     def load_counters(self) -> dict:
         out = np.zeros(8, np.uint64)

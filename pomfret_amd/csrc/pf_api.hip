@@ -1923,6 +1923,18 @@ extern "C" int64_t pf_batch_debug_calls(pf_dbatch_t *b, uint64_t *call_off, uint
     return (int64_t)b->N;
 }
 
+extern "C" int pf_batch_debug_spans(pf_dbatch_t *b, uint32_t *start, uint32_t *end, uint32_t n) {
+    if (!b || !start || !end) return PF_ERR_ARG;
+    const int rc = run_debug(b, 0);
+    if (rc) return rc;
+    if (b->R > n) return PF_ERR_ARG;
+    if (b->R) {
+        HIPCHK(hipMemcpy(start, b->d.read_start, 4ull * b->R, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(end, b->d.read_end, 4ull * b->R, hipMemcpyDeviceToHost));
+    }
+    return PF_OK;
+}
+
 extern "C" int pf_batch_set_hp(pf_dbatch_t *b, const uint8_t *hp, uint32_t n) {
     if (!b || !b->has_aln || n != b->ld.n_recs || (n && !hp)) return PF_ERR_ARG;
     if (!n) return PF_OK;

@@ -21,7 +21,8 @@
 //     64-entry LDS search and a select-k-th-bit; the CpG context test and the
 //     ML category follow.  Result: the trigger list T (position<<2 | category),
 //     ascending.
-//  3. CIGAR: 64 operations per step (prefix sums of read advance and reference
+//  3. CIGAR: 128 operations per step, two per lane (64 for an implicit-mode
+//     read; prefix sums of read advance and reference
 //     offset); the triggers each op consumes -- the reference's
 //     `while (i_read+length >= next_trigger)` (663) takes every trigger up to
 //     and INCLUDING the op's end -- are mapped 64 at a time by an LDS search
@@ -126,6 +127,18 @@ DEV unsigned long long k0_now() {
 // kept lane
 #ifndef PF_K0_EMITDPP
 #define PF_K0_EMITDPP 1
+#endif
+// SEQ count (rows and tiles): 1 = a pair of rows that starts at or past the
+// read's last word is skipped by a wave-uniform branch (its loads are
+// predicated to zero already; its count, scan and LDS stores are not)
+#ifndef PF_K0_ROWSKIP
+#define PF_K0_ROWSKIP 1
+#endif
+// CIGAR walk (rows and tiles): 1 = the explicit walk takes 128 operations per
+// tile, two per lane, in one table (K0Wide); implicit-canonical reads keep
+// tiles of 64 (their chunks need the merge lists the wide table lies over)
+#ifndef PF_K0_TILE128
+#define PF_K0_TILE128 1
 #endif
 // PF_K0_DIAG=1 (measurement only: the trigger placement reads no SEQ word)
 // is compiled in on request alone: the test sat in the SEQ pass's inner loop
@@ -250,15 +263,28 @@ struct K0Seq {
     uint16_t sb[8 * 64];              // SEQ block: rank base of each (row, word pair)
     uint8_t sc[8 * 64];               //            target count of the pair's first word
 };
+struct K0Wide {                       // phase 3, explicit mode: one tile of 128 operations in one table
+    uint32_t E[128], Off[128];        // ends (~0 from the stop on), reference offsets
+    uint32_t gE[16], sE[4];           // last end of each group of 8, of each 4 groups
+    uint8_t T[128];                   // operation codes
+    uint32_t mV[64];                  // emission spill
+    uint8_t mC[64];
+};
 struct K0W {                          // LDS of one wave (5 KB: 8 waves per SIMD)
     uint32_t T[PF_K0_TCAP];           // ranks, then triggers (p<<2 | cat)
-    uint32_t opE[64], opOff[64], opA[64];
-    uint8_t opT[64];
     union {
-        K0Seq s;                      // phase 2
-        K0Merge mg;                   // phase 3: implicit-mode lists, emission spill
-    } u;
+        struct {
+            uint32_t opE[64], opOff[64], opA[64];
+            uint8_t opT[64];
+            union {
+                K0Seq s;              // phase 2
+                K0Merge mg;           // phase 3: implicit-mode lists, emission spill
+            } u;
+        };
+        K0Wide w;                     // PF_K0_TILE128: the explicit walk's tables lie over all of the above
+    };
 };
+static_assert(sizeof(K0W) == 5120, "K0W: 5 KB per wave, 20,480 B per block");
 
 // emission state, uniform across the wave
 struct K0Out {
@@ -781,6 +807,15 @@ DEV uint32_t k0_seq_pass(K0Args d, K0W &L, const uint8_t *seq, uint32_t len, boo
         };
 #pragma unroll
         for (uint32_t i = 0; i < ROWS; i += 2) {
+#if PF_K0_ROWSKIP
+            // both rows past the read: no targets, and no trigger lands here
+            // (f < btot puts every trigger in a row before this one)
+            if (i * RW >= nwords - b * BW) {
+                pref[i] = run;
+                pref[i + 1] = run;
+                continue;
+            }
+#endif
             uint32_t c0a, c0b;
             const uint32_t ca = count(i, c0a), cb = count(i + 1, c0b);
             L.u.s.sc[i * 64 + lane] = (uint8_t)c0a;
@@ -1437,6 +1472,116 @@ DEV bool k0_walk(K0Args d, K0W &L, const uint32_t *cig, uint32_t ncig, uint32_t 
     return true;
 }
 
+#if PF_K0_TILE128
+// The explicit walk in tiles of 128 operations: lane l takes operations 2l and
+// 2l + 1 (one scan per quantity over the lane sums), and all 128 go into one
+// table, K0Wide.  A trigger's operation is found in three steps of packed LDS
+// reads -- the last ends of the 4 quarters, of the quarter's 4 groups of 8,
+// then the group's 8 ends: 16 compares, as many as a tile of 64 took.
+// Everything else is k0_walk's: the stop and the first fatal operation over
+// the whole tile, bam_endpos over every operation, the trailing tiles.
+template <int MODE, typename TP>
+DEV bool k0_walk128(K0Args d, K0W &L, const uint32_t *cig, uint32_t ncig, uint32_t qs, bool rev, TP TB,
+                    uint32_t nT, uint32_t lane, K0Out &o, uint32_t &racc) {
+    K0Wide &W = L.w;
+    const uint32_t cgoffset = rev ? 0xFFFFFFFFu : 0u;
+    uint32_t a_cur = 0, off_cur = 0, j = 0, tc = 0, i_ref = qs;
+    if ((cig[0] & 15u) == 4u) {                       // prologue (629-652)
+        const uint32_t sclip = cig[0] >> 4;
+        tc = k0_tlb(TB, nT, sclip + 1);
+        if (tc > 0 && (TB[tc - 1] >> 2) == sclip) k0_emit_one<MODE>(o, qs + cgoffset, TB[tc - 1] & 3u, false);
+        i_ref = qs - sclip;
+        a_cur = sclip;
+        j = 1;
+    }
+    bool trunc = false;
+    auto ld_tile = [&](uint32_t t) {                  // past the end: 4u (S), a stop that is never fatal
+        const uint32_t g = t + 2 * lane;
+        return make_uint2(g < ncig ? cig[g] : 4u, g + 1 < ncig ? cig[g + 1] : 4u);
+    };
+    uint2 cn = ld_tile(j);
+    auto next_tile = [&]() { cn = j + 128 < ncig ? ld_tile(j + 128) : make_uint2(4u, 4u); };
+    // the tile's first stop (N, S, past the end; 128: none); false when a
+    // fatal operation comes before it (exit(1) at 776-779)
+    auto first_of = [](uint64_t even, uint64_t odd) {
+        const uint32_t fe = even ? 2u * ((uint32_t)__ffsll((long long)even) - 1) : 128u;
+        const uint32_t fo = odd ? 2u * ((uint32_t)__ffsll((long long)odd) - 1) + 1u : 128u;
+        return min(fe, fo);
+    };
+    auto tile_stop = [&](uint32_t op0, uint32_t op1, uint32_t &fs) {
+        fs = first_of(__ballot(op0 == 3u || op0 == 4u), __ballot(op1 == 3u || op1 == 4u));
+        return first_of(__ballot(op0 > 4u), __ballot(op1 > 4u)) >= fs;
+    };
+    while (j < ncig && !trunc && tc < nT) {
+        const uint2 c = cn;
+        next_tile();
+        racc += k0_refc(c.x) + k0_refc(c.y);
+        const uint32_t op0 = c.x & 15u, op1 = c.y & 15u, ln0 = c.x >> 4, ln1 = c.y >> 4;
+        uint32_t nv;
+        if (!tile_stop(op0, op1, nv)) return false;
+        trunc = nv < 128;
+        const bool v0 = 2 * lane < nv, v1 = 2 * lane + 1 < nv;
+        const uint32_t rl0 = v0 && op0 <= 1u ? ln0 : 0u, rl1 = v1 && op1 <= 1u ? ln1 : 0u;
+        const uint32_t dl0 = !v0 ? 0u : op0 == 2u ? ln0 : op0 == 1u ? 0u - ln0 : 0u;
+        const uint32_t dl1 = !v1 ? 0u : op1 == 2u ? ln1 : op1 == 1u ? 0u - ln1 : 0u;
+        const uint32_t rs = rl0 + rl1, ds = dl0 + dl1;
+        const uint32_t rin = wscan(rs, lane), din = wscan(ds, lane);
+        const uint32_t a0 = a_cur + rin - rs, off0 = off_cur + din - ds;
+        const uint32_t oe1 = v1 ? a0 + rs : 0xFFFFFFFFu;
+        reinterpret_cast<uint2 *>(W.E)[lane] = make_uint2(v0 ? a0 + rl0 : 0xFFFFFFFFu, oe1);
+        reinterpret_cast<uint2 *>(W.Off)[lane] = make_uint2(off0, off0 + dl0);
+        reinterpret_cast<uint16_t *>(W.T)[lane] = (uint16_t)(op0 | (op1 << 8));
+        if ((lane & 3u) == 3u) W.gE[lane >> 2] = oe1;
+        if ((lane & 15u) == 15u) W.sE[lane >> 4] = oe1;
+        const uint32_t a_end = a_cur + rdl(rin, 63);
+        const uint32_t off_end = off_cur + rdl(din, 63);
+        wsync();
+        // the triggers this tile consumes (p <= a_end), 64 at a time
+        for (;;) {
+            const uint32_t k = tc + lane;
+            const uint32_t key = k < nT ? TB[k] : 0xFFFFFFFFu;
+            const uint32_t p = key >> 2;
+            const bool in = k < nT && p <= a_end;
+            const uint64_t bi = __ballot(in);
+            if (!bi) break;
+            bool keep = false;
+            uint32_t v = 0;
+            if (in) {
+                // first operation with end >= p: the tile's last end is >= p
+                // (a_end, or ~0 from the stop on), so every count is < 4, 4, 8
+                auto lt4 = [&](uint4 x) {
+                    return (x.x < p ? 1u : 0u) + (x.y < p ? 1u : 0u) + (x.z < p ? 1u : 0u) + (x.w < p ? 1u : 0u);
+                };
+                const uint32_t s = lt4(*reinterpret_cast<const uint4 *>(W.sE));
+                const uint32_t g = 4 * s + lt4(reinterpret_cast<const uint4 *>(W.gE)[s]);
+                const uint4 *ge = reinterpret_cast<const uint4 *>(W.E + 8 * g);
+                const uint32_t oi = 8 * g + lt4(ge[0]) + lt4(ge[1]);
+                keep = W.T[oi] == 0;
+                v = i_ref + p + cgoffset + W.Off[oi];
+            }
+            k0_emit_lanes<MODE>(d, o, keep, v, key & 3u, false, lane, W.mV, W.mC);
+            tc += popc(bi);
+            if (popc(bi) < 64) break;
+        }
+        wsync();
+        a_cur = a_end;
+        off_cur = off_end;
+        j += 128;
+    }
+    // the tiles past the last consumed trigger, as in k0_walk
+    for (; j < ncig; j += 128) {
+        const uint2 c = cn;
+        next_tile();
+        racc += k0_refc(c.x) + k0_refc(c.y);
+        if (trunc) continue;
+        uint32_t fs;
+        if (!tile_stop(c.x & 15u, c.y & 15u, fs)) return false;
+        trunc = fs < 128;
+    }
+    return true;
+}
+#endif
+
 // a record's fields: its wave slot's row (pf_k0_hdr), read by scalar loads
 // where each phase needs them (the slot is uniform across the wave)
 DEV K0HdrP k0_rec(K0Args d, uint32_t slot) { return (K0HdrP)(d->hdr + slot); }
@@ -1665,7 +1810,12 @@ DEV void k0_record(K0Args d, K0W &L, K0HdrP h, uint32_t lane, TP TB, uint32_t ca
         k0_bcast(o, s);
         fatal = uni(f ? 1u : 0u) != 0;
     } else {
+#if PF_K0_TILE128
+        if (!implicit) fatal = !k0_walk128<1>(d, L, cig, ncig, qs, rev, TB, nT, lane, o, racc);
+        else fatal = !k0_walk<1>(d, L, cig, ncig, qs, rev, TB, nT, seq, len, true, lane, o, racc);
+#else
         fatal = !k0_walk<1>(d, L, cig, ncig, qs, rev, TB, nT, seq, len, implicit, lane, o, racc);
+#endif
         walked = true;
     }
     K0_STAMP(2);
