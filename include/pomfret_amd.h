@@ -620,6 +620,76 @@ int  pf_batch_permtest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, u
                        uint32_t seed, pf_perm_t **out);
 void pf_perm_free(pf_perm_t *p);
 
+/* Read-level rank-sum test of windows (pf_rank.hip; no reference counterpart):
+ * the Mann-Whitney U test between the two haplotypes' reads, each read
+ * contributing its own methylation fraction inside the window.  The read is
+ * the exchangeable unit, as in the permutation test; here the null
+ * distribution has a closed form (pf_rank_p), so the p-value has no floor and
+ * costs one pass, and AUC = U / (n1*n2) is a read-level effect size.  All in
+ * integers; windows may overlap, every window is tested on its own.
+ *   participating  as in pf_batch_permtest: tag 0 or 1, m_i / u_i the read's
+ *                  cat 0 / cat 1 entries with ws <= pos < we (a duplicate entry
+ *                  counts each time, cat 2 nowhere), n_i = m_i + u_i >= 1;
+ *   counted        a participating read with n_i >= min_calls; n_short[h] the
+ *                  participating reads tagged h below min_calls; n1 / n2 the
+ *                  counted reads tagged 0 / 1;
+ *   order          f_i > f_j iff m_i*n_j > m_j*n_i, equal iff the products are
+ *                  equal, in unsigned 64-bit arithmetic (N = sum of n_i over the
+ *                  participating reads is below 2^31, so products stay below
+ *                  2^62); never floating point;
+ *   statistic      over the pairs (i tagged 0, j tagged 1) of counted reads
+ *                  G = #{f_i > f_j}, E = #{f_i == f_j}; u2 = 2G + E, twice
+ *                  haplotype 1's U, in [0, 2*n1*n2];
+ *   ties           T = sum of t^3 - t over the groups of equal fraction among
+ *                  all counted reads = sum over i of e_i^2 - 1, e_i the counted
+ *                  reads with f_j == f_i, i itself included;
+ *   classes        per tag the counted reads with u_i == 0 (all-meth), with
+ *                  m_i == 0 (all-unmeth) and with both above 0 (mixed); sum[4]
+ *                  the counted reads' m1, u1, m2, u2;
+ *   status         0 tested; 1 nothing to test (n1 == 0 or n2 == 0), u2 and T
+ *                  0; 2 more than PF_RANK_MAX_READS counted reads, u2 and T 0
+ *                  (no error). */
+#define PF_RANK_MAX_READS 4096u
+typedef struct pf_rank {
+    uint32_t n_windows;
+    uint32_t min_calls;
+    const uint32_t *n_reads;   /* [n_windows*2] counted reads tagged 0, tagged 1  */
+    const uint32_t *n_short;   /* [n_windows*2] participating reads below min_calls */
+    const uint32_t *cls;       /* [n_windows*6] all-meth, all-unmeth, mixed of tag 0, then of tag 1 */
+    const uint64_t *sum;       /* [n_windows*4] the counted reads' m1, u1, m2, u2 */
+    const uint64_t *u2;        /* [n_windows] 2G + E                              */
+    const uint64_t *ties;      /* [n_windows] T                                   */
+    const uint32_t *status;    /* [n_windows] 0, 1, 2 as above                    */
+    float ms_kernels;          /* event-timed: the kernel only                    */
+} pf_rank_t;
+/* Batches, tags, the refusal while a run is in flight and ownership
+ * (pf_rank_free) exactly as in pf_batch_permtest; the batch is left as it was.
+ * min_calls outside [1, 65535] returns PF_ERR_ARG, N >= 2^31 in any window
+ * PF_ERR_LIMIT.  One workgroup per window; a window whose largest n_i is at
+ * most 65,535 is compared with 32-bit products, any other with 64-bit ones.
+ * The result depends on neither launch geometry, the product width nor atomic
+ * order.  In the environment (tests): PF_RANK_THREADS=<64|256|1024> sets the
+ * workgroup size (default 256); PF_RANK_WIDE=1 forces the 64-bit products for
+ * every window, unset or 0 leaves the choice per window; any other value of
+ * either returns PF_ERR_ARG. */
+int  pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t min_calls,
+                       pf_rank_t **out);
+void pf_rank_free(pf_rank_t *r);
+
+/* The rank test's two-sided p-value by the normal approximation with tie and
+ * continuity correction (host only), in doubles in exactly this order:
+ *   a = (double)n1 * (double)n2;  n = (double)n1 + (double)n2;
+ *   auc = u2 / (2a);
+ *   var = (a / 12) * ((n + 1) - T / (n * (n - 1)));
+ *   var <= 0 (every read tied): z = 0, p = 1;
+ *   else d = max(|u2 - a| / 2 - 0.5, 0);  z = d / sqrt(var);
+ *        p = min(1, erfc(z / sqrt(2))).
+ * It is scipy.stats.mannwhitneyu(alternative="two-sided", method="asymptotic",
+ * use_continuity=True).  The test is asymptotic: approximate below about eight
+ * reads per haplotype.  p underflows to 0 near z > 38; z does not.  PF_ERR_ARG
+ * when n1 or n2 is 0 or u2 > 2*n1*n2.  auc, z and p may each be NULL. */
+int  pf_rank_p(uint64_t u2, uint32_t n1, uint32_t n2, uint64_t ties, double *auc, double *z, double *p);
+
 /* Tags for untagged reads from a window's allele-specific methylation
  * (pf_assign.hip; no reference counterpart): inside a window [ws, we) where
  * the two haplotypes' methylation differs, an untagged read's own calls say
@@ -1735,6 +1805,64 @@ int  pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *
                             pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst, pf_hapmeth_hmm_stats_t *hst,
                             pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast, pf_hapmeth_tagcheck_stats_t *tst,
                             pf_hapmeth_regions_stats_t *rst);
+
+/* pf_bh_adjust with the p-values given as doubles: the tested entries sorted by
+ * (p, index), a group of exactly equal p shares the rank b of its last member,
+ * x = (p * (double)m) / (double)b with m the tested entries, q the running
+ * minimum of x from the largest p down, capped at 1.0; NaN for an untested
+ * entry.  A tested p that is NaN returns PF_ERR_ARG. */
+int  pf_bh_adjust_p(const double *p, const uint8_t *tested, uint64_t n, double *q);
+
+/* hapmeth --dmr-rank: one region of the second pass and its window of
+ * pf_batch_ranktest. */
+typedef struct pf_rank_rec {
+    const char *chrom;
+    uint32_t start, end;
+    uint32_t reads[2];         /* pf_rank_t.n_reads of its window                 */
+    uint32_t n_short[2];       /* .n_short                                        */
+    uint32_t cls[6];           /* .cls                                            */
+    uint32_t status;           /* .status                                         */
+    uint64_t u2, ties;         /* .u2, .ties                                      */
+} pf_rank_rec_t;
+/* {prefix}.hapmeth.rank.tsv, the whole file, tab-separated:
+ *   #chrom start end reads_h1 reads_h2 short_h1 short_h2 allmeth_h1
+ *   allunmeth_h1 mixed_h1 allmeth_h2 allunmeth_h2 mixed_h2 auc z rank_p rank_q
+ * one line per record in the given order.  With status 0: auc (%.4f), z (%.3f)
+ * and rank_p (%.6g) by pf_rank_p, and with bh != 0 rank_q (%.6g) by
+ * pf_bh_adjust_p over the status-0 records of rec[0, n), "." with bh == 0 (the
+ * regions of --dmr are selected on the data and get no correction); any other
+ * status prints "." in all four.  No record: the header alone.  *n_tested: the
+ * records with a numeric rank_p. */
+int  pf_write_rank(const char *path, const pf_rank_rec_t *rec, uint64_t n, int bh, uint64_t *n_tested);
+
+typedef struct pf_hapmeth_rank {
+    uint32_t min_calls;        /* pf_batch_ranktest's, 1 .. 65535; the CLI's default is 3  */
+} pf_hapmeth_rank_t;
+
+typedef struct pf_hapmeth_rank_stats {
+    uint64_t n_tested;         /* lines of the rank file with a numeric rank_p             */
+    uint64_t n_untested;       /* its other lines                                          */
+    uint64_t n_records;        /* records fetched by the second pass                       */
+    double ms_kernels;         /* summed pf_rank_t.ms_kernels                              */
+} pf_hapmeth_rank_stats_t;
+
+/* pf_hapmeth_run_regions, and with rank != NULL {out_prefix}.hapmeth.rank.tsv
+ * (pf_write_rank): the second pass, on the batch it fetched for perm, assign
+ * and tagcheck (with rank alone the pass still runs), also runs
+ * pf_batch_ranktest under the records' HP tags.  The windows are the pass's own:
+ * with dmr alone the regions that pass max_p, with regions the eligible ones.
+ * One record per region of the pass, in the order the pass takes them, kept on
+ * the host and written at the run's end, rank_q with regions only.  No file of
+ * the other features changes with rank.  rank == NULL: exactly
+ * pf_hapmeth_run_regions (kst is zeroed).  rank without dmr, or min_calls
+ * outside [1, 65535], returns PF_ERR_ARG.  On failure every file is unlinked.
+ * Every stats pointer may be NULL. */
+int  pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                         const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                         const pf_hapmeth_tagcheck_t *tagcheck, const pf_hapmeth_regions_t *regions,
+                         const pf_hapmeth_rank_t *rank, pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst,
+                         pf_hapmeth_hmm_stats_t *hst, pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast,
+                         pf_hapmeth_tagcheck_stats_t *tst, pf_hapmeth_regions_stats_t *rst, pf_hapmeth_rank_stats_t *kst);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from .abi import (DMR_HMM_SITES, DMR_RUN_DTYPE, REGION_SUM_DTYPE, PfRegions, HmmConfig, PfDmrHmm, PfDmrHmmCfg, AlnBatch, AssignConfig, PfAssign, PfAssignCfg, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
-                  PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfReadAlnBatch, PfTagcheck, PfWindowBatch, PfWindowOut, ReadAlnBatch,
+                  PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfRank, PfReadAlnBatch, PfTagcheck, PfWindowBatch, PfWindowOut, ReadAlnBatch,
                   WindowBatch, WindowResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -107,6 +107,10 @@ def lib():
                                         C.POINTER(C.POINTER(PfPerm))]
         L.pf_perm_free.argtypes = [C.POINTER(PfPerm)]
         L.pf_write_dmr_perm.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(PfDmr), C.POINTER(PfPerm), C.c_double, C.c_int]
+        L.pf_batch_ranktest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                        C.POINTER(C.POINTER(PfRank))]
+        L.pf_rank_free.argtypes = [C.POINTER(PfRank)]
+        L.pf_rank_p.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64] + [C.POINTER(C.c_double)] * 3
         L.pf_batch_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PfAssignCfg),
                                       C.POINTER(C.POINTER(PfAssign))]
         L.pf_assign_free.argtypes = [C.POINTER(PfAssign)]
@@ -380,6 +384,20 @@ def fisher_exact(n11, n12, n21, n22):
     l, r, t = C.c_double(), C.c_double(), C.c_double()
     q = lib().pf_fisher_exact(n11, n12, n21, n22, C.byref(l), C.byref(r), C.byref(t))
     return q, l.value, r.value, t.value
+
+
+def rank_p(u2, n1, n2, ties):
+    """(auc, z, p) of the rank-sum test from DeviceBatch.ranktest's integers
+    (pf_rank_p, host only): the two-sided normal approximation with tie and
+    continuity correction -- scipy.stats.mannwhitneyu(alternative="two-sided",
+    method="asymptotic", use_continuity=True).  Asymptotic: approximate below
+    about eight reads per haplotype; p underflows to 0 near z > 38."""
+    for v, top in ((u2, 2 ** 64), (n1, 2 ** 32), (n2, 2 ** 32), (ties, 2 ** 64)):
+        if not 0 <= int(v) < top:
+            raise PomfretError("pf_rank_p: an argument is out of range")
+    a, z, p = C.c_double(), C.c_double(), C.c_double()
+    _check(lib().pf_rank_p(int(u2), int(n1), int(n2), int(ties), C.byref(a), C.byref(z), C.byref(p)), "pf_rank_p")
+    return a.value, z.value, p.value
 
 
 class Context:
@@ -718,6 +736,41 @@ class DeviceBatch:
                         seed=int(r.seed), ms=float(r.ms_kernels))
         finally:
             lib().pf_perm_free(p)
+
+    def ranktest(self, min_calls: int = 3, read_hp=None) -> dict:
+        """Read-level rank-sum (Mann-Whitney) test of every window of the
+        batch (pf_batch_ranktest; include/pomfret_amd.h has the definition):
+        dict(n_reads [W, 2] the counted reads tagged 0 / 1 (tag 0 or 1, at
+        least min_calls call entries inside the window), n_short [W, 2] the
+        reads below min_calls, cls [W, 2, 3] the all-meth, all-unmeth and mixed
+        reads per tag, sum [W, 4] the counted reads' m1, u1, m2, u2, u2 [W]
+        twice haplotype 1's U, ties [W] the tie term, status [W] (0 tested, 1
+        a haplotype without a counted read, 2 more than 4,096 counted reads),
+        min_calls, ms the kernel's time).  rank_p(u2, n1, n2, ties) gives auc,
+        z and p where status is 0.  read_hp as in pileup."""
+        hp_ptr, n_hp = None, 0
+        if read_hp is not None:
+            hp = np.zeros(np.size(read_hp) + 1, np.uint8)
+            hp[:-1] = np.asarray(read_hp, np.uint8).ravel()
+            hp_ptr, n_hp = hp.ctypes.data, hp.size - 1
+        if not 0 <= int(min_calls) <= 0xFFFFFFFF:
+            raise PomfretError("pf_batch_ranktest: min_calls is 32-bit unsigned")
+        p = C.POINTER(PfRank)()
+        _check(lib().pf_batch_ranktest(self.ctx.handle, self.handle, hp_ptr, n_hp, int(min_calls), C.byref(p)),
+               "pf_batch_ranktest")
+        try:
+            r = p.contents
+            W = int(r.n_windows)
+
+            def arr(ptr, n, dt):
+                return np.ctypeslib.as_array(ptr, (n,)).copy() if W else np.zeros(0, dt)
+            return dict(n_reads=arr(r.n_reads, 2 * W, np.uint32).reshape(W, 2),
+                        n_short=arr(r.n_short, 2 * W, np.uint32).reshape(W, 2),
+                        cls=arr(r.cls, 6 * W, np.uint32).reshape(W, 2, 3), sum=arr(r.sum, 4 * W, np.uint64).reshape(W, 4),
+                        u2=arr(r.u2, W, np.uint64), ties=arr(r.ties, W, np.uint64), status=arr(r.status, W, np.uint32),
+                        min_calls=int(r.min_calls), ms=float(r.ms_kernels))
+        finally:
+            lib().pf_rank_free(p)
 
     def assign(self, cfg: AssignConfig = None, read_hp=None) -> dict:
         """Tags for the batch's untagged reads from each window's

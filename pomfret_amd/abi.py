@@ -505,6 +505,32 @@ class PfHapmethPermStats(C.Structure):
                 ("ms_kernels", C.c_double)]
 
 
+class PfRank(C.Structure):
+    """pf_rank_t: the rank-sum test of a batch's windows (pf_batch_ranktest)."""
+    _fields_ = [("n_windows", C.c_uint32), ("min_calls", C.c_uint32), ("n_reads", C.POINTER(C.c_uint32)),
+                ("n_short", C.POINTER(C.c_uint32)), ("cls", C.POINTER(C.c_uint32)), ("sum", C.POINTER(C.c_uint64)),
+                ("u2", C.POINTER(C.c_uint64)), ("ties", C.POINTER(C.c_uint64)), ("status", C.POINTER(C.c_uint32)),
+                ("ms_kernels", C.c_float)]
+
+
+class PfRankRec(C.Structure):
+    """pf_rank_rec_t: one line of {prefix}.hapmeth.rank.tsv (pf_write_rank)."""
+    _fields_ = [("chrom", C.c_char_p), ("start", C.c_uint32), ("end", C.c_uint32), ("reads", C.c_uint32 * 2),
+                ("n_short", C.c_uint32 * 2), ("cls", C.c_uint32 * 6), ("status", C.c_uint32), ("u2", C.c_uint64),
+                ("ties", C.c_uint64)]
+
+
+class PfHapmethRank(C.Structure):
+    """pf_hapmeth_rank_t (pf_hapmeth_run_rank)."""
+    _fields_ = [("min_calls", C.c_uint32)]
+
+
+class PfHapmethRankStats(C.Structure):
+    """pf_hapmeth_rank_stats_t."""
+    _fields_ = [("n_tested", C.c_uint64), ("n_untested", C.c_uint64), ("n_records", C.c_uint64),
+                ("ms_kernels", C.c_double)]
+
+
 class PfAssignCfg(C.Structure):
     """pf_assign_cfg_t."""
     _fields_ = [("min_cov", C.c_uint32), ("min_calls", C.c_uint32), ("min_llr_q16", C.c_int64)]

@@ -12,6 +12,7 @@
  *                         [--dmr-blocks blocks.gtf] [--dmr-perm N [--dmr-seed S]]
  *                         [--dmr-hmm [--dmr-hmm-site-cost BITS] [--dmr-hmm-switch BITS]]
  *                         [--regions regions.bed  (instead of --dmr: the regions are given)]
+ *                         [--dmr-rank [--dmr-rank-min-calls N]]
  *                         [--assign] [--tag-check] [--assign-min-llr BITS] [--assign-min-calls N]] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
@@ -98,7 +99,8 @@ static void help_methphase(const char *prefix) {
 enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV, O_BAMT, O_UNTAG, O_WIT,
        O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
        O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED,
-       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK, O_DMR_HMM, O_DMR_HMM_SITE, O_DMR_HMM_SWITCH, O_REGIONS };
+       O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK, O_DMR_HMM, O_DMR_HMM_SITE, O_DMR_HMM_SWITCH, O_REGIONS,
+       O_DMR_RANK, O_DMR_RANK_CALLS };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -123,6 +125,7 @@ static const struct option longopts[] = {
     {"dmr-hmm", no_argument, 0, O_DMR_HMM},      {"dmr-hmm-site-cost", required_argument, 0, O_DMR_HMM_SITE},
     {"dmr-hmm-switch", required_argument, 0, O_DMR_HMM_SWITCH},
     {"regions", required_argument, 0, O_REGIONS},
+    {"dmr-rank", no_argument, 0, O_DMR_RANK},    {"dmr-rank-min-calls", required_argument, 0, O_DMR_RANK_CALLS},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -322,6 +325,21 @@ static void help_hapmeth(void) {
                     "               holds although one read contributes to many CpGs (\".\" where a region has reads of\n"
                     "               one haplotype only, or more than 4096).  N in 1 .. 1000000. [0: off]\n");
     fprintf(stderr, "  --dmr-seed S [opt] Seed of the permutations. [1]\n");
+    fprintf(stderr, "  --dmr-rank [opt] Needs --dmr or --regions.  Also write {out_prefix}.hapmeth.rank.tsv: every region of the\n"
+                    "               second pass (those --dmr-perm tests) under a read-level Mann-Whitney rank-sum test.  Each\n"
+                    "               read counts once, with its own methylation fraction inside the region: reads_h1, reads_h2,\n"
+                    "               short_h1, short_h2 (reads below --dmr-rank-min-calls, left out), the fully methylated,\n"
+                    "               fully unmethylated and mixed reads of each haplotype, auc = U / (reads_h1 * reads_h2) (the\n"
+                    "               chance that a haplotype-1 read is more methylated than a haplotype-2 read; 1 or 0: an\n"
+                    "               on/off switch), z, rank_p and, with --regions, rank_q (Benjamini-Hochberg over the run's\n"
+                    "               tested regions; \".\" with --dmr, whose regions are selected on the data).  rank_p is the\n"
+                    "               two-sided normal approximation with tie and continuity correction: it has no floor and\n"
+                    "               needs no permutations, but it is asymptotic, so approximate below about eight reads per\n"
+                    "               haplotype; the exact small-sample distribution is not computed.  rank_p underflows to 0\n"
+                    "               near z > 38, which is why z has its own column.  \".\" in the four where a haplotype has no\n"
+                    "               counted read, or a region more than 4096.\n");
+    fprintf(stderr, "  --dmr-rank-min-calls N [opt] Needs --dmr-rank.  Calls inside the region a read needs to count, 1 .. 65535;\n"
+                    "               a choice, not a measured optimum. [3]\n");
     fprintf(stderr, "  --dmr-hmm [opt] Needs --dmr.  Find the regions with a three-state hidden Markov model (none, h1>h2,\n"
                     "               h1<h2) over each contig's CpGs instead of the per-CpG threshold: every CpG adds its\n"
                     "               evidence for one direction (log2 likelihood ratio of two methylation levels against\n"
@@ -381,7 +399,8 @@ static int hapmeth(int argc, char **argv) {
     pf_hapmeth_assign_t am;
     memset(&am, 0, sizeof am);
     int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0, tagcheck = 0, hmm = 0, hmm_opt = 0;
-    int gap_opt = 0;
+    int gap_opt = 0, rank = 0, rank_opt = 0;
+    long rcalls = 3;
     pf_hapmeth_regions_t rg;
     rg.bed_path = NULL;
     double hsite = 2.0, hswitch = 8.0;
@@ -418,6 +437,8 @@ static int hapmeth(int argc, char **argv) {
         case O_TAGCHECK: tagcheck = 1; break;
         case O_DMR_HMM: hmm = 1; break;
         case O_REGIONS: rg.bed_path = optarg; break;
+        case O_DMR_RANK: rank = 1; break;
+        case O_DMR_RANK_CALLS: rank_opt = 1; rcalls = strtol(optarg, &end, 10); if (*end || !*optarg) rcalls = -1; break;
         case O_DMR_HMM_SITE: hmm_opt = 1; hsite = strtod(optarg, &end); if (*end || !*optarg) hsite = -1.0; break;
         case O_DMR_HMM_SWITCH: hmm_opt = 1; hswitch = strtod(optarg, &end); if (*end || !*optarg) hswitch = -1.0; break;
         case O_ASSIGN_LLR: assign_opt = 1; allr = strtod(optarg, &end); if (*end || !*optarg) allr = -1.0; break;
@@ -455,6 +476,9 @@ static int hapmeth(int argc, char **argv) {
     }
     if (assign && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --assign needs --dmr or --regions\n"); return 1; }
     if (tagcheck && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --tag-check needs --dmr or --regions\n"); return 1; }
+    if (rank && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-rank needs --dmr or --regions\n"); return 1; }
+    if (rank_opt && !rank) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-rank-min-calls needs --dmr-rank\n"); return 1; }
+    if (rcalls < 1 || rcalls > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-rank-min-calls (1 .. 65535)\n"); return 1; }
     if (hmm_opt && !hmm) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-hmm-* options need --dmr-hmm\n"); return 1; }
     if (hmm && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-hmm needs --dmr\n"); return 1; }
     if (!(hsite >= 0.0 && hsite <= 64.0)) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-hmm-site-cost (0 .. 64)\n"); return 1; }
@@ -484,9 +508,12 @@ static int hapmeth(int argc, char **argv) {
     hm.cfg.site_cost_q16 = (int32_t)llround(hsite * 65536.0); hm.cfg.switch_q16 = (int32_t)llround(hswitch * 65536.0);
     pf_hapmeth_hmm_stats_t hst;
     pf_hapmeth_regions_stats_t rst;
-    const int rc = pf_hapmeth_run_regions(&op, have ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
-                                          assign || tagcheck ? &am : NULL, tagcheck ? &tm : NULL, rg.bed_path ? &rg : NULL,
-                                          &st, &dst, &hst, &pst, &ast, &tst, &rst);
+    pf_hapmeth_rank_t km;
+    km.min_calls = (uint32_t)rcalls;
+    pf_hapmeth_rank_stats_t kst;
+    const int rc = pf_hapmeth_run_rank(&op, have ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
+                                       assign || tagcheck ? &am : NULL, tagcheck ? &tm : NULL, rg.bed_path ? &rg : NULL,
+                                       rank ? &km : NULL, &st, &dst, &hst, &pst, &ast, &tst, &rst, &kst);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;
@@ -500,6 +527,9 @@ static int hapmeth(int argc, char **argv) {
                 op.out_prefix);
     if (pm.n_perm)
         fprintf(stderr, "[M::main] %llu of them with a permutation p-value\n", (unsigned long long)pst.n_tested);
+    if (rank)
+        fprintf(stderr, "[M::main] %llu regions written to %s.hapmeth.rank.tsv, %llu of them with a rank-sum p-value\n",
+                (unsigned long long)(kst.n_tested + kst.n_untested), op.out_prefix, (unsigned long long)kst.n_tested);
     if (assign)
         fprintf(stderr, "[M::main] %llu scored reads written to %s.hapmeth.assign.tsv, %llu of them with a tag\n",
                 (unsigned long long)ast.n_lines, op.out_prefix, (unsigned long long)(ast.n_h1 + ast.n_h2));

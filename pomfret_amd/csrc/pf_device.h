@@ -54,6 +54,10 @@
 #define PF_PERM_THREADS 256         /* the permutation test's workgroup (PF_PERM_THREADS=<64|256|1024> overrides it) */
 #define PF_PERM_THREADS_MAX 1024
 #define PF_PERM_READS 4096          /* participating reads per window held in LDS (PF_PERM_MAX_READS): 8 B each */
+#define PF_RANK_THREADS 256         /* the rank test's workgroup (PF_RANK_THREADS=<64|256|1024> overrides it) */
+#define PF_RANK_THREADS_MAX 1024
+#define PF_RANK_READS 4096          /* counted reads per window held in LDS (PF_RANK_MAX_READS): 8 B each, 32 KB */
+#define PF_RANK_NARROW_MAX 65535u   /* a window whose largest n_i is at most this compares 32-bit products */
 #define PF_ASSIGN_TILE 4096         /* sites per LDS tile of pf_assign_score: position and two weights, 12 B each, 48 KB
                                       (PF_ASSIGN_TILE=<n> overrides it downwards) */
 #define PF_ASSIGN_THREADS 256       /* its workgroup: each wave takes 64 of the window's reads at a time (1,024 measured:

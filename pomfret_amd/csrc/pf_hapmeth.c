@@ -46,7 +46,12 @@
  *   pf_hapmeth_run_regions: pf_hapmeth_run_hmm, and with --regions the regions
  *                     come from a BED: each job's sites through pf_region_sums,
  *                     the records added per region, the second pass on the
- *                     eligible ones, the file written at the run's end.
+ *                     eligible ones, the file written at the run's end;
+ *   pf_rank_p, pf_bh_adjust_p, pf_write_rank: the rank test's p-value, q-values
+ *                     of doubles, and {prefix}.hapmeth.rank.tsv (host only);
+ *   pf_hapmeth_run_rank: pf_hapmeth_run_regions, and with --dmr-rank the second
+ *                     pass also runs pf_batch_ranktest on its batch; one record
+ *                     per region, the file written at the run's end.
  */
 #include <math.h>
 #include <stdint.h>
@@ -423,6 +428,111 @@ int pf_write_regions(const char *path, const pf_region_rec_t *rec, uint64_t n, i
     return PF_OK;
 }
 
+/* ---- the rank test: the p-value, the q-values of doubles and the writer */
+int pf_rank_p(uint64_t u2, uint32_t n1, uint32_t n2, uint64_t ties, double *auc, double *z, double *p) {
+    if (n1 == 0 || n2 == 0 || u2 > 2ull * (uint64_t)n1 * (uint64_t)n2) return PF_ERR_ARG;
+    const double a = (double)n1 * (double)n2;
+    const double n = (double)n1 + (double)n2;
+    const double u = (double)u2;
+    const double var = (a / 12.0) * ((n + 1.0) - (double)ties / (n * (n - 1.0)));
+    double zz = 0.0, pp = 1.0;
+    if (var > 0.0) {
+        double d = fabs(u - a) / 2.0 - 0.5;
+        if (!(d > 0.0)) d = 0.0;
+        zz = d / sqrt(var);
+        pp = erfc(zz / sqrt(2.0));
+        if (pp > 1.0) pp = 1.0;
+    }
+    if (auc) *auc = u / (2.0 * a);
+    if (z) *z = zz;
+    if (p) *p = pp;
+    return PF_OK;
+}
+
+typedef struct { double p; uint64_t i; } bhp_ent_t;
+
+static int cmp_bhp(const void *a, const void *b) {
+    const bhp_ent_t *x = (const bhp_ent_t *)a, *y = (const bhp_ent_t *)b;
+    if (x->p != y->p) return x->p < y->p ? -1 : 1;
+    return x->i < y->i ? -1 : x->i > y->i;
+}
+
+int pf_bh_adjust_p(const double *p, const uint8_t *tested, uint64_t n, double *q) {
+    if (n && (!p || !tested || !q)) return PF_ERR_ARG;
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; i++)
+        if (tested[i]) {
+            if (p[i] != p[i]) return PF_ERR_ARG;
+            m++;
+        }
+    for (uint64_t i = 0; i < n; i++) q[i] = NAN;
+    if (!m) return PF_OK;
+    bhp_ent_t *v = (bhp_ent_t *)malloc(m * sizeof *v);
+    if (!v) return PF_ERR_NOMEM;
+    uint64_t k = 0;
+    for (uint64_t i = 0; i < n; i++)
+        if (tested[i]) { v[k].p = p[i]; v[k].i = i; k++; }
+    qsort(v, m, sizeof *v, cmp_bhp);
+    /* as pf_bh_adjust: from the largest p down, a group of equal p [a, b) has rank b */
+    double run = 0.0;
+    int have = 0;
+    for (uint64_t b = m; b > 0;) {
+        uint64_t a = b - 1;
+        while (a > 0 && v[a - 1].p == v[b - 1].p) a--;
+        const double x = (v[a].p * (double)m) / (double)b;
+        if (!have || x < run) run = x;
+        have = 1;
+        for (uint64_t j = a; j < b; j++) q[v[j].i] = run < 1.0 ? run : 1.0;
+        b = a;
+    }
+    free(v);
+    return PF_OK;
+}
+
+int pf_write_rank(const char *path, const pf_rank_rec_t *rec, uint64_t n, int bh, uint64_t *n_tested) {
+    if (n_tested) *n_tested = 0;
+    if (!path || (n && !rec)) return PF_ERR_ARG;
+    double *pv = NULL, *q = NULL;
+    uint8_t *tested = NULL;
+    if (n) {
+        pv = (double *)malloc(8ull * n);
+        q = (double *)malloc(8ull * n);
+        tested = (uint8_t *)malloc(n);
+        int rc = pv && q && tested ? PF_OK : PF_ERR_NOMEM;
+        for (uint64_t i = 0; i < n && !rc; i++) {
+            pv[i] = 1.0;
+            tested[i] = rec[i].status == 0;
+            if (tested[i]) rc = pf_rank_p(rec[i].u2, rec[i].reads[0], rec[i].reads[1], rec[i].ties, NULL, NULL, pv + i);
+        }
+        if (!rc && bh) rc = pf_bh_adjust_p(pv, tested, n, q);
+        if (rc) { free(pv); free(q); free(tested); return rc; }
+    }
+    FILE *fp = fopen(path, "w");
+    if (!fp) { free(pv); free(q); free(tested); return -1; }
+    fprintf(fp, "#chrom\tstart\tend\treads_h1\treads_h2\tshort_h1\tshort_h2\tallmeth_h1\tallunmeth_h1\tmixed_h1\tallmeth_h2"
+            "\tallunmeth_h2\tmixed_h2\tauc\tz\trank_p\trank_q\n");
+    for (uint64_t i = 0; i < n; i++) {
+        const pf_rank_rec_t *r = rec + i;
+        fprintf(fp, "%s\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u", r->chrom ? r->chrom : ".", r->start, r->end,
+                r->reads[0], r->reads[1], r->n_short[0], r->n_short[1], r->cls[0], r->cls[1], r->cls[2], r->cls[3], r->cls[4],
+                r->cls[5]);
+        if (!tested[i]) fprintf(fp, "\t.\t.\t.\t.\n");
+        else {
+            double auc = 0.0, z = 0.0, p = 1.0;
+            (void)pf_rank_p(r->u2, r->reads[0], r->reads[1], r->ties, &auc, &z, &p);
+            fprintf(fp, "\t%.4f\t%.3f\t%.6g\t", auc, z, p);
+            if (bh) fprintf(fp, "%.6g\n", q[i]); else fprintf(fp, ".\n");
+            if (n_tested) ++*n_tested;
+        }
+    }
+    free(pv);
+    free(q);
+    free(tested);
+    const int bad = ferror(fp);
+    if (fclose(fp) != 0 || bad) return -1;
+    return PF_OK;
+}
+
 /* "chrom" or "chrom:beg-end" / "chrom:beg" (1-based inclusive, commas allowed)
  * -> tid and the 0-based [*s, *e); a name that holds ':' itself is tried whole
  * first */
@@ -501,6 +611,12 @@ typedef struct {
     uint64_t kn;
     size_t rec0;               /* rec + rec0: the current contig's */
     pf_hapmeth_regions_stats_t rst;
+    /* --dmr-rank */
+    const pf_hapmeth_rank_t *rank;
+    char *kpath;
+    pf_rank_rec_t *krec;       /* the run's regions of the second pass, in the pass's order */
+    size_t nk, mk;
+    pf_hapmeth_rank_stats_t kst;
 } hm_t;
 
 /* the fetch of one job, the same in both passes: the records of the windows
@@ -756,6 +872,7 @@ static int hm_second(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t 
         if (H->perm) H->pst.n_records += fetched;
         if (H->assign) H->ast.n_records += fetched;
         if (H->tagcheck) H->tst.n_records += fetched;
+        if (H->rank) H->kst.n_records += fetched;
         if (rc == PF_ERR_LIMIT)
             fprintf(stderr, "[E::pf_hapmeth_main] %s:%u-%u: a region exceeds a device limit (65,535 records per window)\n",
                     chrom, ws[0] + 1, we[k - 1]);
@@ -770,6 +887,28 @@ static int hm_second(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t 
                 stat[idx[j]] = part->status[j];
             }
             if (!rc) H->pst.ms_kernels += part->ms_kernels;
+        }
+        if (!rc && H->rank) {
+            pf_rank_t *rk = NULL;
+            rc = pf_batch_ranktest(H->ctx, db, NULL, 0, H->rank->min_calls, &rk);
+            if (!rc && rk->n_windows != k) rc = PF_ERR_INTERNAL;
+            if (!rc && H->nk + k > H->mk) {
+                size_t nm = H->mk ? H->mk * 2 : 256;
+                while (nm < H->nk + k) nm *= 2;
+                pf_rank_rec_t *p = (pf_rank_rec_t *)realloc(H->krec, nm * sizeof *p);
+                if (!p) rc = PF_ERR_NOMEM;
+                else { H->krec = p; H->mk = nm; }
+            }
+            for (uint32_t j = 0; j < k && !rc; j++) {
+                pf_rank_rec_t *r = H->krec + H->nk++;
+                memset(r, 0, sizeof *r);
+                r->chrom = chrom; r->start = ws[j]; r->end = we[j];
+                for (int q = 0; q < 2; q++) { r->reads[q] = rk->n_reads[2 * j + q]; r->n_short[q] = rk->n_short[2 * j + q]; }
+                for (int q = 0; q < 6; q++) r->cls[q] = rk->cls[6 * j + q];
+                r->status = rk->status[j]; r->u2 = rk->u2[j]; r->ties = rk->ties[j];
+            }
+            if (!rc) H->kst.ms_kernels += rk->ms_kernels;
+            pf_rank_free(rk);
         }
         if (!rc && H->assign) {
             pf_assign_cfg_t ac;
@@ -848,7 +987,7 @@ static int hm_flush(hm_t *H, const char *chrom) {
     pf_perm_t *P = NULL;
     uint64_t lines = 0, dots = 0;
     int rc = H->hmm ? hm_model(H, &fin) : pf_dmr_acc_flush(H->acc, &fin);
-    if (!rc && (H->perm || H->assign || H->tagcheck)) rc = hm_second(H, chrom, fin, &P);
+    if (!rc && (H->perm || H->assign || H->tagcheck || H->rank)) rc = hm_second(H, chrom, fin, &P);
     if (!rc) rc = write_dmr(H->dpath, chrom, fin, P, H->dmr->max_p, 0, &lines, &dots);
     if (!rc) {
         H->dst.n_regions += lines;
@@ -868,7 +1007,7 @@ static int hm_flush(hm_t *H, const char *chrom) {
 /* --regions: the contig's sums are complete; its eligible regions go through
  * the second pass as the windows [start, end) */
 static int hm_regions_flush(hm_t *H, const char *chrom) {
-    if (!H->perm && !H->assign && !H->tagcheck) return PF_OK;
+    if (!H->perm && !H->assign && !H->tagcheck && !H->rank) return PF_OK;
     pf_region_rec_t *rec = H->rec + H->rec0;
     const uint64_t n = H->kn;
     pf_dmr_t fin;
@@ -983,6 +1122,18 @@ int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *d
                            pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats, pf_hapmeth_hmm_stats_t *hstats,
                            pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats,
                            pf_hapmeth_tagcheck_stats_t *tstats, pf_hapmeth_regions_stats_t *rstats) {
+    return pf_hapmeth_run_rank(o, dmr, hmm, perm, assign, tagcheck, regions, NULL, stats, dstats, hstats, pstats, astats,
+                               tstats, rstats, NULL);
+}
+
+int pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                        const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                        const pf_hapmeth_tagcheck_t *tagcheck, const pf_hapmeth_regions_t *regions,
+                        const pf_hapmeth_rank_t *rank, pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats,
+                        pf_hapmeth_hmm_stats_t *hstats, pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats,
+                        pf_hapmeth_tagcheck_stats_t *tstats, pf_hapmeth_regions_stats_t *rstats,
+                        pf_hapmeth_rank_stats_t *kstats) {
+    if (kstats) memset(kstats, 0, sizeof *kstats);
     if (rstats) memset(rstats, 0, sizeof *rstats);
     if (hstats) memset(hstats, 0, sizeof *hstats);
     if (tstats) memset(tstats, 0, sizeof *tstats);
@@ -1001,8 +1152,10 @@ int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *d
                 hmm->cfg.switch_q16 > 64 * 65536))
         return PF_ERR_ARG;
     if (regions && (!dmr || hmm || !regions->bed_path)) return PF_ERR_ARG;
+    if (rank && (!dmr || rank->min_calls < 1u || rank->min_calls > 65535u)) return PF_ERR_ARG;
     hm_t H;
     memset(&H, 0, sizeof H);
+    H.rank = rank;
     H.regions = regions;
     H.o = o;
     H.dmr = dmr;
@@ -1068,9 +1221,10 @@ int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *d
         H.tpath = (char *)malloc(l);
         H.trpath = (char *)malloc(l);
         H.rpath = (char *)malloc(l);
+        H.kpath = (char *)malloc(l);
         ws = (uint32_t *)malloc(4ull * jw);
         we = (uint32_t *)malloc(4ull * jw);
-        if (!H.path || !H.dpath || !H.apath || !H.tpath || !H.trpath || !H.rpath || !ws || !we) rc = PF_ERR_NOMEM;
+        if (!H.path || !H.dpath || !H.apath || !H.tpath || !H.trpath || !H.rpath || !H.kpath || !ws || !we) rc = PF_ERR_NOMEM;
         else {
             snprintf(H.path, l, "%s.hapmeth.bed", o->out_prefix);
             snprintf(H.dpath, l, "%s.hapmeth.dmr.bed", o->out_prefix);
@@ -1078,6 +1232,7 @@ int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *d
             snprintf(H.tpath, l, "%s.hapmeth.tagcheck.tsv", o->out_prefix);
             snprintf(H.trpath, l, "%s.hapmeth.tagcheck.regions.tsv", o->out_prefix);
             snprintf(H.rpath, l, "%s.hapmeth.regions.bed", o->out_prefix);
+            snprintf(H.kpath, l, "%s.hapmeth.rank.tsv", o->out_prefix);
         }
     }
     if (!rc) {
@@ -1123,6 +1278,16 @@ int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *d
             H.rst.n_untested = H.pst.n_untested = H.nrec - tested;
         }
     }
+    int kmade = 0;
+    if (!rc && rank) {                                 /* at the end: rank_q needs every region */
+        uint64_t tested = 0;
+        kmade = 1;
+        rc = pf_write_rank(H.kpath, H.krec, H.nk, regions != NULL, &tested);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.kpath);
+        H.kst.n_tested = tested;
+        H.kst.n_untested = H.nk - tested;
+    }
+    if (rc && kmade) (void)unlink(H.kpath);
     if (rc && rmade) (void)unlink(H.rpath);
     if (rc && made) (void)unlink(H.path);              /* no truncated output behind a failure */
     if (rc && dmade) (void)unlink(H.dpath);
@@ -1150,6 +1315,10 @@ int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *d
                 "%llu records fetched again, permutation kernels %.3f ms\n", (unsigned long long)H.pst.n_tested,
                 perm->n_perm, perm->seed, (unsigned long long)H.pst.n_untested, (unsigned long long)H.pst.n_records,
                 H.pst.ms_kernels);
+    if (!rc && o->verbose && rank)
+        fprintf(stderr, "[M::pf_hapmeth_main] rank test: %llu regions tested (at least %u calls a read), %llu without a test, "
+                "%llu records fetched for it, rank kernels %.3f ms\n", (unsigned long long)H.kst.n_tested, rank->min_calls,
+                (unsigned long long)H.kst.n_untested, (unsigned long long)H.kst.n_records, H.kst.ms_kernels);
     if (!rc && o->verbose && assign)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu candidate reads scored, %llu assigned (%llu h1 / %llu h2), "
                 "%llu records fetched for it, assign kernels %.3f ms\n", (unsigned long long)H.ast.n_lines,
@@ -1173,6 +1342,7 @@ int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *d
     if (tstats) *tstats = H.tst;
     if (hstats) *hstats = H.hst;
     if (rstats) *rstats = H.rst;
+    if (kstats) *kstats = H.kst;
     free(ws);
     free(we);
     free(H.path);
@@ -1184,6 +1354,8 @@ int pf_hapmeth_run_regions(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *d
     free(H.hpos);
     free(H.hcnt);
     free(H.rpath);
+    free(H.kpath);
+    free(H.krec);
     free(H.rec);
     free(H.ks);
     free(H.ke);

@@ -1,0 +1,343 @@
+// pf_rank.hip -- read-level rank-sum test of a batch's windows
+// (pf_batch_ranktest; include/pomfret_amd.h has the definition).
+//
+// One workgroup per window, two phases, all in integers.
+//
+// Phase 1 is pf_perm_test's read loop: the window's reads blockDim.x at a
+// time, one per lane; a read whose sorted call slice ends left of the window or
+// starts right of it needs no search, the others binary-search the slice for
+// the window's first position; the wave then strides over each hitting read's
+// calls up to the window's end and counts its meth and unmeth entries with two
+// ballots per 64 calls.  The counted reads (tag 0 or 1, at least min_calls
+// entries) are compacted in read order into LDS with ballot / mbcnt prefixes
+// across the waves as (m, n | tag << 31), 8 B each; the class counters, the
+// sums, the short reads and the largest n are collected by LDS integer
+// atomics.
+//
+// Phase 2 is the all-pairs pass.  A lane owns a row i (rows tid, tid +
+// blockDim.x, ...); every j comes as a broadcast, all lanes reading one LDS
+// address, which costs no bank conflict.  Per pair two products and two
+// compares: the lane counts g_i (f_i > f_j) and c_i (f_i == f_j) over the j
+// tagged 1 -- they enter G and E only where i is tagged 0 -- and e_i (f_i ==
+// f_j) over every j.  The waves reduce the three sums, add them in LDS as
+// 64-bit integers, and the window is stored once.  No HBM atomic, no scratch.
+// The pass is instantiated for 32-bit and for 64-bit products and chosen per
+// window: where the window's largest n is at most 65,535 every product is
+// below 2^32.  Integer sums only: neither the workgroup size, the product
+// width nor the order of the atomics reaches the result.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <vector>
+#include "pf_device.h"
+#include "../../include/pomfret_amd.h"
+
+struct pf_ctx;
+struct pf_dbatch;
+extern "C" int pf_ctx_device(const pf_ctx *c);
+extern "C" hipStream_t pf_ctx_stream(const pf_ctx *c);
+extern "C" int pf_batch_calls_view(pf_ctx *ctx, pf_dbatch *b, pf_dev_batch *view);       // pf_api.hip
+
+namespace {
+
+static_assert(PF_RANK_READS == PF_RANK_MAX_READS, "the LDS array holds exactly the documented limit");
+
+#define RANK_ST_LIMIT 3u            /* internal: N >= 2^31, the call returns PF_ERR_LIMIT */
+#ifndef PF_RANK_UNROLL
+#define PF_RANK_UNROLL 4             /* pairs per trip of the j loop (measured: profiles/rank/README.md) */
+#endif
+#define RANK_UNROLL PF_RANK_UNROLL
+
+struct rank_out {
+    uint64_t sum[4];
+    uint64_t u2, ties;
+    uint32_t n_reads[2], n_short[2], cls[6];
+    uint32_t status, wide;                           /* wide: the products the window took (not part of pf_rank_t) */
+};
+static_assert(sizeof(rank_out) == 96, "rank_out is copied back as 96-byte records");
+
+struct rank_args {
+    uint32_t W, min_calls, force_wide, pad;
+    const uint32_t *win_start, *win_end, *win_read_off;
+    const uint8_t *read_hp;                          /* the batch's tags or the caller's */
+    const uint64_t *read_call_off, *read_call_end;
+    const uint32_t *call_pos;
+    const uint8_t *call_cat;
+    rank_out *out;                                   /* [W] */
+};
+
+__device__ __forceinline__ uint32_t lane_prefix(uint64_t bal) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+}
+
+__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), d);
+        x += ((uint64_t)hi << 32) | lo;
+    }
+    return x;
+}
+
+// The rows tid, tid + nt, ... of the n counted reads in s_r against every j.
+// P: the products' type, uint32_t where every n is at most 65,535.
+template <typename P>
+__device__ __forceinline__ void rank_rows(const uint2 *s_r, uint32_t n, uint32_t tid, uint32_t nt, uint64_t &G, uint64_t &E,
+                                          uint64_t &T) {
+    for (uint32_t i = tid; i < n; i += nt) {
+        const uint2 ri = s_r[i];
+        const P mi = (P)ri.x, ni = (P)(ri.y & 0x7FFFFFFFu);
+        uint32_t g = 0, c = 0, e = 0;
+        auto pair = [&](uint32_t j) {
+            const uint2 rj = s_r[j];                  // the same address in every lane: a broadcast
+            const uint32_t tj = rj.y >> 31;
+            const P a = mi * (P)(rj.y & 0x7FFFFFFFu), b = (P)rj.x * ni;
+            g += a > b ? tj : 0u;
+            c += a == b ? tj : 0u;
+            e += a == b ? 1u : 0u;
+        };
+        uint32_t j = 0;
+        for (; j + RANK_UNROLL <= n; j += RANK_UNROLL) {
+#pragma unroll
+            for (uint32_t q = 0; q < RANK_UNROLL; q++) pair(j + q);
+        }
+        for (; j < n; j++) pair(j);
+        const bool h1 = (ri.y >> 31) == 0u;           // only rows of haplotype 1 count against haplotype 2
+        G += h1 ? g : 0u;
+        E += h1 ? c : 0u;
+        T += (uint64_t)e * e - 1ull;                  // e >= 1: the read itself
+    }
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(PF_RANK_THREADS_MAX) void pf_rank_test(rank_args a) {
+    __shared__ uint2 s_r[PF_RANK_READS];             // per counted read: m, n | tag << 31
+    __shared__ unsigned long long s_sum[4], s_N, s_acc[3];
+    __shared__ uint32_t s_nr[2], s_short[2], s_cls[6], s_max, wsum[PF_RANK_THREADS_MAX / PF_WAVE];
+    const uint32_t w = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t nt = blockDim.x, nw = nt >> 6;
+    if (w >= a.W) return;
+    if (tid < 4u) s_sum[tid] = 0ull;
+    if (tid < 3u) s_acc[tid] = 0ull;
+    if (tid < 2u) { s_nr[tid] = 0u; s_short[tid] = 0u; }
+    if (tid < 6u) s_cls[tid] = 0u;
+    if (tid == 0u) { s_N = 0ull; s_max = 0u; }
+    __syncthreads();
+
+    // ---- phase 1: the counted reads in read order
+    const uint32_t ws = a.win_start[w], we = a.win_end[w];
+    const uint32_t r0 = a.win_read_off[w], r1 = a.win_read_off[w + 1];
+    uint32_t n = 0;
+    for (uint32_t g = r0; g < r1; g += nt) {          // the same rounds in every thread: barriers inside
+        const uint32_t r = g + tid;
+        uint64_t lo = 0, c1 = 0;
+        uint32_t hp = 2u;
+        if (r >= g && r < r1) {
+            lo = a.read_call_off[r];
+            c1 = a.read_call_end[r];
+            hp = a.read_hp[r];
+        }
+        if (hp > 1u) lo = c1;                         // untagged, HP >= 3: not a read of the test
+        if (lo < c1 && (a.call_pos[c1 - 1] < ws || a.call_pos[lo] >= we)) lo = c1;
+        for (uint64_t hi = c1; lo < hi;) {
+            const uint64_t mid = lo + (hi - lo) / 2;
+            if (a.call_pos[mid] < ws) lo = mid + 1; else hi = mid;
+        }
+        const bool hit = lo < c1 && a.call_pos[lo] < we;
+        uint32_t my_m = 0, my_u = 0;
+        for (uint64_t m = __ballot(hit); m; m &= m - 1) {
+            const int l = __builtin_ctzll(m);
+            const uint64_t s = ((uint64_t)(uint32_t)__shfl((int)(lo >> 32), l) << 32) | (uint32_t)__shfl((int)lo, l);
+            const uint64_t e = ((uint64_t)(uint32_t)__shfl((int)(c1 >> 32), l) << 32) | (uint32_t)__shfl((int)c1, l);
+            uint32_t cm = 0, cu = 0;                  // wave-uniform
+            for (uint64_t c0 = s; c0 < e; c0 += 64) {
+                const uint64_t c = c0 + lane;
+                const bool valid = c < e;
+                const uint32_t p = valid ? a.call_pos[c] : 0u;
+                const uint32_t cat = valid ? a.call_cat[c] : 2u;
+                const bool in = valid && p < we;      // p >= ws: the slice is sorted and starts at the bound
+                cm += (uint32_t)__popcll(__ballot(in && cat == 0u));
+                cu += (uint32_t)__popcll(__ballot(in && cat == 1u));
+                if (__ballot(valid && !in)) break;    // past the window's end
+            }
+            my_m = lane == (uint32_t)l ? cm : my_m;
+            my_u = lane == (uint32_t)l ? cu : my_u;
+        }
+        const uint32_t my_n = my_m + my_u;
+        const bool part = hit && my_n != 0u;
+        const bool counted = part && my_n >= a.min_calls;
+        const uint64_t bal = __ballot(counted);
+        if (lane == 0u) wsum[wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = 0, tot = 0;
+        for (uint32_t k = 0; k < nw; k++) {
+            const uint32_t s = wsum[k];
+            before += k < wave ? s : 0u;
+            tot += s;
+        }
+        if (part) atomicAdd(&s_N, (unsigned long long)my_n);
+        if (part && !counted) atomicAdd(&s_short[hp], 1u);
+        if (counted) {
+            const uint32_t idx = n + before + lane_prefix(bal);
+            if (idx < PF_RANK_READS) s_r[idx] = make_uint2(my_m, (my_n & 0x7FFFFFFFu) | (hp << 31));
+            atomicAdd(&s_sum[2u * hp], (unsigned long long)my_m);
+            atomicAdd(&s_sum[2u * hp + 1u], (unsigned long long)my_u);
+            atomicAdd(&s_nr[hp], 1u);
+            atomicAdd(&s_cls[3u * hp + (my_u == 0u ? 0u : my_m == 0u ? 1u : 2u)], 1u);
+            atomicMax(&s_max, my_n);
+        }
+        n += tot;
+        __syncthreads();
+    }
+
+    const uint32_t n1 = s_nr[0], n2 = s_nr[1];
+    const bool over = s_N >= 0x80000000ull;
+    const uint32_t status = over ? RANK_ST_LIMIT : n > PF_RANK_READS ? 2u : (n1 == 0u || n2 == 0u) ? 1u : 0u;
+    const bool wide = a.force_wide != 0u || s_max > PF_RANK_NARROW_MAX;
+
+    // ---- phase 2: all pairs
+    if (status == 0u) {
+        uint64_t G = 0, E = 0, T = 0;
+        if (wide) rank_rows<uint64_t>(s_r, n, tid, nt, G, E, T);
+        else rank_rows<uint32_t>(s_r, n, tid, nt, G, E, T);
+        G = wave_sum64(G);
+        E = wave_sum64(E);
+        T = wave_sum64(T);
+        if (lane == 0u) {
+            if (G) atomicAdd(&s_acc[0], (unsigned long long)G);
+            if (E) atomicAdd(&s_acc[1], (unsigned long long)E);
+            if (T) atomicAdd(&s_acc[2], (unsigned long long)T);
+        }
+    }
+    __syncthreads();
+    if (tid == 0u) {
+        rank_out o;
+        for (int k = 0; k < 4; k++) o.sum[k] = s_sum[k];
+        o.u2 = 2ull * s_acc[0] + s_acc[1];
+        o.ties = s_acc[2];
+        o.n_reads[0] = n1; o.n_reads[1] = n2;
+        o.n_short[0] = s_short[0]; o.n_short[1] = s_short[1];
+        for (int k = 0; k < 6; k++) o.cls[k] = s_cls[k];
+        o.status = status;
+        o.wide = wide ? 1u : 0u;
+        a.out[w] = o;
+    }
+}
+
+// ---- host side
+extern "C" void pf_rank_free(pf_rank_t *p) {
+    if (!p) return;
+    free(const_cast<uint32_t *>(p->n_reads));
+    free(const_cast<uint32_t *>(p->n_short));
+    free(const_cast<uint32_t *>(p->cls));
+    free(const_cast<uint64_t *>(p->sum));
+    free(const_cast<uint64_t *>(p->u2));
+    free(const_cast<uint64_t *>(p->ties));
+    free(const_cast<uint32_t *>(p->status));
+    free(p);
+}
+
+// the workgroup: PF_RANK_THREADS=<64|256|1024> (tests); 0 for any other value
+static uint32_t rank_threads() {
+    const char *e = getenv("PF_RANK_THREADS");
+    if (!e) return PF_RANK_THREADS;
+    if (!strcmp(e, "64")) return 64;
+    if (!strcmp(e, "256")) return 256;
+    if (!strcmp(e, "1024")) return 1024;
+    return 0;
+}
+
+// PF_RANK_WIDE: unset or "0" 0, "1" 1 (64-bit products for every window), anything else -1
+static int rank_wide() {
+    const char *e = getenv("PF_RANK_WIDE");
+    if (!e || !strcmp(e, "0")) return 0;
+    if (!strcmp(e, "1")) return 1;
+    return -1;
+}
+
+extern "C" int pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t min_calls,
+                                 pf_rank_t **out) {
+    if (!ctx || !db || !out) return PF_ERR_ARG;
+    *out = nullptr;
+    if (min_calls < 1u || min_calls > 65535u) return PF_ERR_ARG;
+    const uint32_t nt = rank_threads();
+    const int fw = rank_wide();
+    if (!nt || fw < 0) return PF_ERR_ARG;
+    pf_dev_batch d;
+    const int vrc = pf_batch_calls_view(ctx, db, &d);
+    if (vrc) return vrc;
+    const uint32_t W = d.W, R = d.R;
+    if (read_hp && n_hp != R) return PF_ERR_ARG;
+    hipStream_t st = pf_ctx_stream(ctx);
+
+    pf_rank_t *res = (pf_rank_t *)calloc(1, sizeof(pf_rank_t));
+    if (!res) return PF_ERR_NOMEM;
+    res->n_windows = W;
+    res->min_calls = min_calls;
+    if (W == 0) { *out = res; return PF_OK; }
+    uint32_t *h_nr = (uint32_t *)calloc(2ull * W, 4), *h_short = (uint32_t *)calloc(2ull * W, 4);
+    uint32_t *h_cls = (uint32_t *)calloc(6ull * W, 4), *h_stat = (uint32_t *)calloc(W, 4);
+    uint64_t *h_sum = (uint64_t *)calloc(4ull * W, 8), *h_u2 = (uint64_t *)calloc(W, 8), *h_ties = (uint64_t *)calloc(W, 8);
+    res->n_reads = h_nr; res->n_short = h_short; res->cls = h_cls; res->sum = h_sum; res->u2 = h_u2; res->ties = h_ties;
+    res->status = h_stat;
+    std::vector<void *> tmp;                                  // this call's device arrays
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto done = [&](int rc) {
+        (void)hipStreamSynchronize(st);
+        for (void *p : tmp) (void)hipFree(p);
+        for (auto e : ev) if (e) (void)hipEventDestroy(e);
+        if (rc) pf_rank_free(res); else *out = res;
+        return rc;
+    };
+    if (!h_nr || !h_short || !h_cls || !h_stat || !h_sum || !h_u2 || !h_ties) return done(PF_ERR_NOMEM);
+    auto talloc = [&](void **p, size_t bytes) {
+        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
+        tmp.push_back(*p);
+        return PF_OK;
+    };
+    std::vector<rank_out> h_out;
+    try { h_out.resize(W); } catch (...) { return done(PF_ERR_NOMEM); }
+    void *p_hp = nullptr, *p_out = nullptr;
+    if ((read_hp && R && talloc(&p_hp, R)) || talloc(&p_out, sizeof(rank_out) * (size_t)W)) return done(PF_ERR_NOMEM);
+    rank_args a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.min_calls = min_calls; a.force_wide = (uint32_t)fw;
+    a.win_start = d.win_start; a.win_end = d.win_end; a.win_read_off = d.win_read_off;
+    a.read_hp = d.read_hp;
+    a.read_call_off = d.read_call_off; a.read_call_end = d.read_call_end;
+    a.call_pos = d.call_pos; a.call_cat = d.call_cat;
+    a.out = static_cast<rank_out *>(p_out);
+    if (p_hp) {
+        if (hipMemcpyAsync(p_hp, read_hp, R, hipMemcpyHostToDevice, st) != hipSuccess) return done(PF_ERR_HIP);
+        a.read_hp = static_cast<const uint8_t *>(p_hp);
+    }
+    for (auto &e : ev)
+        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
+    if (hipEventRecord(ev[0], st) != hipSuccess) return done(PF_ERR_HIP);
+    hipLaunchKernelGGL(pf_rank_test, dim3(W), dim3(nt), 0, st, a);
+    if (hipGetLastError() != hipSuccess || hipEventRecord(ev[1], st) != hipSuccess ||
+        hipMemcpyAsync(h_out.data(), p_out, sizeof(rank_out) * (size_t)W, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return done(PF_ERR_HIP);
+    float ms = 0.0f;
+    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+    (void)hipGetLastError();
+    for (uint32_t w = 0; w < W; w++) {
+        const rank_out &o = h_out[w];
+        if (o.status == RANK_ST_LIMIT) {
+            fprintf(stderr, "[E::pomfret_amd] ranktest: a window holds 2^31 or more calls\n");
+            return done(PF_ERR_LIMIT);
+        }
+        for (int k = 0; k < 4; k++) h_sum[4ull * w + k] = o.sum[k];
+        for (int k = 0; k < 2; k++) { h_nr[2ull * w + k] = o.n_reads[k]; h_short[2ull * w + k] = o.n_short[k]; }
+        for (int k = 0; k < 6; k++) h_cls[6ull * w + k] = o.cls[k];
+        h_u2[w] = o.u2;
+        h_ties[w] = o.ties;
+        h_stat[w] = o.status;
+    }
+    res->ms_kernels = ms;
+    return done(PF_OK);
+}

@@ -37,6 +37,7 @@ from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfH
                   AssignConfig, HAPMETH_TAGCHECK_RULE_ONLY, PfAssign, PfHapmethAssign, PfHapmethAssignStats,
                   PfHapmethTagcheck, PfHapmethTagcheckStats, PfTagcheck, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup,
                   HmmConfig, PfHapmethHmm, PfHapmethHmmStats, PfHapmethRegions, PfHapmethRegionsStats, PfRegionRec,
+                  PfHapmethRank, PfHapmethRankStats, PfRankRec,
                   REGION_ELIGIBLE, REGION_SPLIT)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
@@ -144,6 +145,15 @@ def _bind():
                                          C.POINTER(PfHapmethDmrStats), C.POINTER(PfHapmethHmmStats),
                                          C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
                                          C.POINTER(PfHapmethTagcheckStats), C.POINTER(PfHapmethRegionsStats)]
+    L.pf_hapmeth_run_rank.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethHmm),
+                                      C.POINTER(PfHapmethPerm), C.POINTER(PfHapmethAssign), C.POINTER(PfHapmethTagcheck),
+                                      C.POINTER(PfHapmethRegions), C.POINTER(PfHapmethRank), C.POINTER(PfHapmethStats),
+                                      C.POINTER(PfHapmethDmrStats), C.POINTER(PfHapmethHmmStats),
+                                      C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
+                                      C.POINTER(PfHapmethTagcheckStats), C.POINTER(PfHapmethRegionsStats),
+                                      C.POINTER(PfHapmethRankStats)]
+    L.pf_bh_adjust_p.argtypes = [vp, vp, C.c_uint64, vp]
+    L.pf_write_rank.argtypes = [C.c_char_p, C.POINTER(PfRankRec), C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pf_regions_load.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(vp)]
     L.pf_regions_contig.argtypes = [vp, C.c_uint32, C.POINTER(C.POINTER(C.c_uint32)), C.POINTER(C.POINTER(C.c_uint32)),
                                     C.POINTER(C.POINTER(C.c_char_p)), C.POINTER(C.c_uint64)]
@@ -518,7 +528,8 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
                   job_windows: int = 0, dmr: Optional[DmrConfig] = None, dmr_max_p: float = 1.0,
                   dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1,
                   assign: Optional[AssignConfig] = None, tag_check=False,
-                  dmr_hmm: Optional[HmmConfig] = None, regions: Optional[str] = None) -> Dict:
+                  dmr_hmm: Optional[HmmConfig] = None, regions: Optional[str] = None, dmr_rank: bool = False,
+                  dmr_rank_min_calls: int = 3) -> Dict:
     """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
@@ -573,7 +584,17 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     Benjamini-Hochberg q-value over the run's tested regions.  Adds
     regions_path, n_regions, n_regions_unknown_contig, n_regions_outside (not
     wholly inside `region`), n_regions_split, n_tested, n_untested and
-    regions_ms_kernels to the dict, in place of the dmr entries."""
+    regions_ms_kernels to the dict, in place of the dmr entries.
+    dmr_rank: True (`--dmr-rank`; needs dmr or regions) also writes out_prefix +
+    .hapmeth.rank.tsv, one line per region of the second pass (the ones
+    dmr_perm tests) with the read-level Mann-Whitney rank-sum test between the
+    haplotypes (pf_write_rank has the columns): every read counts once, with
+    its own methylation fraction inside the region, if it has at least
+    dmr_rank_min_calls calls there (1 .. 65535; a choice, not a measured
+    optimum).  rank_p is the asymptotic two-sided p-value (approximate below
+    about eight reads per haplotype), rank_q its Benjamini-Hochberg q-value
+    with regions, "." with found regions.  Adds rank_path, rank_tested,
+    rank_untested, rank_records and rank_ms_kernels to the dict."""
     L = _bind()
     if regions is not None:
         if dmr_hmm is not None:
@@ -590,6 +611,10 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         raise PomfretError("hapmeth_files: dmr_hmm needs dmr")
     if isinstance(tag_check, AssignConfig) and assign is not None:
         raise PomfretError("hapmeth_files: with assign, tag_check checks assign's rule: pass True")
+    if dmr_rank and dmr is None:
+        raise PomfretError("hapmeth_files: dmr_rank needs dmr or regions")
+    if dmr_rank and not 1 <= int(dmr_rank_min_calls) <= 65535:
+        raise PomfretError("hapmeth_files: dmr_rank_min_calls is 1 .. 65535")
     lc = lcfg or LoadConfig(min_len=0)
     o = PfHapmethOpts(bam.encode(), out_prefix.encode(), region.encode() if region else None, int(chunk_size),
                       int(job_windows), lc.to_c(), int(threads), int(bool(host_fetch)), int(device), 0)
@@ -601,7 +626,21 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         dst = PfHapmethDmrStats()
         pm = PfHapmethPerm(int(dmr_perm), int(dmr_seed))
         pst = PfHapmethPermStats()
-        if regions is not None:
+        if dmr_rank:
+            rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
+            am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
+            tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
+            rg = PfHapmethRegions(regions.encode()) if regions is not None else None
+            hm = PfHapmethHmm(dmr_hmm.to_c()) if dmr_hmm is not None else None
+            km, kst = PfHapmethRank(int(dmr_rank_min_calls)), PfHapmethRankStats()
+            hst, ast, tst, rst = PfHapmethHmmStats(), PfHapmethAssignStats(), PfHapmethTagcheckStats(), PfHapmethRegionsStats()
+            _check(L.pf_hapmeth_run_rank(C.byref(o), C.byref(d), C.byref(hm) if hm is not None else None,
+                                         C.byref(pm) if dmr_perm else None,
+                                         C.byref(am) if assign is not None or tag_check else None,
+                                         C.byref(tm) if tag_check else None, C.byref(rg) if rg is not None else None,
+                                         C.byref(km), C.byref(st), C.byref(dst), C.byref(hst), C.byref(pst), C.byref(ast),
+                                         C.byref(tst), C.byref(rst), C.byref(kst)), "pf_hapmeth_run_rank")
+        elif regions is not None:
             rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
             am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
             tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
@@ -654,6 +693,10 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         if dmr_perm:
             res.update(n_tested=int(pst.n_tested), n_untested=int(pst.n_untested), perm_records=int(pst.n_records),
                        perm_ms_kernels=float(pst.ms_kernels))
+        if dmr_rank:
+            res.update(rank_path=out_prefix + ".hapmeth.rank.tsv", rank_tested=int(kst.n_tested),
+                       rank_untested=int(kst.n_untested), rank_records=int(kst.n_records),
+                       rank_ms_kernels=float(kst.ms_kernels))
         if assign is not None:
             res.update(assign_path=out_prefix + ".hapmeth.assign.tsv", n_assign_lines=int(ast.n_lines),
                        n_assigned=int(ast.n_h1 + ast.n_h2), n_assigned_h1=int(ast.n_h1), n_assigned_h2=int(ast.n_h2),
@@ -767,6 +810,43 @@ def bh_adjust(hits, tested, n_perm: int) -> np.ndarray:
     q = np.zeros(max(h.size, 1), np.float64)
     _check(L.pf_bh_adjust(h.ctypes.data, t.ctypes.data, h.size, int(n_perm), q.ctypes.data), "pf_bh_adjust")
     return q[:h.size]
+
+
+def bh_adjust_p(p, tested) -> np.ndarray:
+    """Benjamini-Hochberg q-values of the tested entries from p-values given as
+    doubles (pf_bh_adjust_p, host only): bh_adjust's rule and order of
+    operations; NaN for an untested entry."""
+    L = _bind()
+    pv = np.ascontiguousarray(p, np.float64).ravel()
+    t = np.ascontiguousarray(tested, np.uint8).ravel()
+    if pv.size != t.size:
+        raise PomfretError("bh_adjust_p: p and tested differ in length")
+    pv = np.concatenate([pv, np.zeros(1)])                    # never an empty buffer
+    t = np.concatenate([t, np.zeros(1, np.uint8)])
+    q = np.zeros(pv.size, np.float64)
+    _check(L.pf_bh_adjust_p(pv.ctypes.data, t.ctypes.data, pv.size - 1, q.ctypes.data), "pf_bh_adjust_p")
+    return q[:-1]
+
+
+def write_rank(path: str, recs, bh: bool = False) -> int:
+    """{prefix}.hapmeth.rank.tsv from records (pf_write_rank, host only).  recs:
+    dicts of chrom, start, end, n_reads [2], n_short [2], cls [6] (or [2][3]),
+    u2, ties and status -- a window of DeviceBatch.ranktest and its region.
+    bh: rank_q by Benjamini-Hochberg over the status-0 records, else ".".
+    Returns the records with a numeric rank_p."""
+    L = _bind()
+    arr = (PfRankRec * max(len(recs), 1))()
+    for k, r in enumerate(recs):
+        x = arr[k]
+        x.chrom, x.start, x.end = r["chrom"].encode(), int(r["start"]), int(r["end"])
+        for j in range(2):
+            x.reads[j], x.n_short[j] = int(r["n_reads"][j]), int(r["n_short"][j])
+        for j, v in enumerate(np.asarray(r["cls"]).ravel().tolist()):
+            x.cls[j] = int(v)
+        x.status, x.u2, x.ties = int(r["status"]), int(r["u2"]), int(r["ties"])
+    n = C.c_uint64()
+    _check(L.pf_write_rank(path.encode(), arr, len(recs), int(bool(bh)), C.byref(n)), "pf_write_rank")
+    return int(n.value)
 
 
 def write_regions(path: str, recs, perm: bool = False, n_perm: int = 0) -> int:
