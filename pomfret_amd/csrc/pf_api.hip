@@ -15,11 +15,14 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <memory>
 #include <thread>
 #include <vector>
 #include "pf_device.h"
 #include "pf_load.h"
 #include "pf_host.h"
+#include "pf_reads.h"
+#include "pf_call.h"
 #include "../../include/pomfret_amd.h"
 
 __global__ void pf_k12_sites_methmers(pf_dev_batch d);
@@ -1522,16 +1525,6 @@ extern "C" void pf_pileup_free(pf_pileup_t *p) {
     free(p);
 }
 
-// the tile in positions: PF_PILE_TILE=<n> (tests: tile edges at tiny shapes),
-// n a power of two in [64, PF_PILE_TILE_MAX]; 0 for any other value
-static uint32_t pile_tile() {
-    const char *e = getenv("PF_PILE_TILE");
-    if (!e) return PF_PILE_TILE;
-    const long n = atol(e);
-    if (n < 64 || n > PF_PILE_TILE_MAX || (n & (n - 1))) return 0;
-    return (uint32_t)n;
-}
-
 // dev == NULL: pf_batch_pileup.  Else the site CSR stays in HBM for a consumer
 // in another file (pf_assign.hip): *dev takes over win_off, pos and cnt
 // (pf_pile_dev_free), nothing but the site count is copied back, *out is not
@@ -1543,7 +1536,7 @@ static int pile_run(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *read_hp, uint3
     if (out) *out = nullptr;
     if (dev) memset(dev, 0, sizeof *dev);
     if (b->n_launch != b->n_finish) return PF_ERR_ARG;       // a run is in flight
-    const uint32_t T = pile_tile();
+    const uint32_t T = pf_env_pow2("PF_PILE_TILE", 64, PF_PILE_TILE_MAX, PF_PILE_TILE);
     if (!T) return PF_ERR_ARG;
     HIPCHK(hipSetDevice(ctx->device));
     // record level: K0, scan and pack size the batch and leave its reads and calls
@@ -1557,133 +1550,102 @@ static int pile_run(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *read_hp, uint3
     const pf_dev_batch &d = b->d;
 
     pf_pileup_t *res = (pf_pileup_t *)calloc(1, sizeof(pf_pileup_t));
+    if (!res) return PF_ERR_NOMEM;
+    std::unique_ptr<pf_pileup_t, void (*)(pf_pileup_t *)> own(res, pf_pileup_free);    // freed unless *out takes it
     uint64_t *h_win_off = (uint64_t *)calloc((size_t)W + 1, sizeof(uint64_t));
-    std::vector<void *> tmp;                                  // this call's device arrays
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto done = [&](int rc) {
-        (void)hipStreamSynchronize(st);
-        for (void *p : tmp) (void)hipFree(p);
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (rc || dev) {
-            if (res) { res->win_off = h_win_off; pf_pileup_free(res); } else free(h_win_off);
-        } else
-            *out = res;
-        return rc;
-    };
-    if (!res || !h_win_off) return done(PF_ERR_NOMEM);
-    res->n_windows = W;
     res->win_off = h_win_off;
+    if (!h_win_off) return PF_ERR_NOMEM;
+    res->n_windows = W;
     if (dev) dev->W = W;
-    if (W == 0) return done(PF_OK);
+    auto ok = [&]() {
+        if (!dev) *out = own.release();
+        return PF_OK;
+    };
+    if (W == 0) return ok();
 
     // items: the tiles of every window
     std::vector<uint32_t> hws(W), hwe(W), tile_off((size_t)W + 1, 0);
+    uint64_t n_sites = 0;
+    uint32_t stt = 0;
+    pf_call call(st);
     if (hipMemcpyAsync(hws.data(), d.win_start, 4ull * W, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipMemcpyAsync(hwe.data(), d.win_end, 4ull * W, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
+        return PF_ERR_HIP;
     uint64_t n_items = 0;
     for (uint32_t w = 0; w < W; w++) {
         n_items += hwe[w] > hws[w] ? ((uint64_t)(hwe[w] - hws[w]) + T - 1) / T : 0;
-        if (n_items > 0x7FFFFFFFull) return done(PF_ERR_LIMIT);      // one workgroup per item
+        if (n_items > 0x7FFFFFFFull) return PF_ERR_LIMIT;            // one workgroup per item
         tile_off[w + 1] = (uint32_t)n_items;
     }
-    if (n_items == 0) return done(PF_OK);
+    if (n_items == 0) return ok();
 
     pf_pile_args a;
     memset(&a, 0, sizeof a);
     a.W = W; a.T = T; a.n_items = (uint32_t)n_items;
-    a.win_start = d.win_start; a.win_end = d.win_end; a.win_read_off = d.win_read_off;
-    a.read_hp = d.read_hp;
-    a.read_call_off = d.read_call_off; a.read_call_end = d.read_call_end;
-    a.call_pos = d.call_pos; a.call_cat = d.call_cat;
-    auto talloc = [&](void **p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
-        tmp.push_back(*p);
-        return PF_OK;
-    };
-    void *p_hp = nullptr, *p_to = nullptr, *p_ic = nullptr, *p_io = nullptr, *p_wo = nullptr, *p_st = nullptr;
-    if ((read_hp && R && talloc(&p_hp, R)) || talloc(&p_to, 4ull * (W + 1)) || talloc(&p_ic, 4ull * n_items) ||
-        talloc(&p_io, 8ull * (n_items + 1)) || talloc(&p_wo, 8ull * (W + 1)) || talloc(&p_st, 8))
-        return done(PF_ERR_NOMEM);
-    if (p_hp) {
-        if (hipMemcpyAsync(p_hp, read_hp, R, hipMemcpyHostToDevice, st) != hipSuccess) return done(PF_ERR_HIP);
-        a.read_hp = static_cast<const uint8_t *>(p_hp);
-    }
+    a.v = pf_calls_view_of(d);
+    const int hrc = call.upload_hp(read_hp, R, a.v);
+    if (hrc) return hrc;
+    void *p_to = nullptr;
+    if (!(p_to = call.alloc(4ull * (W + 1))) || !(a.item_cnt = static_cast<uint32_t *>(call.alloc(4ull * n_items))) ||
+        !(a.item_off = static_cast<uint64_t *>(call.alloc(8ull * (n_items + 1)))) ||
+        !(a.win_off = static_cast<uint64_t *>(call.alloc(8ull * (W + 1)))) || !(a.status = static_cast<uint32_t *>(call.alloc(8))))
+        return PF_ERR_NOMEM;
     a.tile_off = static_cast<uint32_t *>(p_to);
-    a.item_cnt = static_cast<uint32_t *>(p_ic);
-    a.item_off = static_cast<uint64_t *>(p_io);
-    a.win_off = static_cast<uint64_t *>(p_wo);
-    a.status = static_cast<uint32_t *>(p_st);
     const uint32_t lds = 12u * T;
     if (lds > 65536u) {
         const void *f[2] = {(const void *)pf_pile_count, (const void *)pf_pile_emit};
-        if (raise_lds_limit(ctx->device, 4, f, 2, lds)) return done(PF_ERR_HIP);
+        if (raise_lds_limit(ctx->device, 4, f, 2, lds)) return PF_ERR_HIP;
     }
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
-    uint64_t n_sites = 0;
-    uint32_t stt = 0;
     if (hipMemcpyAsync(p_to, tile_off.data(), 4ull * (W + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemsetAsync(p_st, 0, 8, st) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess)
-        return done(PF_ERR_HIP);
+        hipMemsetAsync(a.status, 0, 8, st) != hipSuccess || !call.mark(0))
+        return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_pile_count, dim3(a.n_items), dim3(PF_PILE_THREADS), lds, st, a);
-    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_pile_scan, dim3(1), dim3(PF_PILE_SCAN_THREADS), 0, st, a);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(ev[1], st) != hipSuccess ||
+    if (hipGetLastError() != hipSuccess || !call.mark(1) ||
         hipMemcpyAsync(&n_sites, a.item_off + a.n_items, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&stt, p_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&stt, a.status, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
+        return PF_ERR_HIP;
     if (stt) {
         fprintf(stderr, "[E::pomfret_amd] pileup: a count passed 65,535 (duplicate call entries)\n");
-        return done(PF_ERR_LIMIT);
+        return PF_ERR_LIMIT;
     }
-    float ms0 = 0.0f, ms1 = 0.0f;
-    if (n_sites && dev) {
-        void *p_op = nullptr, *p_oc = nullptr;
-        if (talloc(&p_op, 4ull * n_sites) || talloc(&p_oc, 24ull * n_sites)) return done(PF_ERR_NOMEM);
-        a.out_pos = static_cast<uint32_t *>(p_op);
-        a.out_cnt = static_cast<uint32_t *>(p_oc);
-        if (hipEventRecord(ev[2], st) != hipSuccess) return done(PF_ERR_HIP);
+    float ms1 = 0.0f;
+    if (n_sites) {
+        uint32_t *h_pos = nullptr, *h_cnt = nullptr;
+        if (!dev) {
+            res->pos = h_pos = (uint32_t *)malloc(4ull * n_sites);
+            res->cnt = h_cnt = (uint32_t *)malloc(24ull * n_sites);
+            if (!h_pos || !h_cnt) return PF_ERR_NOMEM;
+        }
+        if (!(a.out_pos = static_cast<uint32_t *>(call.alloc(4ull * n_sites))) ||
+            !(a.out_cnt = static_cast<uint32_t *>(call.alloc(24ull * n_sites))))
+            return PF_ERR_NOMEM;
+        if (!call.mark(2)) return PF_ERR_HIP;
         hipLaunchKernelGGL(pf_pile_emit, dim3(a.n_items), dim3(PF_PILE_THREADS), lds, st, a);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[3], st) != hipSuccess ||
+        if (hipGetLastError() != hipSuccess || !call.mark(3) ||
+            (!dev && (hipMemcpyAsync(h_pos, a.out_pos, 4ull * n_sites, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                      hipMemcpyAsync(h_cnt, a.out_cnt, 24ull * n_sites, hipMemcpyDeviceToHost, st) != hipSuccess ||
+                      hipMemcpyAsync(h_win_off, a.win_off, 8ull * (W + 1), hipMemcpyDeviceToHost, st) != hipSuccess)) ||
             hipStreamSynchronize(st) != hipSuccess)
-            return done(PF_ERR_HIP);
-        (void)hipEventElapsedTime(&ms1, ev[2], ev[3]);
-        // the three arrays outlive this call
-        for (void *keep : {p_wo, p_op, p_oc})
-            for (size_t i = 0; i < tmp.size(); i++)
-                if (tmp[i] == keep) { tmp.erase(tmp.begin() + (long)i); break; }
-        dev->n_sites = n_sites;
-        dev->win_off = static_cast<uint64_t *>(p_wo);
-        dev->pos = a.out_pos;
-        dev->cnt = a.out_cnt;
-    } else if (n_sites) {
-        uint32_t *h_pos = (uint32_t *)malloc(4ull * n_sites), *h_cnt = (uint32_t *)malloc(24ull * n_sites);
-        res->pos = h_pos;
-        res->cnt = h_cnt;
-        void *p_op = nullptr, *p_oc = nullptr;
-        if (!h_pos || !h_cnt || talloc(&p_op, 4ull * n_sites) || talloc(&p_oc, 24ull * n_sites))
-            return done(PF_ERR_NOMEM);
-        a.out_pos = static_cast<uint32_t *>(p_op);
-        a.out_cnt = static_cast<uint32_t *>(p_oc);
-        if (hipEventRecord(ev[2], st) != hipSuccess) return done(PF_ERR_HIP);
-        hipLaunchKernelGGL(pf_pile_emit, dim3(a.n_items), dim3(PF_PILE_THREADS), lds, st, a);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[3], st) != hipSuccess ||
-            hipMemcpyAsync(h_pos, p_op, 4ull * n_sites, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(h_cnt, p_oc, 24ull * n_sites, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(h_win_off, p_wo, 8ull * (W + 1), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipStreamSynchronize(st) != hipSuccess)
-            return done(PF_ERR_HIP);
-        (void)hipEventElapsedTime(&ms1, ev[2], ev[3]);
+            return PF_ERR_HIP;
+        ms1 = call.ms(2, 3);
+        if (dev) {                                   // the three arrays outlive this call
+            call.release(a.win_off);
+            call.release(a.out_pos);
+            call.release(a.out_cnt);
+            dev->n_sites = n_sites;
+            dev->win_off = a.win_off;
+            dev->pos = a.out_pos;
+            dev->cnt = a.out_cnt;
+        }
     }
-    (void)hipEventElapsedTime(&ms0, ev[0], ev[1]);
-    (void)hipGetLastError();
     res->n_sites = n_sites;
-    res->ms_kernels = ms0 + ms1;
-    if (dev) dev->ms_kernels = ms0 + ms1;
-    return done(PF_OK);
+    res->ms_kernels = call.ms(0, 1) + ms1;
+    if (dev) dev->ms_kernels = res->ms_kernels;
+    return ok();
 }
 
 extern "C" int pf_batch_pileup(pf_ctx_t *ctx, pf_dbatch_t *b, const uint8_t *read_hp, uint32_t n_hp,

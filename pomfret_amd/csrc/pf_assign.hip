@@ -31,9 +31,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <vector>
+#include <memory>
 #include "pf_device.h"
 #include "pf_llr.h"                 // ilog2_q16, site_weights: shared with pf_tagcheck.hip
+#include "pf_reads.h"
+#include "pf_call.h"
 #include "../../include/pomfret_amd.h"
 
 struct pf_ctx;
@@ -51,11 +53,7 @@ struct assign_args {
     uint32_t W, T, min_cov, min_calls;
     long long min_llr;
     uint64_t n_sites;
-    const uint32_t *win_read_off;
-    const uint8_t *read_hp;                          /* the batch's tags or the caller's */
-    const uint64_t *read_call_off, *read_call_end;
-    const uint32_t *call_pos;
-    const uint8_t *call_cat;
+    pf_calls_view v;                                 /* read_hp: the batch's tags or the caller's */
     const uint64_t *site_off;                        /* [W+1] */
     const uint32_t *site_pos;                        /* [n_sites] */
     const uint32_t *site_cnt;                        /* [n_sites*6] */
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(PF_ASSIGN_THREADS) void pf_assign_score(assign_args
     int32_t *s_wm = reinterpret_cast<int32_t *>(s_tile + T), *s_wu = reinterpret_cast<int32_t *>(s_tile + 2u * T);
     if (tid < 3u) s_n[tid] = 0u;
     const uint64_t s0 = a.site_off[w], s1 = a.site_off[w + 1];
-    const uint32_t r0 = a.win_read_off[w], r1 = a.win_read_off[w + 1];
+    const uint32_t r0 = a.v.win_read_off[w], r1 = a.v.win_read_off[w + 1];
     const uint64_t n_tiles = s1 > s0 ? (s1 - s0 + T - 1) / T : 1;      // a window without sites: one empty tile
     for (uint64_t t = 0; t < n_tiles; t++) {
         const uint64_t b0 = s0 + t * T;
@@ -106,33 +104,33 @@ __global__ __launch_bounds__(PF_ASSIGN_THREADS) void pf_assign_score(assign_args
         for (uint32_t g = r0 + wave * 64u; g < r1; g += PF_ASSIGN_WAVES * 64u) {
             const uint32_t r = g + lane;
             const bool have = r >= g && r < r1;
-            const uint32_t hp = have ? a.read_hp[r] : 0u;
+            const uint32_t hp = have ? a.v.read_hp[r] : 0u;
             const bool cand = have && hp == 254u;
             uint64_t lo = 0, c1 = 0;
             if (cand && n) {
-                lo = a.read_call_off[r];
-                c1 = a.read_call_end[r];
+                lo = a.v.read_call_off[r];
+                c1 = a.v.read_call_end[r];
             }
             // a slice that ends left of the tile or starts right of it needs no search
-            if (lo < c1 && (a.call_pos[c1 - 1] < p_lo || a.call_pos[lo] > p_hi)) lo = c1;
+            if (lo < c1 && (a.v.call_pos[c1 - 1] < p_lo || a.v.call_pos[lo] > p_hi)) lo = c1;
             for (uint64_t hi = c1; lo < hi;) {
                 const uint64_t mid = lo + (hi - lo) / 2;
-                if (a.call_pos[mid] < p_lo) lo = mid + 1; else hi = mid;
+                if (a.v.call_pos[mid] < p_lo) lo = mid + 1; else hi = mid;
             }
-            const bool hit = lo < c1 && a.call_pos[lo] <= p_hi;
+            const bool hit = lo < c1 && a.v.call_pos[lo] <= p_hi;
             long long my_s = 0;
             uint32_t my_n = 0;
             for (uint64_t m = __ballot(hit); m; m &= m - 1) {
                 const int l = __builtin_ctzll(m);
-                const uint64_t s = ((uint64_t)(uint32_t)__shfl((int)(lo >> 32), l) << 32) | (uint32_t)__shfl((int)lo, l);
-                const uint64_t e = ((uint64_t)(uint32_t)__shfl((int)(c1 >> 32), l) << 32) | (uint32_t)__shfl((int)c1, l);
+                const uint64_t s = shfl64(lo, l);
+                const uint64_t e = shfl64(c1, l);
                 long long acc = 0;
                 uint32_t cn = 0;
                 for (uint64_t c0 = s; c0 < e; c0 += 64) {
                     const uint64_t c = c0 + lane;
                     const bool valid = c < e;
-                    const uint32_t p = valid ? a.call_pos[c] : 0u;
-                    const uint32_t cat = valid ? a.call_cat[c] : 2u;
+                    const uint32_t p = valid ? a.v.call_pos[c] : 0u;
+                    const uint32_t cat = valid ? a.v.call_cat[c] : 2u;
                     if (valid && p <= p_hi && cat < 2u) {     // p >= p_lo: the slice is sorted and starts at the bound
                         uint32_t k = 0;
                         for (uint32_t hi = n; k < hi;) {
@@ -214,33 +212,21 @@ extern "C" void pf_assign_free(pf_assign_t *p) {
     free(p);
 }
 
-// the tile in sites: PF_ASSIGN_TILE=<n> (tests: tile edges at tiny shapes), n a
-// power of two in [64, PF_ASSIGN_TILE]; 0 for any other value
-static uint32_t assign_tile() {
-    const char *e = getenv("PF_ASSIGN_TILE");
-    if (!e) return PF_ASSIGN_TILE;
-    if (*e < '0' || *e > '9') return 0;
-    char *end = nullptr;
-    const long n = strtol(e, &end, 10);
-    if (*end || n < 64 || n > PF_ASSIGN_TILE || (n & (n - 1))) return 0;
-    return (uint32_t)n;
-}
-
 extern "C" int pf_batch_assign(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, const pf_assign_cfg_t *cfg,
                                pf_assign_t **out) {
     if (!ctx || !db || !out || !cfg) return PF_ERR_ARG;
     *out = nullptr;
-    const uint32_t T = assign_tile();
+    const uint32_t T = pf_env_pow2("PF_ASSIGN_TILE", 64, PF_ASSIGN_TILE, PF_ASSIGN_TILE);
     if (!T) return PF_ERR_ARG;
     pf_dev_batch d;
     const int vrc = pf_batch_calls_view(ctx, db, &d);
     if (vrc) return vrc;
     const uint32_t W = d.W, R = d.R;
     if (read_hp && n_hp != R) return PF_ERR_ARG;
-    hipStream_t st = pf_ctx_stream(ctx);
 
     pf_assign_t *res = (pf_assign_t *)calloc(1, sizeof(pf_assign_t));
     if (!res) return PF_ERR_NOMEM;
+    std::unique_ptr<pf_assign_t, void (*)(pf_assign_t *)> own(res, pf_assign_free);    // freed on every return but the last
     res->n_windows = W;
     res->n_reads = R;
     uint32_t *h_wro = (uint32_t *)calloc((size_t)W + 1, 4), *h_nu = (uint32_t *)calloc((size_t)R + 1, 4);
@@ -248,83 +234,58 @@ extern "C" int pf_batch_assign(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *re
     int64_t *h_llr = (int64_t *)calloc((size_t)R + 1, 8);
     uint8_t *h_hp = (uint8_t *)calloc((size_t)R + 1, 1);
     res->win_read_off = h_wro; res->n_used = h_nu; res->win_n = h_wn; res->llr = h_llr; res->hp = h_hp;
-    std::vector<void *> tmp;                                  // this call's device arrays
-    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (!h_wro || !h_nu || !h_wn || !h_llr || !h_hp) return PF_ERR_NOMEM;
     pf_pile_dev pd;
     memset(&pd, 0, sizeof pd);
-    auto done = [&](int rc) {
-        (void)hipStreamSynchronize(st);
-        for (void *p : tmp) (void)hipFree(p);
-        pf_pile_dev_free(&pd);
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (rc) pf_assign_free(res); else *out = res;
-        return rc;
-    };
-    if (!h_wro || !h_nu || !h_wn || !h_llr || !h_hp) return done(PF_ERR_NOMEM);
-    auto talloc = [&](void **p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
-        tmp.push_back(*p);
-        return PF_OK;
-    };
+    std::unique_ptr<pf_pile_dev, void (*)(pf_pile_dev *)> pd_own(&pd, pf_pile_dev_free);
+    pf_call call(pf_ctx_stream(ctx));
+    hipStream_t st = call.st;
     // the site table under this call's tags (the view above has run the load stage)
     const int prc = pf_batch_pileup_dev(ctx, db, read_hp, n_hp, &pd);
-    if (prc) return done(prc);
+    if (prc) return prc;
 
-    void *p_hp = nullptr, *p_so = nullptr, *p_w = nullptr, *p_nu = nullptr, *p_llr = nullptr, *p_ohp = nullptr, *p_wn = nullptr;
-    if ((read_hp && R && talloc(&p_hp, R)) || (!pd.n_sites && talloc(&p_so, 8ull * ((size_t)W + 1))) ||
-        (pd.n_sites && talloc(&p_w, 8ull * pd.n_sites)) || talloc(&p_nu, 4ull * R) || talloc(&p_llr, 8ull * R) ||
-        talloc(&p_ohp, R) || talloc(&p_wn, 12ull * W))
-        return done(PF_ERR_NOMEM);
     assign_args a;
     memset(&a, 0, sizeof a);
     a.W = W; a.T = T; a.min_cov = cfg->min_cov; a.min_calls = cfg->min_calls;
     a.min_llr = (long long)cfg->min_llr_q16;
     a.n_sites = pd.n_sites;
-    a.win_read_off = d.win_read_off;
-    a.read_hp = d.read_hp;
-    a.read_call_off = d.read_call_off; a.read_call_end = d.read_call_end;
-    a.call_pos = d.call_pos; a.call_cat = d.call_cat;
+    a.v = pf_calls_view_of(d);
+    const int hrc = call.upload_hp(read_hp, R, a.v);
+    if (hrc) return hrc;
+    void *p_so = nullptr;
+    if ((!pd.n_sites && !(p_so = call.alloc(8ull * ((size_t)W + 1)))) ||
+        (pd.n_sites && !(a.site_w = static_cast<int2 *>(call.alloc(8ull * pd.n_sites)))) ||
+        !(a.n_used = static_cast<uint32_t *>(call.alloc(4ull * R))) || !(a.llr = static_cast<long long *>(call.alloc(8ull * R))) ||
+        !(a.hp = static_cast<uint8_t *>(call.alloc(R))) || !(a.win_n = static_cast<uint32_t *>(call.alloc(12ull * W))))
+        return PF_ERR_NOMEM;
     a.site_off = pd.n_sites ? pd.win_off : static_cast<const uint64_t *>(p_so);
     a.site_pos = pd.pos; a.site_cnt = pd.cnt;
-    a.site_w = static_cast<int2 *>(p_w);
-    a.n_used = static_cast<uint32_t *>(p_nu);
-    a.llr = static_cast<long long *>(p_llr);
-    a.hp = static_cast<uint8_t *>(p_ohp);
-    a.win_n = static_cast<uint32_t *>(p_wn);
-    if (p_hp) {
-        if (hipMemcpyAsync(p_hp, read_hp, R, hipMemcpyHostToDevice, st) != hipSuccess) return done(PF_ERR_HIP);
-        a.read_hp = static_cast<const uint8_t *>(p_hp);
-    }
     // a read outside every window keeps its tag and zeros
     if ((p_so && hipMemsetAsync(p_so, 0, 8ull * ((size_t)W + 1), st) != hipSuccess) ||
-        hipMemsetAsync(p_nu, 0, R ? 4ull * R : 8, st) != hipSuccess || hipMemsetAsync(p_llr, 0, R ? 8ull * R : 8, st) != hipSuccess ||
-        hipMemsetAsync(p_wn, 0, W ? 12ull * W : 8, st) != hipSuccess ||
-        (R && hipMemcpyAsync(p_ohp, a.read_hp, R, hipMemcpyDeviceToDevice, st) != hipSuccess))
-        return done(PF_ERR_HIP);
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
-    if (hipEventRecord(ev[0], st) != hipSuccess) return done(PF_ERR_HIP);
+        hipMemsetAsync(a.n_used, 0, R ? 4ull * R : 8, st) != hipSuccess || hipMemsetAsync(a.llr, 0, R ? 8ull * R : 8, st) != hipSuccess ||
+        hipMemsetAsync(a.win_n, 0, W ? 12ull * W : 8, st) != hipSuccess ||
+        (R && hipMemcpyAsync(a.hp, a.v.read_hp, R, hipMemcpyDeviceToDevice, st) != hipSuccess))
+        return PF_ERR_HIP;
+    if (!call.mark(0)) return PF_ERR_HIP;
     if (pd.n_sites) {
         const uint64_t nb = (pd.n_sites + 255u) / 256u;
-        if (nb > 0x7FFFFFFFull) return done(PF_ERR_LIMIT);
+        if (nb > 0x7FFFFFFFull) return PF_ERR_LIMIT;
         hipLaunchKernelGGL(pf_assign_weights, dim3((uint32_t)nb), dim3(256), 0, st, a);
-        if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+        if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     }
     if (W) {
         hipLaunchKernelGGL(pf_assign_score, dim3(W), dim3(PF_ASSIGN_THREADS), 12u * T, st, a);
-        if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+        if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     }
-    if (hipEventRecord(ev[1], st) != hipSuccess ||
+    if (!call.mark(1) ||
         (W && hipMemcpyAsync(h_wro, d.win_read_off, 4ull * ((size_t)W + 1), hipMemcpyDeviceToHost, st) != hipSuccess) ||
-        (R && (hipMemcpyAsync(h_nu, p_nu, 4ull * R, hipMemcpyDeviceToHost, st) != hipSuccess ||
-               hipMemcpyAsync(h_llr, p_llr, 8ull * R, hipMemcpyDeviceToHost, st) != hipSuccess ||
-               hipMemcpyAsync(h_hp, p_ohp, R, hipMemcpyDeviceToHost, st) != hipSuccess)) ||
-        (W && hipMemcpyAsync(h_wn, p_wn, 12ull * W, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+        (R && (hipMemcpyAsync(h_nu, a.n_used, 4ull * R, hipMemcpyDeviceToHost, st) != hipSuccess ||
+               hipMemcpyAsync(h_llr, a.llr, 8ull * R, hipMemcpyDeviceToHost, st) != hipSuccess ||
+               hipMemcpyAsync(h_hp, a.hp, R, hipMemcpyDeviceToHost, st) != hipSuccess)) ||
+        (W && hipMemcpyAsync(h_wn, a.win_n, 12ull * W, hipMemcpyDeviceToHost, st) != hipSuccess) ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-    (void)hipGetLastError();
-    res->ms_kernels = ms;
-    return done(PF_OK);
+        return PF_ERR_HIP;
+    res->ms_kernels = call.ms(0, 1);
+    *out = own.release();
+    return PF_OK;
 }

@@ -150,6 +150,16 @@ struct pf_dev_batch {
     uint32_t mask_n;                   /* 0: no mask */
 };
 
+/* What a per-window consumer of the batch's calls reads (pf_reads.h has the
+ * scan over it and pf_calls_view_of, which fills it from a pf_dev_batch) */
+struct pf_calls_view {
+    const uint32_t *win_start, *win_end, *win_read_off;
+    const uint8_t *read_hp;                          /* the batch's tags or the caller's */
+    const uint64_t *read_call_off, *read_call_end;   /* read r's calls: [off[r], end[r]) */
+    const uint32_t *call_pos;
+    const uint8_t *call_cat;
+};
+
 /* The per-haplotype pileup (pf_pileup.hip): one workgroup per item, an item
  * being one tile of T positions of one window; window w owns the items
  * [tile_off[w], tile_off[w+1]), tile j covering [win_start + j*T, +T) cut at
@@ -158,11 +168,7 @@ struct pf_dev_batch {
  * writes its sites at item_off. */
 struct pf_pile_args {
     uint32_t W, T, n_items;
-    const uint32_t *win_start, *win_end, *win_read_off;
-    const uint8_t *read_hp;                          /* the batch's tags or the caller's */
-    const uint64_t *read_call_off, *read_call_end;
-    const uint32_t *call_pos;
-    const uint8_t *call_cat;
+    pf_calls_view v;
     const uint32_t *tile_off;                        /* [W+1] */
     uint32_t *item_cnt;                              /* [n_items] */
     uint64_t *item_off;                              /* [n_items+1] */

@@ -32,9 +32,10 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
-#include <vector>
+#include <memory>
 #include "pf_device.h"
 #include "pf_site.h"
+#include "pf_call.h"
 #include "../../include/pomfret_amd.h"
 
 struct pf_ctx;
@@ -314,16 +315,6 @@ extern "C" void pf_dmr_free(pf_dmr_t *d) {
     free(d);
 }
 
-// sites per workgroup: PF_DMR_BLOCK=<n> (tests: block edges at tiny shapes), n
-// a power of two in [64, PF_DMR_BLOCK]; 0 for any other value
-static uint32_t dmr_block_env() {
-    const char *e = getenv("PF_DMR_BLOCK");
-    if (!e) return PF_DMR_BLOCK;
-    const long n = atol(e);
-    if (n < 64 || n > PF_DMR_BLOCK || (n & (n - 1))) return 0;
-    return (uint32_t)n;
-}
-
 extern "C" int pf_dmr_regions_block(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w0, uint32_t w1,
                                     const pf_dmr_cfg_t *cfg, const uint32_t *breaks, uint32_t n_breaks, uint32_t block,
                                     pf_dmr_t **out) {
@@ -331,7 +322,7 @@ extern "C" int pf_dmr_regions_block(pf_ctx_t *ctx, const pf_pileup_t *pile, uint
         (n_breaks && !breaks) || cfg->min_delta_pct > 100u)
         return PF_ERR_ARG;
     *out = nullptr;
-    const uint32_t B = block ? block : dmr_block_env();
+    const uint32_t B = block ? block : pf_env_pow2("PF_DMR_BLOCK", 64, PF_DMR_BLOCK, PF_DMR_BLOCK);
     if (B < 64u || B > PF_DMR_BLOCK || (B & (B - 1u))) return PF_ERR_ARG;
     for (uint32_t i = 1; i < n_breaks; i++)
         if (breaks[i] < breaks[i - 1]) return PF_ERR_ARG;
@@ -343,82 +334,63 @@ extern "C" int pf_dmr_regions_block(pf_ctx_t *ctx, const pf_pileup_t *pile, uint
     pf_dmr_t *res = (pf_dmr_t *)calloc(1, sizeof(pf_dmr_t));
     if (!res) return PF_ERR_NOMEM;
     if (n == 0) { *out = res; return PF_OK; }
-    if (hipSetDevice(pf_ctx_device(ctx)) != hipSuccess) { free(res); return PF_ERR_HIP; }
-    hipStream_t st = pf_ctx_stream(ctx);
-    std::vector<void *> tmp;                                  // this call's device arrays
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto done = [&](int rc) {
-        (void)hipStreamSynchronize(st);
-        for (void *p : tmp) (void)hipFree(p);
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (rc) pf_dmr_free(res); else *out = res;
-        return rc;
-    };
-    auto talloc = [&](void **p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
-        tmp.push_back(*p);
-        return PF_OK;
-    };
+    std::unique_ptr<pf_dmr_t, void (*)(pf_dmr_t *)> own(res, pf_dmr_free);     // freed on every return but the last
+    if (hipSetDevice(pf_ctx_device(ctx)) != hipSuccess) return PF_ERR_HIP;
+    uint64_t tot[2] = {0, 0};
+    uint32_t stt = 0;
+    pf_call call(pf_ctx_stream(ctx));
+    hipStream_t st = call.st;
     dmr_args a;
     memset(&a, 0, sizeof a);
     a.n = (uint32_t)n; a.B = B; a.K = B > PF_DMR_THREADS ? B / PF_DMR_THREADS : 1u;
     a.n_blocks = (uint32_t)((n + B - 1) / B);
     a.min_cov = cfg->min_cov; a.min_delta_pct = cfg->min_delta_pct; a.max_gap = cfg->max_gap; a.min_sites = cfg->min_sites;
     a.n_brk = n_breaks;
-    void *p_pos = nullptr, *p_cnt = nullptr, *p_brk = nullptr, *p_agg = nullptr, *p_tot = nullptr, *p_st = nullptr;
-    if (talloc(&p_pos, 4ull * n) || talloc(&p_cnt, 24ull * n) || talloc(&p_brk, 4ull * n_breaks) ||
-        talloc(&p_agg, sizeof(dmr_agg) * (size_t)a.n_blocks) || talloc(&p_tot, 16) || talloc(&p_st, 8))
-        return done(PF_ERR_NOMEM);
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
+    void *p_pos = nullptr, *p_cnt = nullptr, *p_brk = nullptr;
+    if (!(p_pos = call.alloc(4ull * n)) || !(p_cnt = call.alloc(24ull * n)) || !(p_brk = call.alloc(4ull * n_breaks)) ||
+        !(a.agg = static_cast<dmr_agg *>(call.alloc(sizeof(dmr_agg) * (size_t)a.n_blocks))) ||
+        !(a.tot = static_cast<uint64_t *>(call.alloc(16))) || !(a.status = static_cast<uint32_t *>(call.alloc(8))))
+        return PF_ERR_NOMEM;
     const auto t0 = std::chrono::steady_clock::now();
     if (hipMemcpyAsync(p_pos, pile->pos + s0, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(p_cnt, pile->cnt + 6ull * s0, 24ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
         (n_breaks && hipMemcpyAsync(p_brk, breaks, 4ull * n_breaks, hipMemcpyHostToDevice, st) != hipSuccess) ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
+        return PF_ERR_HIP;
     res->ms_upload = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     a.pos = static_cast<const uint32_t *>(p_pos);
     a.cnt = static_cast<const uint32_t *>(p_cnt);
     a.brk = static_cast<const uint32_t *>(p_brk);
-    a.agg = static_cast<dmr_agg *>(p_agg);
-    a.tot = static_cast<uint64_t *>(p_tot);
-    a.status = static_cast<uint32_t *>(p_st);
-    uint64_t tot[2] = {0, 0};
-    uint32_t stt = 0;
-    if (hipMemsetAsync(p_st, 0, 8, st) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess) return done(PF_ERR_HIP);
+    if (hipMemsetAsync(a.status, 0, 8, st) != hipSuccess || !call.mark(0)) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_dmr_count, dim3(a.n_blocks), dim3(PF_DMR_THREADS), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_dmr_scan, dim3(1), dim3(PF_DMR_THREADS), 0, st, a);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(ev[1], st) != hipSuccess ||
-        hipMemcpyAsync(tot, p_tot, 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&stt, p_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+    if (hipGetLastError() != hipSuccess || !call.mark(1) ||
+        hipMemcpyAsync(tot, a.tot, 16, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&stt, a.status, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
-    if (stt & 1u) return done(PF_ERR_ARG);                    // positions not ascending over the range
-    if (stt & 2u) return done(PF_ERR_LIMIT);
-    float ms0 = 0.0f, ms1 = 0.0f;
+        return PF_ERR_HIP;
+    if (stt & 1u) return PF_ERR_ARG;                          // positions not ascending over the range
+    if (stt & 2u) return PF_ERR_LIMIT;
+    float ms1 = 0.0f;
     if (tot[0]) {
         pf_dmr_run_t *h = (pf_dmr_run_t *)malloc(sizeof(pf_dmr_run_t) * (size_t)tot[0]);
         res->runs = h;
-        void *p_out = nullptr;
-        if (!h || talloc(&p_out, sizeof(pf_dmr_run_t) * (size_t)tot[0])) return done(PF_ERR_NOMEM);
-        a.out = static_cast<pf_dmr_run_t *>(p_out);
+        if (!h || !(a.out = static_cast<pf_dmr_run_t *>(call.alloc(sizeof(pf_dmr_run_t) * (size_t)tot[0])))) return PF_ERR_NOMEM;
         a.n_out = tot[0];
-        if (hipEventRecord(ev[2], st) != hipSuccess) return done(PF_ERR_HIP);
+        if (!call.mark(2)) return PF_ERR_HIP;
         hipLaunchKernelGGL(pf_dmr_emit, dim3(a.n_blocks), dim3(PF_DMR_THREADS), 0, st, a);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[3], st) != hipSuccess ||
-            hipMemcpyAsync(h, p_out, sizeof(pf_dmr_run_t) * (size_t)tot[0], hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (hipGetLastError() != hipSuccess || !call.mark(3) ||
+            hipMemcpyAsync(h, a.out, sizeof(pf_dmr_run_t) * (size_t)tot[0], hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
-            return done(PF_ERR_HIP);
-        (void)hipEventElapsedTime(&ms1, ev[2], ev[3]);
+            return PF_ERR_HIP;
+        ms1 = call.ms(2, 3);
     }
-    (void)hipEventElapsedTime(&ms0, ev[0], ev[1]);
-    (void)hipGetLastError();
     res->n_runs = tot[0];
     res->n_informative = tot[1];
-    res->ms_kernels = ms0 + ms1;
-    return done(PF_OK);
+    res->ms_kernels = call.ms(0, 1) + ms1;
+    *out = own.release();
+    return PF_OK;
 }
 
 extern "C" int pf_dmr_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w0, uint32_t w1, const pf_dmr_cfg_t *cfg,
@@ -435,61 +407,41 @@ int pf_dmr_state_runs(pf_ctx_t *ctx, const uint32_t *d_pos, const uint32_t *d_cn
                       uint64_t *n_runs, float *ms) {
     *runs = nullptr; *n_runs = 0; *ms = 0.0f;
     if (n == 0) return PF_OK;
-    hipStream_t st = pf_ctx_stream(ctx);
-    std::vector<void *> tmp;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    pf_dmr_run_t *h = nullptr;
-    auto done = [&](int rc) {
-        (void)hipStreamSynchronize(st);
-        for (void *p : tmp) (void)hipFree(p);
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (rc) { free(h); *n_runs = 0; } else *runs = h;
-        return rc;
-    };
-    auto talloc = [&](void **p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
-        tmp.push_back(*p);
-        return PF_OK;
-    };
+    std::unique_ptr<pf_dmr_run_t, void (*)(void *)> h(nullptr, free);
+    uint64_t tot[2] = {0, 0};
+    pf_call call(pf_ctx_stream(ctx));
+    hipStream_t st = call.st;
     dmr_args a;
     memset(&a, 0, sizeof a);
     a.n = n; a.B = B; a.K = B > PF_DMR_THREADS ? B / PF_DMR_THREADS : 1u;
     a.n_blocks = (uint32_t)(((uint64_t)n + B - 1) / B);
     a.min_cov = cfg->min_cov; a.min_delta_pct = cfg->min_delta_pct; a.max_gap = cfg->max_gap; a.min_sites = cfg->min_sites;
     a.pos = d_pos; a.cnt = d_cnt; a.brk = d_brk; a.n_brk = n_brk; a.state = d_state;
-    void *p_agg = nullptr, *p_tot = nullptr, *p_st = nullptr;
-    if (talloc(&p_agg, sizeof(dmr_agg) * (size_t)a.n_blocks) || talloc(&p_tot, 16) || talloc(&p_st, 8)) return done(PF_ERR_NOMEM);
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
-    a.agg = static_cast<dmr_agg *>(p_agg);
-    a.tot = static_cast<uint64_t *>(p_tot);
-    a.status = static_cast<uint32_t *>(p_st);
-    uint64_t tot[2] = {0, 0};
-    if (hipMemsetAsync(p_st, 0, 8, st) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess) return done(PF_ERR_HIP);
+    if (!(a.agg = static_cast<dmr_agg *>(call.alloc(sizeof(dmr_agg) * (size_t)a.n_blocks))) ||
+        !(a.tot = static_cast<uint64_t *>(call.alloc(16))) || !(a.status = static_cast<uint32_t *>(call.alloc(8))))
+        return PF_ERR_NOMEM;
+    if (hipMemsetAsync(a.status, 0, 8, st) != hipSuccess || !call.mark(0)) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_dmr_count_state, dim3(a.n_blocks), dim3(PF_DMR_THREADS), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_dmr_scan, dim3(1), dim3(PF_DMR_THREADS), 0, st, a);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(ev[1], st) != hipSuccess ||
-        hipMemcpyAsync(tot, p_tot, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
-    float ms0 = 0.0f, ms1 = 0.0f;
+    if (hipGetLastError() != hipSuccess || !call.mark(1) ||
+        hipMemcpyAsync(tot, a.tot, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return PF_ERR_HIP;
+    float ms1 = 0.0f;
     if (tot[0]) {
-        h = (pf_dmr_run_t *)malloc(sizeof(pf_dmr_run_t) * (size_t)tot[0]);
-        void *p_out = nullptr;
-        if (!h || talloc(&p_out, sizeof(pf_dmr_run_t) * (size_t)tot[0])) return done(PF_ERR_NOMEM);
-        a.out = static_cast<pf_dmr_run_t *>(p_out);
+        h.reset((pf_dmr_run_t *)malloc(sizeof(pf_dmr_run_t) * (size_t)tot[0]));
+        if (!h || !(a.out = static_cast<pf_dmr_run_t *>(call.alloc(sizeof(pf_dmr_run_t) * (size_t)tot[0])))) return PF_ERR_NOMEM;
         a.n_out = tot[0];
-        if (hipEventRecord(ev[2], st) != hipSuccess) return done(PF_ERR_HIP);
+        if (!call.mark(2)) return PF_ERR_HIP;
         hipLaunchKernelGGL(pf_dmr_emit_state, dim3(a.n_blocks), dim3(PF_DMR_THREADS), 0, st, a);
-        if (hipGetLastError() != hipSuccess || hipEventRecord(ev[3], st) != hipSuccess ||
-            hipMemcpyAsync(h, p_out, sizeof(pf_dmr_run_t) * (size_t)tot[0], hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (hipGetLastError() != hipSuccess || !call.mark(3) ||
+            hipMemcpyAsync(h.get(), a.out, sizeof(pf_dmr_run_t) * (size_t)tot[0], hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
-            return done(PF_ERR_HIP);
-        (void)hipEventElapsedTime(&ms1, ev[2], ev[3]);
+            return PF_ERR_HIP;
+        ms1 = call.ms(2, 3);
     }
-    (void)hipEventElapsedTime(&ms0, ev[0], ev[1]);
-    (void)hipGetLastError();
+    *ms = call.ms(0, 1) + ms1;
     *n_runs = tot[0];
-    *ms = ms0 + ms1;
-    return done(PF_OK);
+    *runs = h.release();
+    return PF_OK;
 }

@@ -42,9 +42,10 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
-#include <vector>
+#include <memory>
 #include "pf_device.h"
 #include "pf_llr.h"
+#include "pf_call.h"
 #include "../../include/pomfret_amd.h"
 
 struct pf_ctx;
@@ -393,15 +394,6 @@ extern "C" void pf_dmr_hmm_free(pf_dmr_hmm_t *h) {
     free(h);
 }
 
-// sites per workgroup: PF_DMR_BLOCK=<n> as pf_dmr_regions reads it; 0 for a bad value
-static uint32_t hmm_block_env() {
-    const char *e = getenv("PF_DMR_BLOCK");
-    if (!e) return PF_DMR_BLOCK;
-    const long n = atol(e);
-    if (n < 64 || n > PF_DMR_BLOCK || (n & (n - 1))) return 0;
-    return (uint32_t)n;
-}
-
 // the pooled levels differ by min_delta_pct in the run's direction
 static bool hmm_delta_ok(const pf_dmr_run_t &r, uint32_t min_delta_pct) {
     const __int128 M1 = r.sum[0], M2 = r.sum[2], N1 = (__int128)r.sum[0] + r.sum[1], N2 = (__int128)r.sum[2] + r.sum[3];
@@ -416,7 +408,7 @@ extern "C" int pf_dmr_hmm_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32
         hcfg->switch_q16 < 0 || hcfg->switch_q16 > 64 * 65536)
         return PF_ERR_ARG;
     *out = nullptr;
-    const uint32_t B = block ? block : hmm_block_env();
+    const uint32_t B = block ? block : pf_env_pow2("PF_DMR_BLOCK", 64, PF_DMR_BLOCK, PF_DMR_BLOCK);   // as pf_dmr_regions reads it
     if (B < 64u || B > PF_DMR_BLOCK || (B & (B - 1u))) return PF_ERR_ARG;
     for (uint32_t i = 1; i < n_breaks; i++)
         if (breaks[i] < breaks[i - 1]) return PF_ERR_ARG;
@@ -429,22 +421,12 @@ extern "C" int pf_dmr_hmm_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32
     if (!res) return PF_ERR_NOMEM;
     res->n_sites = n;
     if (n == 0) { *out = res; return PF_OK; }
-    if (hipSetDevice(pf_ctx_device(ctx)) != hipSuccess) { free(res); return PF_ERR_HIP; }
-    hipStream_t st = pf_ctx_stream(ctx);
-    std::vector<void *> tmp;                                  // this call's device arrays
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    auto done = [&](int rc) {
-        (void)hipStreamSynchronize(st);
-        for (void *p : tmp) (void)hipFree(p);
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (rc) pf_dmr_hmm_free(res); else *out = res;
-        return rc;
-    };
-    auto talloc = [&](void **p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
-        tmp.push_back(*p);
-        return PF_OK;
-    };
+    std::unique_ptr<pf_dmr_hmm_t, void (*)(pf_dmr_hmm_t *)> own(res, pf_dmr_hmm_free);     // freed on every return but the last
+    if (hipSetDevice(pf_ctx_device(ctx)) != hipSuccess) return PF_ERR_HIP;
+    unsigned long long tot[2] = {0, 0};
+    uint32_t stt = 0;
+    pf_call call(pf_ctx_stream(ctx));
+    hipStream_t st = call.st;
     hmm_args a;
     memset(&a, 0, sizeof a);
     a.n = (uint32_t)n; a.B = B; a.K = B > PF_DMR_THREADS ? B / PF_DMR_THREADS : 1u;
@@ -453,63 +435,47 @@ extern "C" int pf_dmr_hmm_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32
     a.site_cost = hcfg->site_cost_q16; a.sw = hcfg->switch_q16;
     a.n_brk = n_breaks;
     const bool sites = flags & PF_DMR_HMM_SITES;
-    void *p_pos = nullptr, *p_cnt = nullptr, *p_brk = nullptr, *p_blk = nullptr, *p_tot = nullptr, *p_st = nullptr,
-         *p_state = nullptr, *p_evid = nullptr;
-    if (talloc(&p_pos, 4ull * n) || talloc(&p_cnt, 24ull * n) || talloc(&p_brk, 4ull * n_breaks) ||
-        talloc(&p_blk, 4ull * a.nb_n) || talloc(&p_tot, 16) || talloc(&p_st, 8) || talloc(&p_state, n) ||
-        (sites && talloc(&p_evid, 8ull * n)))
-        return done(PF_ERR_NOMEM);
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
+    void *p_pos = nullptr, *p_cnt = nullptr, *p_brk = nullptr;
+    if (!(p_pos = call.alloc(4ull * n)) || !(p_cnt = call.alloc(24ull * n)) || !(p_brk = call.alloc(4ull * n_breaks)) ||
+        !(a.blk = static_cast<uint32_t *>(call.alloc(4ull * a.nb_n))) ||
+        !(a.tot = static_cast<unsigned long long *>(call.alloc(16))) || !(a.status = static_cast<uint32_t *>(call.alloc(8))) ||
+        !(a.state = static_cast<uint8_t *>(call.alloc(n))) || (sites && !(a.evid = static_cast<int64_t *>(call.alloc(8ull * n)))))
+        return PF_ERR_NOMEM;
     const auto t0 = std::chrono::steady_clock::now();
     if (hipMemcpyAsync(p_pos, pile->pos + s0, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(p_cnt, pile->cnt + 6ull * s0, 24ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
         (n_breaks && hipMemcpyAsync(p_brk, breaks, 4ull * n_breaks, hipMemcpyHostToDevice, st) != hipSuccess) ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
+        return PF_ERR_HIP;
     res->ms_upload = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     a.pos = static_cast<const uint32_t *>(p_pos);
     a.cnt = static_cast<const uint32_t *>(p_cnt);
     a.brk = static_cast<const uint32_t *>(p_brk);
-    a.blk = static_cast<uint32_t *>(p_blk);
-    a.tot = static_cast<unsigned long long *>(p_tot);
-    a.status = static_cast<uint32_t *>(p_st);
-    a.state = static_cast<uint8_t *>(p_state);
-    a.evid = static_cast<int64_t *>(p_evid);
-    unsigned long long tot[2] = {0, 0};
-    uint32_t stt = 0;
     const dim3 T(PF_DMR_THREADS);
-    if (hipMemsetAsync(p_st, 0, 8, st) != hipSuccess || hipMemsetAsync(p_tot, 0, 16, st) != hipSuccess ||
-        hipEventRecord(ev[0], st) != hipSuccess)
-        return done(PF_ERR_HIP);
+    if (hipMemsetAsync(a.status, 0, 8, st) != hipSuccess || hipMemsetAsync(a.tot, 0, 16, st) != hipSuccess || !call.mark(0))
+        return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_hmm_count, dim3(a.nb_n), T, 0, st, a);
-    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_hmm_offsets, dim3(1), T, 0, st, a);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(ev[1], st) != hipSuccess ||
-        hipMemcpyAsync(tot, p_tot, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&stt, p_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
-    if (stt & 1u) return done(PF_ERR_ARG);                    // positions not ascending over the range
-    if (stt & 2u) return done(PF_ERR_LIMIT);
+    if (hipGetLastError() != hipSuccess || !call.mark(1) ||
+        hipMemcpyAsync(tot, a.tot, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&stt, a.status, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return PF_ERR_HIP;
+    if (stt & 1u) return PF_ERR_ARG;                          // positions not ascending over the range
+    if (stt & 2u) return PF_ERR_LIMIT;
     const uint64_t m = tot[0];
-    if (m > n) return done(PF_ERR_INTERNAL);
+    if (m > n) return PF_ERR_INTERNAL;
     a.m = (uint32_t)m;
     a.nb_m = (uint32_t)((m + B - 1) / B);
-    void *p_cpos = nullptr, *p_cidx = nullptr, *p_crank = nullptr, *p_ce = nullptr, *p_V = nullptr, *p_agg = nullptr,
-         *p_magg = nullptr;
-    if (talloc(&p_cpos, 4ull * m) || talloc(&p_cidx, 4ull * m) || talloc(&p_crank, 4ull * m) || talloc(&p_ce, 8ull * m) ||
-        talloc(&p_V, 24ull * m) || talloc(&p_agg, sizeof(hmm_mat) * (size_t)a.nb_m) || talloc(&p_magg, 4ull * a.nb_m))
-        return done(PF_ERR_NOMEM);
-    a.cpos = static_cast<uint32_t *>(p_cpos);
-    a.cidx = static_cast<uint32_t *>(p_cidx);
-    a.crank = static_cast<uint32_t *>(p_crank);
-    a.ce = static_cast<int64_t *>(p_ce);
-    a.V = static_cast<int64_t *>(p_V);
-    a.agg = static_cast<hmm_mat *>(p_agg);
-    a.magg = static_cast<uint32_t *>(p_magg);
-    if (hipEventRecord(ev[2], st) != hipSuccess) return done(PF_ERR_HIP);
+    if (!(a.cpos = static_cast<uint32_t *>(call.alloc(4ull * m))) || !(a.cidx = static_cast<uint32_t *>(call.alloc(4ull * m))) ||
+        !(a.crank = static_cast<uint32_t *>(call.alloc(4ull * m))) || !(a.ce = static_cast<int64_t *>(call.alloc(8ull * m))) ||
+        !(a.V = static_cast<int64_t *>(call.alloc(24ull * m))) ||
+        !(a.agg = static_cast<hmm_mat *>(call.alloc(sizeof(hmm_mat) * (size_t)a.nb_m))) ||
+        !(a.magg = static_cast<uint32_t *>(call.alloc(4ull * a.nb_m))))
+        return PF_ERR_NOMEM;
+    if (!call.mark(2)) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_hmm_compact, dim3(a.nb_n), T, 0, st, a);
-    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     if (m) {
         hipLaunchKernelGGL(pf_hmm_fwd_count, dim3(a.nb_m), T, 0, st, a);
         hipLaunchKernelGGL(pf_hmm_fwd_scan, dim3(1), T, 0, st, a);
@@ -517,15 +483,13 @@ extern "C" int pf_dmr_hmm_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32
         hipLaunchKernelGGL(pf_hmm_back_count, dim3(a.nb_m), T, 0, st, a);
         hipLaunchKernelGGL(pf_hmm_back_scan, dim3(1), T, 0, st, a);
         hipLaunchKernelGGL(pf_hmm_back_apply, dim3(a.nb_m), T, 0, st, a);
-        if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+        if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     }
-    if (hipEventRecord(ev[3], st) != hipSuccess ||
-        hipMemcpyAsync(tot + 1, a.tot + 1, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
-    float ms0 = 0.0f, ms1 = 0.0f, ms2 = 0.0f;
-    (void)hipEventElapsedTime(&ms0, ev[0], ev[1]);
-    (void)hipEventElapsedTime(&ms1, ev[2], ev[3]);
-    (void)hipGetLastError();
+    if (!call.mark(3) || hipMemcpyAsync(tot + 1, a.tot + 1, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return PF_ERR_HIP;
+    const float ms01 = call.ms(0, 1) + call.ms(2, 3);
+    float ms2 = 0.0f;
     res->n_informative = m;
     res->n_chains = tot[1];
     if (sites) {
@@ -533,17 +497,17 @@ extern "C" int pf_dmr_hmm_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32
         int64_t *he = (int64_t *)malloc(8ull * n);
         res->state = hs;
         res->evidence = he;
-        if (!hs || !he) return done(PF_ERR_NOMEM);
-        if (hipMemcpyAsync(hs, p_state, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(he, p_evid, 8ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        if (!hs || !he) return PF_ERR_NOMEM;
+        if (hipMemcpyAsync(hs, a.state, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(he, a.evid, 8ull * n, hipMemcpyDeviceToHost, st) != hipSuccess ||
             hipStreamSynchronize(st) != hipSuccess)
-            return done(PF_ERR_HIP);
+            return PF_ERR_HIP;
     }
     if (m) {
         pf_dmr_run_t *runs = nullptr;
         uint64_t n_runs = 0;
         const int rc = pf_dmr_state_runs(ctx, a.pos, a.cnt, a.brk, n_breaks, a.state, a.n, B, cfg, &runs, &n_runs, &ms2);
-        if (rc) return done(rc);
+        if (rc) return rc;
         // the runs at the range's ends are closed here, and filtered like any other
         uint64_t k = 0;
         for (uint64_t i = 0; i < n_runs; i++) {
@@ -556,6 +520,7 @@ extern "C" int pf_dmr_hmm_regions(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32
         res->runs = runs;
         res->n_runs = k;
     }
-    res->ms_kernels = ms0 + ms1 + ms2;
-    return done(PF_OK);
+    res->ms_kernels = ms01 + ms2;
+    *out = own.release();
+    return PF_OK;
 }

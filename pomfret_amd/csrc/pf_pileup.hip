@@ -10,12 +10,11 @@
 // high 16 bits; a window holds at most 65,535 reads, so a count only passes
 // 65,535 when reads carry duplicate entries at one position -- the add that
 // finds its field full sets the status bit and the call fails with
-// PF_ERR_LIMIT).  The waves take the window's reads in turn, 64 at a time:
-// each lane takes one read, drops it when its sorted call slice ends left of
-// the tile or starts right of it (most reads of a window miss a given tile),
-// else binary-searches the slice for the tile's first position; then the
-// wave's lanes stride over each hitting read's calls up to the tile's end with
-// coalesced loads and LDS atomics; no call touches an HBM atomic.  The tile is
+// PF_ERR_LIMIT).  The waves take the window's reads in turn, 64 at a time, by
+// the shared read-slice scan of pf_reads.h against the tile's range (most reads
+// of a window miss a given tile); what is the pileup's own is the stride over
+// each hitting read's calls: coalesced loads and LDS atomics into the tile's
+// counters, and no call touches an HBM atomic.  The tile is
 // then scanned in position order, ballot / mbcnt prefix counts compacting the
 // non-zero positions.  Two passes make the output exactly sized and deterministic:
 // pf_pile_count leaves each item's site count, pf_pile_scan the prefix sums
@@ -25,17 +24,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "pf_device.h"
+#include "pf_reads.h"
 
 namespace {
-
-__device__ __forceinline__ uint32_t lane_prefix(uint64_t bal) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-}
 
 template <bool EMIT>
 __device__ __forceinline__ void pile_item(const pf_pile_args &a) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tile[];   // [3][T]
     __shared__ uint32_t wsum[PF_PILE_WAVES];
+    const pf_calls_view &v = a.v;
     const uint32_t item = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t T = a.T;
     if (item >= a.n_items) return;
@@ -51,7 +48,7 @@ __device__ __forceinline__ void pile_item(const pf_pile_args &a) {
         const uint32_t mid = w + (hi - w) / 2;
         if (a.tile_off[mid] <= item) w = mid; else hi = mid;
     }
-    const uint64_t ws = a.win_start[w], we = a.win_end[w];
+    const uint64_t ws = v.win_start[w], we = v.win_end[w];
     const uint64_t t0 = ws + (uint64_t)(item - a.tile_off[w]) * T;
     const uint64_t t1 = t0 + T < we ? t0 + T : we;
     const uint32_t span = t1 > t0 ? (uint32_t)(t1 - t0) : 0u;          // <= T
@@ -59,7 +56,7 @@ __device__ __forceinline__ void pile_item(const pf_pile_args &a) {
         for (uint32_t i = tid; i < span; i += PF_PILE_THREADS) tile[h * T + i] = 0u;
     __syncthreads();
 
-    const uint32_t r0 = a.win_read_off[w], r1 = a.win_read_off[w + 1];
+    const uint32_t r0 = v.win_read_off[w], r1 = v.win_read_off[w + 1];
     bool wrapped = false;
     for (uint32_t g = r0 + wave * 64u; g < r1; g += PF_PILE_WAVES * 64u) {
         // 64 reads at once, one per lane: the lower bound of t0 in the read's
@@ -67,29 +64,22 @@ __device__ __forceinline__ void pile_item(const pf_pile_args &a) {
         const uint32_t r = g + lane;
         uint64_t lo = 0, c1 = 0;
         uint32_t h = 2u;
-        if (r < r1) {
-            lo = a.read_call_off[r];
-            c1 = a.read_call_end[r];
-            const uint32_t hp = a.read_hp[r];
+        if (r >= g && r < r1) {
+            lo = v.read_call_off[r];
+            c1 = v.read_call_end[r];
+            const uint32_t hp = v.read_hp[r];
             h = hp < 2u ? hp : 2u;
         }
-        // a slice that ends left of the tile or starts right of it needs no search
-        if (lo < c1 && (a.call_pos[c1 - 1] < t0 || a.call_pos[lo] >= t1)) lo = c1;
-        for (uint64_t hi = c1; lo < hi;) {
-            const uint64_t mid = lo + (hi - lo) / 2;
-            if (a.call_pos[mid] < t0) lo = mid + 1; else hi = mid;
-        }
-        const bool hit = lo < c1 && a.call_pos[lo] < t1;
+        const bool hit = slice_seek(v.call_pos, lo, c1, t0, t1);
         // the wave strides over each hitting read's calls from the bound to
         // the tile's end: coalesced loads, LDS atomics
         for (uint64_t m = __ballot(hit); m; m &= m - 1) {
             const int l = __builtin_ctzll(m);
-            const uint64_t s = ((uint64_t)(uint32_t)__shfl((int)(lo >> 32), l) << 32) | (uint32_t)__shfl((int)lo, l);
-            const uint64_t e = ((uint64_t)(uint32_t)__shfl((int)(c1 >> 32), l) << 32) | (uint32_t)__shfl((int)c1, l);
+            const uint64_t s = shfl64(lo, l), e = shfl64(c1, l);
             const uint32_t hh = (uint32_t)__shfl((int)h, l);
             for (uint64_t c = s + lane; c < e; c += 64) {
-                const uint64_t p = a.call_pos[c];
-                const uint32_t cat = a.call_cat[c];  // with the position: one round trip per step
+                const uint64_t p = v.call_pos[c];
+                const uint32_t cat = v.call_cat[c];  // with the position: one round trip per step
                 if (p >= t1) break;
                 if (p < t0 || cat > 1u) continue;    // p < t0: never in a sorted slice
                 const uint32_t old = atomicAdd(&tile[hh * T + (uint32_t)(p - t0)], cat ? 0x10000u : 1u);
@@ -107,18 +97,10 @@ __device__ __forceinline__ void pile_item(const pf_pile_args &a) {
         uint32_t v0 = 0, v1 = 0, v2 = 0;
         if (i < span) { v0 = tile[i]; v1 = tile[T + i]; v2 = tile[2 * T + i]; }
         const bool nz = (v0 | v1 | v2) != 0u;
-        const uint64_t bal = __ballot(nz);
-        if (lane == 0) wsum[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t before = 0, tot = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < PF_PILE_WAVES; k++) {
-            const uint32_t s = wsum[k];
-            before += k < wave ? s : 0u;
-            tot += s;
-        }
+        uint32_t tot;
+        const uint32_t slot = block_compact(nz, wsum, PF_PILE_WAVES, lane, wave, tot);
         if (EMIT && nz) {
-            const uint64_t o = out0 + run + before + lane_prefix(bal);
+            const uint64_t o = out0 + run + slot;
             if (o < out1) {                          // holds: both passes count the same calls
                 a.out_pos[o] = (uint32_t)t0 + i;
                 uint2 *q = reinterpret_cast<uint2 *>(a.out_cnt + 6 * o);

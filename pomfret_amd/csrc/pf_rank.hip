@@ -3,14 +3,11 @@
 //
 // One workgroup per window, two phases, all in integers.
 //
-// Phase 1 is pf_perm_test's read loop: the window's reads blockDim.x at a
-// time, one per lane; a read whose sorted call slice ends left of the window or
-// starts right of it needs no search, the others binary-search the slice for
-// the window's first position; the wave then strides over each hitting read's
-// calls up to the window's end and counts its meth and unmeth entries with two
-// ballots per 64 calls.  The counted reads (tag 0 or 1, at least min_calls
-// entries) are compacted in read order into LDS with ballot / mbcnt prefixes
-// across the waves as (m, n | tag << 31), 8 B each; the class counters, the
+// Phase 1 takes the window's reads blockDim.x at a time, one per lane, and
+// counts each one's meth and unmeth entries inside the window: the shared
+// read-slice scan (pf_reads.h, window_read_counts).  The counted reads (tag 0
+// or 1, at least min_calls entries) are compacted in read order into LDS
+// (block_compact) as (m, n | tag << 31), 8 B each; the class counters, the
 // sums, the short reads and the largest n are collected by LDS integer
 // atomics.
 //
@@ -30,8 +27,11 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <memory>
 #include <vector>
 #include "pf_device.h"
+#include "pf_reads.h"
+#include "pf_call.h"
 #include "../../include/pomfret_amd.h"
 
 struct pf_ctx;
@@ -60,26 +60,9 @@ static_assert(sizeof(rank_out) == 96, "rank_out is copied back as 96-byte record
 
 struct rank_args {
     uint32_t W, min_calls, force_wide, pad;
-    const uint32_t *win_start, *win_end, *win_read_off;
-    const uint8_t *read_hp;                          /* the batch's tags or the caller's */
-    const uint64_t *read_call_off, *read_call_end;
-    const uint32_t *call_pos;
-    const uint8_t *call_cat;
+    pf_calls_view v;                                 /* read_hp: the batch's tags or the caller's */
     rank_out *out;                                   /* [W] */
 };
-
-__device__ __forceinline__ uint32_t lane_prefix(uint64_t bal) {
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-}
-
-__device__ __forceinline__ uint64_t wave_sum64(uint64_t x) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, d), hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), d);
-        x += ((uint64_t)hi << 32) | lo;
-    }
-    return x;
-}
 
 // The rows tid, tid + nt, ... of the n counted reads in s_r against every j.
 // P: the products' type, uint32_t where every n is at most 65,535.
@@ -128,60 +111,21 @@ __global__ __launch_bounds__(PF_RANK_THREADS_MAX) void pf_rank_test(rank_args a)
     __syncthreads();
 
     // ---- phase 1: the counted reads in read order
-    const uint32_t ws = a.win_start[w], we = a.win_end[w];
-    const uint32_t r0 = a.win_read_off[w], r1 = a.win_read_off[w + 1];
+    const uint32_t ws = a.v.win_start[w], we = a.v.win_end[w];
+    const uint32_t r0 = a.v.win_read_off[w], r1 = a.v.win_read_off[w + 1];
     uint32_t n = 0;
     for (uint32_t g = r0; g < r1; g += nt) {          // the same rounds in every thread: barriers inside
-        const uint32_t r = g + tid;
-        uint64_t lo = 0, c1 = 0;
-        uint32_t hp = 2u;
-        if (r >= g && r < r1) {
-            lo = a.read_call_off[r];
-            c1 = a.read_call_end[r];
-            hp = a.read_hp[r];
-        }
-        if (hp > 1u) lo = c1;                         // untagged, HP >= 3: not a read of the test
-        if (lo < c1 && (a.call_pos[c1 - 1] < ws || a.call_pos[lo] >= we)) lo = c1;
-        for (uint64_t hi = c1; lo < hi;) {
-            const uint64_t mid = lo + (hi - lo) / 2;
-            if (a.call_pos[mid] < ws) lo = mid + 1; else hi = mid;
-        }
-        const bool hit = lo < c1 && a.call_pos[lo] < we;
-        uint32_t my_m = 0, my_u = 0;
-        for (uint64_t m = __ballot(hit); m; m &= m - 1) {
-            const int l = __builtin_ctzll(m);
-            const uint64_t s = ((uint64_t)(uint32_t)__shfl((int)(lo >> 32), l) << 32) | (uint32_t)__shfl((int)lo, l);
-            const uint64_t e = ((uint64_t)(uint32_t)__shfl((int)(c1 >> 32), l) << 32) | (uint32_t)__shfl((int)c1, l);
-            uint32_t cm = 0, cu = 0;                  // wave-uniform
-            for (uint64_t c0 = s; c0 < e; c0 += 64) {
-                const uint64_t c = c0 + lane;
-                const bool valid = c < e;
-                const uint32_t p = valid ? a.call_pos[c] : 0u;
-                const uint32_t cat = valid ? a.call_cat[c] : 2u;
-                const bool in = valid && p < we;      // p >= ws: the slice is sorted and starts at the bound
-                cm += (uint32_t)__popcll(__ballot(in && cat == 0u));
-                cu += (uint32_t)__popcll(__ballot(in && cat == 1u));
-                if (__ballot(valid && !in)) break;    // past the window's end
-            }
-            my_m = lane == (uint32_t)l ? cm : my_m;
-            my_u = lane == (uint32_t)l ? cu : my_u;
-        }
+        uint32_t hp, my_m, my_u, tot;
+        bool hit;
+        window_read_counts(a.v, g, r1, ws, we, tid, hp, hit, my_m, my_u);
         const uint32_t my_n = my_m + my_u;
         const bool part = hit && my_n != 0u;
         const bool counted = part && my_n >= a.min_calls;
-        const uint64_t bal = __ballot(counted);
-        if (lane == 0u) wsum[wave] = (uint32_t)__popcll(bal);
-        __syncthreads();
-        uint32_t before = 0, tot = 0;
-        for (uint32_t k = 0; k < nw; k++) {
-            const uint32_t s = wsum[k];
-            before += k < wave ? s : 0u;
-            tot += s;
-        }
+        const uint32_t slot = block_compact(counted, wsum, nw, lane, wave, tot);
         if (part) atomicAdd(&s_N, (unsigned long long)my_n);
         if (part && !counted) atomicAdd(&s_short[hp], 1u);
         if (counted) {
-            const uint32_t idx = n + before + lane_prefix(bal);
+            const uint32_t idx = n + slot;
             if (idx < PF_RANK_READS) s_r[idx] = make_uint2(my_m, (my_n & 0x7FFFFFFFu) | (hp << 31));
             atomicAdd(&s_sum[2u * hp], (unsigned long long)my_m);
             atomicAdd(&s_sum[2u * hp + 1u], (unsigned long long)my_u);
@@ -240,16 +184,6 @@ extern "C" void pf_rank_free(pf_rank_t *p) {
     free(p);
 }
 
-// the workgroup: PF_RANK_THREADS=<64|256|1024> (tests); 0 for any other value
-static uint32_t rank_threads() {
-    const char *e = getenv("PF_RANK_THREADS");
-    if (!e) return PF_RANK_THREADS;
-    if (!strcmp(e, "64")) return 64;
-    if (!strcmp(e, "256")) return 256;
-    if (!strcmp(e, "1024")) return 1024;
-    return 0;
-}
-
 // PF_RANK_WIDE: unset or "0" 0, "1" 1 (64-bit products for every window), anything else -1
 static int rank_wide() {
     const char *e = getenv("PF_RANK_WIDE");
@@ -263,7 +197,7 @@ extern "C" int pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *
     if (!ctx || !db || !out) return PF_ERR_ARG;
     *out = nullptr;
     if (min_calls < 1u || min_calls > 65535u) return PF_ERR_ARG;
-    const uint32_t nt = rank_threads();
+    const uint32_t nt = pf_env_threads("PF_RANK_THREADS", PF_RANK_THREADS);
     const int fw = rank_wide();
     if (!nt || fw < 0) return PF_ERR_ARG;
     pf_dev_batch d;
@@ -271,65 +205,42 @@ extern "C" int pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *
     if (vrc) return vrc;
     const uint32_t W = d.W, R = d.R;
     if (read_hp && n_hp != R) return PF_ERR_ARG;
-    hipStream_t st = pf_ctx_stream(ctx);
 
     pf_rank_t *res = (pf_rank_t *)calloc(1, sizeof(pf_rank_t));
     if (!res) return PF_ERR_NOMEM;
     res->n_windows = W;
     res->min_calls = min_calls;
     if (W == 0) { *out = res; return PF_OK; }
+    std::unique_ptr<pf_rank_t, void (*)(pf_rank_t *)> own(res, pf_rank_free);      // freed on every return but the last
     uint32_t *h_nr = (uint32_t *)calloc(2ull * W, 4), *h_short = (uint32_t *)calloc(2ull * W, 4);
     uint32_t *h_cls = (uint32_t *)calloc(6ull * W, 4), *h_stat = (uint32_t *)calloc(W, 4);
     uint64_t *h_sum = (uint64_t *)calloc(4ull * W, 8), *h_u2 = (uint64_t *)calloc(W, 8), *h_ties = (uint64_t *)calloc(W, 8);
     res->n_reads = h_nr; res->n_short = h_short; res->cls = h_cls; res->sum = h_sum; res->u2 = h_u2; res->ties = h_ties;
     res->status = h_stat;
-    std::vector<void *> tmp;                                  // this call's device arrays
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    auto done = [&](int rc) {
-        (void)hipStreamSynchronize(st);
-        for (void *p : tmp) (void)hipFree(p);
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (rc) pf_rank_free(res); else *out = res;
-        return rc;
-    };
-    if (!h_nr || !h_short || !h_cls || !h_stat || !h_sum || !h_u2 || !h_ties) return done(PF_ERR_NOMEM);
-    auto talloc = [&](void **p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; return PF_ERR_NOMEM; }
-        tmp.push_back(*p);
-        return PF_OK;
-    };
+    if (!h_nr || !h_short || !h_cls || !h_stat || !h_sum || !h_u2 || !h_ties) return PF_ERR_NOMEM;
     std::vector<rank_out> h_out;
-    try { h_out.resize(W); } catch (...) { return done(PF_ERR_NOMEM); }
-    void *p_hp = nullptr, *p_out = nullptr;
-    if ((read_hp && R && talloc(&p_hp, R)) || talloc(&p_out, sizeof(rank_out) * (size_t)W)) return done(PF_ERR_NOMEM);
+    try { h_out.resize(W); } catch (...) { return PF_ERR_NOMEM; }
+    pf_call call(pf_ctx_stream(ctx));
     rank_args a;
     memset(&a, 0, sizeof a);
     a.W = W; a.min_calls = min_calls; a.force_wide = (uint32_t)fw;
-    a.win_start = d.win_start; a.win_end = d.win_end; a.win_read_off = d.win_read_off;
-    a.read_hp = d.read_hp;
-    a.read_call_off = d.read_call_off; a.read_call_end = d.read_call_end;
-    a.call_pos = d.call_pos; a.call_cat = d.call_cat;
-    a.out = static_cast<rank_out *>(p_out);
-    if (p_hp) {
-        if (hipMemcpyAsync(p_hp, read_hp, R, hipMemcpyHostToDevice, st) != hipSuccess) return done(PF_ERR_HIP);
-        a.read_hp = static_cast<const uint8_t *>(p_hp);
-    }
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
-    if (hipEventRecord(ev[0], st) != hipSuccess) return done(PF_ERR_HIP);
-    hipLaunchKernelGGL(pf_rank_test, dim3(W), dim3(nt), 0, st, a);
-    if (hipGetLastError() != hipSuccess || hipEventRecord(ev[1], st) != hipSuccess ||
-        hipMemcpyAsync(h_out.data(), p_out, sizeof(rank_out) * (size_t)W, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-    (void)hipGetLastError();
+    a.v = pf_calls_view_of(d);
+    const int hrc = call.upload_hp(read_hp, R, a.v);
+    if (hrc) return hrc;
+    a.out = static_cast<rank_out *>(call.alloc(sizeof(rank_out) * (size_t)W));
+    if (!a.out) return PF_ERR_NOMEM;
+    if (!call.mark(0)) return PF_ERR_HIP;
+    hipLaunchKernelGGL(pf_rank_test, dim3(W), dim3(nt), 0, call.st, a);
+    if (hipGetLastError() != hipSuccess || !call.mark(1) ||
+        hipMemcpyAsync(h_out.data(), a.out, sizeof(rank_out) * (size_t)W, hipMemcpyDeviceToHost, call.st) != hipSuccess ||
+        hipStreamSynchronize(call.st) != hipSuccess)
+        return PF_ERR_HIP;
+    res->ms_kernels = call.ms(0, 1);
     for (uint32_t w = 0; w < W; w++) {
         const rank_out &o = h_out[w];
         if (o.status == RANK_ST_LIMIT) {
             fprintf(stderr, "[E::pomfret_amd] ranktest: a window holds 2^31 or more calls\n");
-            return done(PF_ERR_LIMIT);
+            return PF_ERR_LIMIT;
         }
         for (int k = 0; k < 4; k++) h_sum[4ull * w + k] = o.sum[k];
         for (int k = 0; k < 2; k++) { h_nr[2ull * w + k] = o.n_reads[k]; h_short[2ull * w + k] = o.n_short[k]; }
@@ -338,6 +249,6 @@ extern "C" int pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *
         h_ties[w] = o.ties;
         h_stat[w] = o.status;
     }
-    res->ms_kernels = ms;
-    return done(PF_OK);
+    *out = own.release();
+    return PF_OK;
 }

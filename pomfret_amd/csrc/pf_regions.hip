@@ -26,10 +26,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
-#include <vector>
+#include <memory>
 #include "pf_device.h"
 #include "pf_llr.h"
 #include "pf_site.h"
+#include "pf_call.h"
 #include "../../include/pomfret_amd.h"
 
 struct pf_ctx;
@@ -239,16 +240,6 @@ extern "C" void pf_regions_free(pf_regions_t *r) {
     free(r);
 }
 
-// sites per workgroup: PF_REG_BLOCK=<n>, n a power of two in [64, 1024]; 0 for
-// any other value
-static uint32_t reg_block_env() {
-    const char *e = getenv("PF_REG_BLOCK");
-    if (!e) return PF_REG_BLOCK;
-    const long n = atol(e);
-    if (n < 64 || n > PF_REG_BLOCK || (n & (n - 1))) return 0;
-    return (uint32_t)n;
-}
-
 extern "C" int pf_region_sums(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w0, uint32_t w1, const pf_dmr_cfg_t *cfg,
                               const uint32_t *reg_start, const uint32_t *reg_end, uint64_t n_regions, uint32_t block,
                               pf_regions_t **out) {
@@ -256,7 +247,7 @@ extern "C" int pf_region_sums(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w
         (n_regions && (!reg_start || !reg_end)) || cfg->min_delta_pct > 100u)
         return PF_ERR_ARG;
     *out = nullptr;
-    const uint32_t B = block ? block : reg_block_env();
+    const uint32_t B = block ? block : pf_env_pow2("PF_REG_BLOCK", 64, PF_REG_BLOCK, PF_REG_BLOCK);
     if (B < 64u || B > PF_REG_BLOCK || (B & (B - 1u))) return PF_ERR_ARG;
     if (n_regions >= 0x80000000ull) return PF_ERR_LIMIT;
     for (uint64_t i = 0; i < n_regions; i++)
@@ -276,83 +267,63 @@ extern "C" int pf_region_sums(pf_ctx_t *ctx, const pf_pileup_t *pile, uint32_t w
     res->n = n_regions;
     res->r = h;
     if (n == 0) { *out = res; return PF_OK; }                 // no site: every record is all zero
-    if (hipSetDevice(pf_ctx_device(ctx)) != hipSuccess) { pf_regions_free(res); return PF_ERR_HIP; }
-    hipStream_t st = pf_ctx_stream(ctx);
-    std::vector<void *> tmp;                                  // this call's device arrays
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    auto done = [&](int rc) {
-        (void)hipStreamSynchronize(st);
-        for (void *p : tmp) (void)hipFree(p);
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (rc) pf_regions_free(res); else *out = res;
-        return rc;
-    };
-    auto talloc = [&](void **p, size_t bytes) {
-        if (hipMalloc(p, bytes ? bytes : 8) != hipSuccess) { *p = nullptr; (void)hipGetLastError(); return PF_ERR_NOMEM; }
-        tmp.push_back(*p);
-        return PF_OK;
-    };
+    std::unique_ptr<pf_regions_t, void (*)(pf_regions_t *)> own(res, pf_regions_free);     // freed on every return but the last
+    if (hipSetDevice(pf_ctx_device(ctx)) != hipSuccess) return PF_ERR_HIP;
+    uint64_t tot = 0;
+    uint32_t stt = 0;
+    pf_call call(pf_ctx_stream(ctx));
+    hipStream_t st = call.st;
     reg_args a;
     memset(&a, 0, sizeof a);
     a.n = (uint32_t)n; a.B = B; a.K = B > PF_DMR_THREADS ? B / PF_DMR_THREADS : 1u;
     a.n_blocks = (uint32_t)((n + B - 1) / B);
     a.min_cov = cfg->min_cov; a.min_delta_pct = cfg->min_delta_pct;
     a.n_reg = (uint32_t)n_regions;
-    void *p_pos = nullptr, *p_cnt = nullptr, *p_blk = nullptr, *p_row = nullptr, *p_tot = nullptr, *p_st = nullptr;
-    void *p_rs = nullptr, *p_re = nullptr, *p_out = nullptr;
-    if (talloc(&p_pos, 4ull * n) || talloc(&p_cnt, 24ull * n) || talloc(&p_blk, sizeof(reg_agg) * (size_t)a.n_blocks) ||
-        talloc(&p_tot, 8) || talloc(&p_st, 8))
-        return done(PF_ERR_NOMEM);
-    if (n_regions && (talloc(&p_row, sizeof(reg_agg) * (size_t)(n + 1)) || talloc(&p_rs, 4ull * n_regions) ||
-                      talloc(&p_re, 4ull * n_regions) || talloc(&p_out, sizeof(pf_region_sum_t) * (size_t)n_regions)))
-        return done(PF_ERR_NOMEM);
-    for (auto &e : ev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return done(PF_ERR_HIP); }
+    void *p_pos = nullptr, *p_cnt = nullptr, *p_rs = nullptr, *p_re = nullptr;
+    if (!(p_pos = call.alloc(4ull * n)) || !(p_cnt = call.alloc(24ull * n)) ||
+        !(a.blk = static_cast<reg_agg *>(call.alloc(sizeof(reg_agg) * (size_t)a.n_blocks))) ||
+        !(a.tot = static_cast<uint64_t *>(call.alloc(8))) || !(a.status = static_cast<uint32_t *>(call.alloc(8))))
+        return PF_ERR_NOMEM;
+    if (n_regions && (!(a.row = static_cast<reg_agg *>(call.alloc(sizeof(reg_agg) * (size_t)(n + 1)))) ||
+                      !(p_rs = call.alloc(4ull * n_regions)) || !(p_re = call.alloc(4ull * n_regions)) ||
+                      !(a.out = static_cast<pf_region_sum_t *>(call.alloc(sizeof(pf_region_sum_t) * (size_t)n_regions)))))
+        return PF_ERR_NOMEM;
     const auto t0 = std::chrono::steady_clock::now();
     if (hipMemcpyAsync(p_pos, pile->pos + s0, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
         hipMemcpyAsync(p_cnt, pile->cnt + 6ull * s0, 24ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
         (n_regions && (hipMemcpyAsync(p_rs, reg_start, 4ull * n_regions, hipMemcpyHostToDevice, st) != hipSuccess ||
                        hipMemcpyAsync(p_re, reg_end, 4ull * n_regions, hipMemcpyHostToDevice, st) != hipSuccess)) ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
+        return PF_ERR_HIP;
     res->ms_upload = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     a.pos = static_cast<const uint32_t *>(p_pos);
     a.cnt = static_cast<const uint32_t *>(p_cnt);
-    a.blk = static_cast<reg_agg *>(p_blk);
-    a.row = static_cast<reg_agg *>(p_row);
-    a.tot = static_cast<uint64_t *>(p_tot);
-    a.status = static_cast<uint32_t *>(p_st);
     a.rs = static_cast<const uint32_t *>(p_rs);
     a.re = static_cast<const uint32_t *>(p_re);
-    a.out = static_cast<pf_region_sum_t *>(p_out);
-    uint64_t tot = 0;
-    uint32_t stt = 0;
-    if (hipMemsetAsync(p_st, 0, 8, st) != hipSuccess || hipEventRecord(ev[0], st) != hipSuccess) return done(PF_ERR_HIP);
+    if (hipMemsetAsync(a.status, 0, 8, st) != hipSuccess || !call.mark(0)) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_reg_count, dim3(a.n_blocks), dim3(PF_DMR_THREADS), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     hipLaunchKernelGGL(pf_reg_scan, dim3(1), dim3(PF_DMR_THREADS), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+    if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     if (n_regions) {
         // a range that the count refuses goes through the other two kernels all
         // the same, in one submission: every index they form is bounded by n and
         // n_regions whatever the sites hold, and the records are dropped below
         hipLaunchKernelGGL(pf_reg_prefix, dim3(a.n_blocks), dim3(PF_DMR_THREADS), 0, st, a);
-        if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+        if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
         hipLaunchKernelGGL(pf_reg_lookup, dim3((uint32_t)((n_regions + PF_DMR_THREADS - 1) / PF_DMR_THREADS)),
                            dim3(PF_DMR_THREADS), 0, st, a);
-        if (hipGetLastError() != hipSuccess) return done(PF_ERR_HIP);
+        if (hipGetLastError() != hipSuccess) return PF_ERR_HIP;
     }
-    if (hipEventRecord(ev[1], st) != hipSuccess || hipMemcpyAsync(&tot, p_tot, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&stt, p_st, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        (n_regions && hipMemcpyAsync(h, p_out, sizeof(pf_region_sum_t) * (size_t)n_regions, hipMemcpyDeviceToHost, st) != hipSuccess) ||
+    if (!call.mark(1) || hipMemcpyAsync(&tot, a.tot, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipMemcpyAsync(&stt, a.status, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        (n_regions && hipMemcpyAsync(h, a.out, sizeof(pf_region_sum_t) * (size_t)n_regions, hipMemcpyDeviceToHost, st) != hipSuccess) ||
         hipStreamSynchronize(st) != hipSuccess)
-        return done(PF_ERR_HIP);
-    if (stt & 1u) return done(PF_ERR_ARG);                    // positions not ascending over the range
-    if (stt & 2u) return done(PF_ERR_LIMIT);
-    float ms = 0.0f;
-    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-    (void)hipGetLastError();
+        return PF_ERR_HIP;
+    if (stt & 1u) return PF_ERR_ARG;                          // positions not ascending over the range
+    if (stt & 2u) return PF_ERR_LIMIT;
     res->n_informative = tot;
-    res->ms_kernels = ms;
-    return done(PF_OK);
+    res->ms_kernels = call.ms(0, 1);
+    *out = own.release();
+    return PF_OK;
 }

@@ -300,7 +300,7 @@ def test_block_override_in_the_environment():
             "    print('REFUSED', e)\n"
             "ctx.close()\n")
     out = {}
-    for v in ("64", "", "100", "32", "1048576"):
+    for v in ("64", "", "100", "32", "1048576", "64x"):
         env = dict(os.environ, PYTHONPATH=ROOT)
         env.pop("PF_DMR_BLOCK", None)
         if v:
@@ -309,5 +309,5 @@ def test_block_override_in_the_environment():
         assert r.returncode == 0, r.stderr
         out[v] = r.stdout.strip().splitlines()[-1]
     assert out["64"] == out[""] == "RUNS [150, 250] [1, 2]"
-    for v in ("100", "32", "1048576"):
+    for v in ("100", "32", "1048576", "64x"):
         assert out[v].startswith("REFUSED") and "argument" in out[v]

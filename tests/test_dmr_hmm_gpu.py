@@ -249,7 +249,7 @@ def test_block_override_in_the_environment():
             "    print('REFUSED', e)\n"
             "ctx.close()\n")
     out = {}
-    for v in ("64", "", "100"):
+    for v in ("64", "", "100", "64x"):
         env = dict(os.environ, PYTHONPATH=ROOT)
         env.pop("PF_DMR_BLOCK", None)
         if v:
@@ -258,4 +258,5 @@ def test_block_override_in_the_environment():
         assert r.returncode == 0, r.stderr
         out[v] = r.stdout.strip().splitlines()[-1]
     assert out["64"] == out[""] and out[""].startswith("RUNS") and int(out[""].split()[1]) > 3
-    assert out["100"].startswith("REFUSED") and "argument" in out["100"]
+    for v in ("100", "64x"):
+        assert out[v].startswith("REFUSED") and "argument" in out[v]

@@ -162,7 +162,7 @@ def test_no_windows(gpu_ctx):
 def test_bad_tile_is_refused(gpu_ctx, monkeypatch):
     from pomfret_amd import PomfretError
     db = gpu_ctx.upload(_cfg(), _calls_batch([(0, 10, [(0, [(1, 0)])])]))
-    for bad in ("96", "32", "16384"):
+    for bad in ("96", "32", "16384", "64x"):
         monkeypatch.setenv("PF_PILE_TILE", bad)
         with pytest.raises(PomfretError):
             db.pileup()

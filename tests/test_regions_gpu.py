@@ -189,7 +189,7 @@ def test_block_override_in_the_environment(gpu_ctx, monkeypatch):
     pile, starts, ends, ref = _case(4097)
     monkeypatch.setenv("PF_REG_BLOCK", "64")
     same(gpu_ctx.region_sums(pile, CFG, starts, ends), ref, "PF_REG_BLOCK=64")
-    for v in ("100", "32", "1048576", "x"):
+    for v in ("100", "32", "1048576", "x", "64x"):
         monkeypatch.setenv("PF_REG_BLOCK", v)
         with pytest.raises(PomfretError, match="argument"):
             gpu_ctx.region_sums(pile, CFG, starts, ends)

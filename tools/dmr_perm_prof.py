@@ -97,7 +97,11 @@ def main():
     ap.add_argument("--cut", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--steps", type=int, default=15)
+    ap.add_argument("--lib", default=None, help="another build of the library, a .so in pomfret_amd/")
     a = ap.parse_args()
+    if a.lib:
+        import pomfret_amd._lib as L
+        L.LIB_PATH = os.path.join(os.path.dirname(L.LIB_PATH), a.lib)
     from pomfret_amd import Config, Context, LoadConfig
     from pomfret_amd.synth_aln import AlnSpec, make_aln_batch
     perms = [int(x) for x in a.perms.split(",")]
