@@ -690,6 +690,62 @@ void pf_rank_free(pf_rank_t *r);
  * when n1 or n2 is 0 or u2 > 2*n1*n2.  auc, z and p may each be NULL. */
 int  pf_rank_p(uint64_t u2, uint32_t n1, uint32_t n2, uint64_t ties, double *auc, double *z, double *p);
 
+/* The rank test's exact null distribution for small windows (pf_rank.hip,
+ * pf_rank_exact; no reference counterpart): conditional on the counted reads'
+ * fractions, ties included, every assignment of n1 of the n = n1 + n2 counted
+ * reads to haplotype 1 is equally likely.  Participating and counted reads,
+ * the order of fractions and the N < 2^31 limit are pf_batch_ranktest's.  For
+ * a subset A of the counted reads with |A| = n1
+ *   u2(A) = 2 * #{(i in A, j not in A): f_i > f_j} + #{(i in A, j not in A): f_i == f_j},
+ * A0 the reads tagged 0, u2(A0) = pf_rank_t.u2, and over all C(n, n1) subsets
+ *   total  C(n, n1);
+ *   le     #{A: u2(A) <= u2(A0)};   ge  #{A: u2(A) >= u2(A0)};
+ *   two    #{A: |u2(A) - n1*n2| >= |u2(A0) - n1*n2|}, in signed 64-bit arithmetic;
+ *   status 0 tested; 1 n1 == 0 or n2 == 0, every count 0; 2 n > max_reads,
+ *          every count 0 (no error).
+ * le / total and ge / total are the exact one-sided p-values, two / total the
+ * two-sided one (pf_rank_exact_p).  Counted as subset sums: with r_i = 2 * #{j:
+ * f_j < f_i} + #{j: f_j == f_i} (i included), u2(A) = sum of r_i over A - |A|^2,
+ * so ways[c][s] += ways[c-1][s - r_i] per read, for the smaller class, le and
+ * ge swapped where that is haplotype 2.  C(64, 32) < 2^63: every count and
+ * intermediate fits 64 bits, which C(68, 34) does not; 64 is the limit.
+ * n_reads, n_short and u2 are pf_batch_ranktest's for the same batch, tags and
+ * min_calls, u2 also where status is 2. */
+#define PF_RANK_EXACT_MAX_READS 64u
+typedef struct pf_rank_exact {
+    uint32_t n_windows;
+    uint32_t min_calls;
+    uint32_t max_reads;
+    const uint32_t *n_reads;   /* [n_windows*2] counted reads tagged 0, tagged 1  */
+    const uint32_t *n_short;   /* [n_windows*2] participating reads below min_calls */
+    const uint32_t *status;    /* [n_windows] 0, 1, 2 as above                    */
+    const uint64_t *u2;        /* [n_windows] pf_rank_t.u2                        */
+    const uint64_t *total;     /* [n_windows] C(n, n1)                            */
+    const uint64_t *le;        /* [n_windows]                                     */
+    const uint64_t *ge;        /* [n_windows]                                     */
+    const uint64_t *two;       /* [n_windows]                                     */
+    float ms_kernels;          /* event-timed: the kernel only                    */
+} pf_rank_exact_t;
+/* Batches, tags, check order, return codes, the refusal while a run is in
+ * flight and ownership (pf_rank_exact_free) exactly as in pf_batch_ranktest;
+ * the batch is left as it was.  max_reads outside [2, PF_RANK_EXACT_MAX_READS]
+ * returns PF_ERR_ARG.  At most 512 workgroups, each taking every 512th window;
+ * a window's table lies in LDS where it has at most 8,113 cells of 8 bytes (up
+ * to 36 counted reads, or a small class), else in the workgroup's slab in
+ * device memory (358 KB at max_reads 64).  The result depends on no launch
+ * geometry, no table placement and no atomic order.  In the environment
+ * (tests): PF_RANKX_THREADS=<64|256|1024> sets the workgroup size (default
+ * 1024), PF_RANKX_HBM=1 puts every window's table in its slab (unset or 0: per
+ * window), PF_RANKX_GRID=<n>, 1 .. 65536, caps the workgroups; any other value
+ * of the three returns PF_ERR_ARG. */
+int  pf_batch_rankexact(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t min_calls,
+                        uint32_t max_reads, pf_rank_exact_t **out);
+void pf_rank_exact_free(pf_rank_exact_t *r);
+
+/* An exact p-value from its counts (host only): *p = (double)count /
+ * (double)total.  PF_ERR_ARG when total == 0 or count > total. */
+int  pf_rank_exact_p(uint64_t count, uint64_t total, double *p);
+
 /* Tags for untagged reads from a window's allele-specific methylation
  * (pf_assign.hip; no reference counterpart): inside a window [ws, we) where
  * the two haplotypes' methylation differs, an untagged read's own calls say
@@ -1863,6 +1919,50 @@ int  pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr
                          const pf_hapmeth_rank_t *rank, pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst,
                          pf_hapmeth_hmm_stats_t *hst, pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast,
                          pf_hapmeth_tagcheck_stats_t *tst, pf_hapmeth_regions_stats_t *rst, pf_hapmeth_rank_stats_t *kst);
+
+/* hapmeth --dmr-rank-exact: a region's window of pf_batch_rankexact, parallel
+ * to its pf_rank_rec_t. */
+typedef struct pf_rank_exact_rec {
+    uint64_t two, total;       /* pf_rank_exact_t.two, .total of its window       */
+    uint32_t status;           /* .status                                         */
+} pf_rank_exact_rec_t;
+/* {prefix}.hapmeth.rank.tsv with the exact test: pf_write_rank's line, its 17
+ * columns byte for byte, and three more,
+ *   exact_p best_p best_q
+ * exact_p = two / total (pf_rank_exact_p, %.6g) where xrec[i].status is 0, else
+ * "."; best_p = exact_p where that is numeric, else rank_p (which may be ".");
+ * best_q (%.6g) with bh != 0 by pf_bh_adjust_p over the records with a numeric
+ * best_p, "." with bh == 0 and where best_p is ".": the rule rank_q follows.
+ * *n_tested as in pf_write_rank; *n_exact: the records with a numeric exact_p.
+ * n != 0 without xrec, a status-0 xrec with total == 0 or two > total:
+ * PF_ERR_ARG. */
+int  pf_write_rank_exact(const char *path, const pf_rank_rec_t *rec, const pf_rank_exact_rec_t *xrec, uint64_t n, int bh,
+                         uint64_t *n_tested, uint64_t *n_exact);
+
+typedef struct pf_hapmeth_rank_exact {
+    uint32_t max_reads;        /* pf_batch_rankexact's, 2 .. 64; the CLI's default is 64   */
+} pf_hapmeth_rank_exact_t;
+
+typedef struct pf_hapmeth_rank_exact_stats {
+    uint64_t n_exact;          /* lines of the rank file with a numeric exact_p            */
+    uint64_t n_over;           /* lines whose region has more than max_reads counted reads */
+    double ms_kernels;         /* summed pf_rank_exact_t.ms_kernels                        */
+} pf_hapmeth_rank_exact_stats_t;
+
+/* pf_hapmeth_run_rank, and with exact != NULL the second pass also runs
+ * pf_batch_rankexact right after pf_batch_ranktest, on the same batch with the
+ * same min_calls (no further fetch), and the rank file is written by
+ * pf_write_rank_exact.  No other file changes.  exact == NULL: exactly
+ * pf_hapmeth_run_rank (xst is zeroed).  exact without rank, or max_reads
+ * outside [2, 64], returns PF_ERR_ARG. */
+int  pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                               const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                               const pf_hapmeth_tagcheck_t *tagcheck, const pf_hapmeth_regions_t *regions,
+                               const pf_hapmeth_rank_t *rank, const pf_hapmeth_rank_exact_t *exact, pf_hapmeth_stats_t *st,
+                               pf_hapmeth_dmr_stats_t *dst, pf_hapmeth_hmm_stats_t *hst, pf_hapmeth_perm_stats_t *pst,
+                               pf_hapmeth_assign_stats_t *ast, pf_hapmeth_tagcheck_stats_t *tst,
+                               pf_hapmeth_regions_stats_t *rst, pf_hapmeth_rank_stats_t *kst,
+                               pf_hapmeth_rank_exact_stats_t *xst);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

@@ -13,10 +13,10 @@ mirror of that interface:
 from .abi import (AlnBatch, Config, KnownVars, LoadConfig, ReadAlnBatch, WindowBatch, WindowResult,
                   HAPTAG_UNPHASED)
 from ._lib import (Context, DeviceBatch, PomfretError, device_count, fisher_exact, lib,
-                   methphase_windows, rank_p)
+                   methphase_windows, rank_exact_p, rank_p)
 
 __all__ = [
     "AlnBatch", "Config", "KnownVars", "LoadConfig", "ReadAlnBatch", "WindowBatch", "WindowResult", "HAPTAG_UNPHASED",
     "Context", "DeviceBatch", "PomfretError", "device_count", "fisher_exact", "lib",
-    "methphase_windows", "rank_p",
+    "methphase_windows", "rank_exact_p", "rank_p",
 ]

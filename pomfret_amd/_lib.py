@@ -13,7 +13,7 @@ import weakref
 import numpy as np
 
 from .abi import (DMR_HMM_SITES, DMR_RUN_DTYPE, REGION_SUM_DTYPE, PfRegions, HmmConfig, PfDmrHmm, PfDmrHmmCfg, AlnBatch, AssignConfig, PfAssign, PfAssignCfg, Config, DmrConfig, KnownVars, LoadConfig, PfAlnBatch, PfCfg, PfDmr, PfDmrCfg,
-                  PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfRank, PfReadAlnBatch, PfTagcheck, PfWindowBatch, PfWindowOut, ReadAlnBatch,
+                  PfKnownVars, PfLoadCfg, PfPerm, PfPileup, PfRank, PfRankExact, PfReadAlnBatch, PfTagcheck, PfWindowBatch, PfWindowOut, ReadAlnBatch,
                   WindowBatch, WindowResult)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -110,6 +110,10 @@ def lib():
         L.pf_batch_ranktest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                         C.POINTER(C.POINTER(PfRank))]
         L.pf_rank_free.argtypes = [C.POINTER(PfRank)]
+        L.pf_batch_rankexact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
+                                         C.POINTER(C.POINTER(PfRankExact))]
+        L.pf_rank_exact_free.argtypes = [C.POINTER(PfRankExact)]
+        L.pf_rank_exact_p.argtypes = [C.c_uint64, C.c_uint64, C.POINTER(C.c_double)]
         L.pf_rank_p.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64] + [C.POINTER(C.c_double)] * 3
         L.pf_batch_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(PfAssignCfg),
                                       C.POINTER(C.POINTER(PfAssign))]
@@ -398,6 +402,18 @@ def rank_p(u2, n1, n2, ties):
     a, z, p = C.c_double(), C.c_double(), C.c_double()
     _check(lib().pf_rank_p(int(u2), int(n1), int(n2), int(ties), C.byref(a), C.byref(z), C.byref(p)), "pf_rank_p")
     return a.value, z.value, p.value
+
+
+def rank_exact_p(count, total):
+    """count / total as a double (pf_rank_exact_p, host only): an exact p-value
+    of the rank-sum test from DeviceBatch.rankexact's integers -- two for the
+    two-sided one, le and ge for the one-sided ones."""
+    for v in (count, total):
+        if not 0 <= int(v) < 2 ** 64:
+            raise PomfretError("pf_rank_exact_p: an argument is out of range")
+    p = C.c_double()
+    _check(lib().pf_rank_exact_p(int(count), int(total), C.byref(p)), "pf_rank_exact_p")
+    return p.value
 
 
 class Context:
@@ -771,6 +787,41 @@ class DeviceBatch:
                         min_calls=int(r.min_calls), ms=float(r.ms_kernels))
         finally:
             lib().pf_rank_free(p)
+
+    def rankexact(self, min_calls: int = 3, max_reads: int = 64, read_hp=None) -> dict:
+        """The rank-sum test's exact null distribution for every window of at
+        most max_reads (2 .. 64) counted reads (pf_batch_rankexact;
+        include/pomfret_amd.h has the definition): dict(n_reads [W, 2], n_short
+        [W, 2] and u2 [W] as ranktest gives them, total [W] = C(n, n1), le, ge
+        and two [W] the assignments of the counted reads whose statistic is at
+        most / at least / at least as far from its centre as the observed one,
+        status [W] (0 tested, 1 a haplotype without a counted read, 2 more
+        than max_reads counted reads; the counts are 0 unless 0), min_calls,
+        max_reads, ms the kernel's time).  rank_exact_p(two, total) is the
+        two-sided p-value where status is 0.  read_hp as in pileup."""
+        hp_ptr, n_hp = None, 0
+        if read_hp is not None:
+            hp = np.zeros(np.size(read_hp) + 1, np.uint8)
+            hp[:-1] = np.asarray(read_hp, np.uint8).ravel()
+            hp_ptr, n_hp = hp.ctypes.data, hp.size - 1
+        if not 0 <= int(min_calls) <= 0xFFFFFFFF or not 0 <= int(max_reads) <= 0xFFFFFFFF:
+            raise PomfretError("pf_batch_rankexact: min_calls and max_reads are 32-bit unsigned")
+        p = C.POINTER(PfRankExact)()
+        _check(lib().pf_batch_rankexact(self.ctx.handle, self.handle, hp_ptr, n_hp, int(min_calls), int(max_reads),
+                                        C.byref(p)), "pf_batch_rankexact")
+        try:
+            r = p.contents
+            W = int(r.n_windows)
+
+            def arr(ptr, n, dt):
+                return np.ctypeslib.as_array(ptr, (n,)).copy() if W else np.zeros(0, dt)
+            return dict(n_reads=arr(r.n_reads, 2 * W, np.uint32).reshape(W, 2),
+                        n_short=arr(r.n_short, 2 * W, np.uint32).reshape(W, 2), u2=arr(r.u2, W, np.uint64),
+                        total=arr(r.total, W, np.uint64), le=arr(r.le, W, np.uint64), ge=arr(r.ge, W, np.uint64),
+                        two=arr(r.two, W, np.uint64), status=arr(r.status, W, np.uint32), min_calls=int(r.min_calls),
+                        max_reads=int(r.max_reads), ms=float(r.ms_kernels))
+        finally:
+            lib().pf_rank_exact_free(p)
 
     def assign(self, cfg: AssignConfig = None, read_hp=None) -> dict:
         """Tags for the batch's untagged reads from each window's

@@ -531,6 +531,29 @@ class PfHapmethRankStats(C.Structure):
                 ("ms_kernels", C.c_double)]
 
 
+class PfRankExact(C.Structure):
+    """pf_rank_exact_t: the exact rank-sum counts of a batch's windows (pf_batch_rankexact)."""
+    _fields_ = [("n_windows", C.c_uint32), ("min_calls", C.c_uint32), ("max_reads", C.c_uint32),
+                ("n_reads", C.POINTER(C.c_uint32)), ("n_short", C.POINTER(C.c_uint32)), ("status", C.POINTER(C.c_uint32)),
+                ("u2", C.POINTER(C.c_uint64)), ("total", C.POINTER(C.c_uint64)), ("le", C.POINTER(C.c_uint64)),
+                ("ge", C.POINTER(C.c_uint64)), ("two", C.POINTER(C.c_uint64)), ("ms_kernels", C.c_float)]
+
+
+class PfRankExactRec(C.Structure):
+    """pf_rank_exact_rec_t: the exact test beside a PfRankRec (pf_write_rank_exact)."""
+    _fields_ = [("two", C.c_uint64), ("total", C.c_uint64), ("status", C.c_uint32)]
+
+
+class PfHapmethRankExact(C.Structure):
+    """pf_hapmeth_rank_exact_t (pf_hapmeth_run_rank_exact)."""
+    _fields_ = [("max_reads", C.c_uint32)]
+
+
+class PfHapmethRankExactStats(C.Structure):
+    """pf_hapmeth_rank_exact_stats_t."""
+    _fields_ = [("n_exact", C.c_uint64), ("n_over", C.c_uint64), ("ms_kernels", C.c_double)]
+
+
 class PfAssignCfg(C.Structure):
     """pf_assign_cfg_t."""
     _fields_ = [("min_cov", C.c_uint32), ("min_calls", C.c_uint32), ("min_llr_q16", C.c_int64)]

@@ -12,7 +12,7 @@
  *                         [--dmr-blocks blocks.gtf] [--dmr-perm N [--dmr-seed S]]
  *                         [--dmr-hmm [--dmr-hmm-site-cost BITS] [--dmr-hmm-switch BITS]]
  *                         [--regions regions.bed  (instead of --dmr: the regions are given)]
- *                         [--dmr-rank [--dmr-rank-min-calls N]]
+ *                         [--dmr-rank [--dmr-rank-min-calls N] [--dmr-rank-exact [--dmr-rank-exact-max N]]]
  *                         [--assign] [--tag-check] [--assign-min-llr BITS] [--assign-min-calls N]] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
@@ -100,7 +100,7 @@ enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV
        O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
        O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED,
        O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK, O_DMR_HMM, O_DMR_HMM_SITE, O_DMR_HMM_SWITCH, O_REGIONS,
-       O_DMR_RANK, O_DMR_RANK_CALLS };
+       O_DMR_RANK, O_DMR_RANK_CALLS, O_DMR_RANK_EXACT, O_DMR_RANK_EXACT_MAX };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -126,6 +126,8 @@ static const struct option longopts[] = {
     {"dmr-hmm-switch", required_argument, 0, O_DMR_HMM_SWITCH},
     {"regions", required_argument, 0, O_REGIONS},
     {"dmr-rank", no_argument, 0, O_DMR_RANK},    {"dmr-rank-min-calls", required_argument, 0, O_DMR_RANK_CALLS},
+    {"dmr-rank-exact", no_argument, 0, O_DMR_RANK_EXACT},
+    {"dmr-rank-exact-max", required_argument, 0, O_DMR_RANK_EXACT_MAX},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -335,11 +337,20 @@ static void help_hapmeth(void) {
                     "               tested regions; \".\" with --dmr, whose regions are selected on the data).  rank_p is the\n"
                     "               two-sided normal approximation with tie and continuity correction: it has no floor and\n"
                     "               needs no permutations, but it is asymptotic, so approximate below about eight reads per\n"
-                    "               haplotype; the exact small-sample distribution is not computed.  rank_p underflows to 0\n"
+                    "               haplotype; --dmr-rank-exact adds the exact small-sample p-value.  rank_p underflows to 0\n"
                     "               near z > 38, which is why z has its own column.  \".\" in the four where a haplotype has no\n"
                     "               counted read, or a region more than 4096.\n");
     fprintf(stderr, "  --dmr-rank-min-calls N [opt] Needs --dmr-rank.  Calls inside the region a read needs to count, 1 .. 65535;\n"
                     "               a choice, not a measured optimum. [3]\n");
+    fprintf(stderr, "  --dmr-rank-exact [opt] Needs --dmr-rank.  Three more columns in {out_prefix}.hapmeth.rank.tsv: exact_p, the\n"
+                    "               exact two-sided p-value of the same test, counted over every way to deal the region's\n"
+                    "               counted reads to the two haplotypes, ties included (all integers; for two separated groups\n"
+                    "               of 10 reads it is 1.08e-5 where rank_p gives 1.83e-4); best_p, exact_p where there is one,\n"
+                    "               else rank_p; best_q, Benjamini-Hochberg over best_p with --regions, \".\" with --dmr.\n"
+                    "               exact_p is \".\" where a haplotype has no counted read or the region has more counted\n"
+                    "               reads than --dmr-rank-exact-max.  The first 17 columns do not change.\n");
+    fprintf(stderr, "  --dmr-rank-exact-max N [opt] Needs --dmr-rank-exact.  The most counted reads of a region that is counted\n"
+                    "               exactly, 2 .. 64 (the counts of 68 reads pass 64 bits). [64]\n");
     fprintf(stderr, "  --dmr-hmm [opt] Needs --dmr.  Find the regions with a three-state hidden Markov model (none, h1>h2,\n"
                     "               h1<h2) over each contig's CpGs instead of the per-CpG threshold: every CpG adds its\n"
                     "               evidence for one direction (log2 likelihood ratio of two methylation levels against\n"
@@ -399,7 +410,8 @@ static int hapmeth(int argc, char **argv) {
     pf_hapmeth_assign_t am;
     memset(&am, 0, sizeof am);
     int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0, tagcheck = 0, hmm = 0, hmm_opt = 0;
-    int gap_opt = 0, rank = 0, rank_opt = 0;
+    int gap_opt = 0, rank = 0, rank_opt = 0, exact = 0, exact_opt = 0;
+    long xmax = 64;
     long rcalls = 3;
     pf_hapmeth_regions_t rg;
     rg.bed_path = NULL;
@@ -438,6 +450,8 @@ static int hapmeth(int argc, char **argv) {
         case O_DMR_HMM: hmm = 1; break;
         case O_REGIONS: rg.bed_path = optarg; break;
         case O_DMR_RANK: rank = 1; break;
+        case O_DMR_RANK_EXACT: exact = 1; break;
+        case O_DMR_RANK_EXACT_MAX: exact_opt = 1; xmax = strtol(optarg, &end, 10); if (*end || !*optarg) xmax = -1; break;
         case O_DMR_RANK_CALLS: rank_opt = 1; rcalls = strtol(optarg, &end, 10); if (*end || !*optarg) rcalls = -1; break;
         case O_DMR_HMM_SITE: hmm_opt = 1; hsite = strtod(optarg, &end); if (*end || !*optarg) hsite = -1.0; break;
         case O_DMR_HMM_SWITCH: hmm_opt = 1; hswitch = strtod(optarg, &end); if (*end || !*optarg) hswitch = -1.0; break;
@@ -478,6 +492,9 @@ static int hapmeth(int argc, char **argv) {
     if (tagcheck && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --tag-check needs --dmr or --regions\n"); return 1; }
     if (rank && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-rank needs --dmr or --regions\n"); return 1; }
     if (rank_opt && !rank) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-rank-min-calls needs --dmr-rank\n"); return 1; }
+    if (exact && !rank) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-rank-exact needs --dmr-rank\n"); return 1; }
+    if (exact_opt && !exact) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-rank-exact-max needs --dmr-rank-exact\n"); return 1; }
+    if (xmax < 2 || xmax > 64) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-rank-exact-max (2 .. 64)\n"); return 1; }
     if (rcalls < 1 || rcalls > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-rank-min-calls (1 .. 65535)\n"); return 1; }
     if (hmm_opt && !hmm) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-hmm-* options need --dmr-hmm\n"); return 1; }
     if (hmm && !dmr) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-hmm needs --dmr\n"); return 1; }
@@ -511,9 +528,13 @@ static int hapmeth(int argc, char **argv) {
     pf_hapmeth_rank_t km;
     km.min_calls = (uint32_t)rcalls;
     pf_hapmeth_rank_stats_t kst;
-    const int rc = pf_hapmeth_run_rank(&op, have ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
+    pf_hapmeth_rank_exact_t xm;
+    xm.max_reads = (uint32_t)xmax;
+    pf_hapmeth_rank_exact_stats_t xst;
+    const int rc = pf_hapmeth_run_rank_exact(&op, have ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
                                        assign || tagcheck ? &am : NULL, tagcheck ? &tm : NULL, rg.bed_path ? &rg : NULL,
-                                       rank ? &km : NULL, &st, &dst, &hst, &pst, &ast, &tst, &rst, &kst);
+                                       rank ? &km : NULL, exact ? &xm : NULL, &st, &dst, &hst, &pst, &ast, &tst, &rst, &kst,
+                                       &xst);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;
@@ -530,6 +551,9 @@ static int hapmeth(int argc, char **argv) {
     if (rank)
         fprintf(stderr, "[M::main] %llu regions written to %s.hapmeth.rank.tsv, %llu of them with a rank-sum p-value\n",
                 (unsigned long long)(kst.n_tested + kst.n_untested), op.out_prefix, (unsigned long long)kst.n_tested);
+    if (exact)
+        fprintf(stderr, "[M::main] %llu of them with an exact p-value, %llu with more than %u counted reads\n",
+                (unsigned long long)xst.n_exact, (unsigned long long)xst.n_over, xm.max_reads);
     if (assign)
         fprintf(stderr, "[M::main] %llu scored reads written to %s.hapmeth.assign.tsv, %llu of them with a tag\n",
                 (unsigned long long)ast.n_lines, op.out_prefix, (unsigned long long)(ast.n_h1 + ast.n_h2));

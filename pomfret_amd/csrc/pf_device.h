@@ -58,6 +58,13 @@
 #define PF_RANK_THREADS_MAX 1024
 #define PF_RANK_READS 4096          /* counted reads per window held in LDS (PF_RANK_MAX_READS): 8 B each, 32 KB */
 #define PF_RANK_NARROW_MAX 65535u   /* a window whose largest n_i is at most this compares 32-bit products */
+#define PF_RANKX_THREADS 1024       /* the exact rank test's workgroup (PF_RANKX_THREADS=<64|256|1024> overrides it;
+                                      measured: profiles/rank_exact/README.md) */
+#define PF_RANKX_READS 64           /* counted reads of a window the exact test takes (PF_RANK_EXACT_MAX_READS) */
+#define PF_RANKX_LDS_CELLS 8113u    /* its LDS array in cells of 8 B: the table of 36 reads, 18 a class (63.4 KB); during
+                                      the read loop the same array holds the counted reads */
+#define PF_RANKX_SLAB_CELLS 44737u  /* the table of 64 reads, 32 a class: the largest per-workgroup slab in HBM, 358 KB */
+#define PF_RANKX_GRID 512u          /* at most this many workgroups, one slab each (PF_RANKX_GRID=<n> overrides it) */
 #define PF_ASSIGN_TILE 4096         /* sites per LDS tile of pf_assign_score: position and two weights, 12 B each, 48 KB
                                       (PF_ASSIGN_TILE=<n> overrides it downwards) */
 #define PF_ASSIGN_THREADS 256       /* its workgroup: each wave takes 64 of the window's reads at a time (1,024 measured:

@@ -51,7 +51,11 @@
  *                     of doubles, and {prefix}.hapmeth.rank.tsv (host only);
  *   pf_hapmeth_run_rank: pf_hapmeth_run_regions, and with --dmr-rank the second
  *                     pass also runs pf_batch_ranktest on its batch; one record
- *                     per region, the file written at the run's end.
+ *                     per region, the file written at the run's end;
+ *   pf_rank_exact_p, pf_write_rank_exact, pf_hapmeth_run_rank_exact: with
+ *                     --dmr-rank-exact pf_batch_rankexact follows the rank test
+ *                     on the same batch and the rank file gains exact_p, best_p
+ *                     and best_q.
  */
 #include <math.h>
 #include <stdint.h>
@@ -489,48 +493,98 @@ int pf_bh_adjust_p(const double *p, const uint8_t *tested, uint64_t n, double *q
     return PF_OK;
 }
 
-int pf_write_rank(const char *path, const pf_rank_rec_t *rec, uint64_t n, int bh, uint64_t *n_tested) {
+int pf_rank_exact_p(uint64_t count, uint64_t total, double *p) {
+    if (total == 0 || count > total) return PF_ERR_ARG;
+    if (p) *p = (double)count / (double)total;
+    return PF_OK;
+}
+
+/* the rank file; with xrec the three columns of the exact test after pf_write_rank's line */
+static int rank_file(const char *path, const pf_rank_rec_t *rec, const pf_rank_exact_rec_t *xrec, uint64_t n, int bh,
+                     uint64_t *n_tested, uint64_t *n_exact) {
     if (n_tested) *n_tested = 0;
+    if (n_exact) *n_exact = 0;
     if (!path || (n && !rec)) return PF_ERR_ARG;
-    double *pv = NULL, *q = NULL;
-    uint8_t *tested = NULL;
+    double *pv = NULL, *q = NULL, *bp = NULL, *bq = NULL;
+    uint8_t *tested = NULL, *best = NULL;
     if (n) {
+        const int x = xrec != NULL;
         pv = (double *)malloc(8ull * n);
         q = (double *)malloc(8ull * n);
         tested = (uint8_t *)malloc(n);
-        int rc = pv && q && tested ? PF_OK : PF_ERR_NOMEM;
+        bp = x ? (double *)malloc(8ull * n) : NULL;
+        bq = x ? (double *)malloc(8ull * n) : NULL;
+        best = x ? (uint8_t *)malloc(n) : NULL;
+        int rc = pv && q && tested && (!x || (bp && bq && best)) ? PF_OK : PF_ERR_NOMEM;
         for (uint64_t i = 0; i < n && !rc; i++) {
             pv[i] = 1.0;
             tested[i] = rec[i].status == 0;
             if (tested[i]) rc = pf_rank_p(rec[i].u2, rec[i].reads[0], rec[i].reads[1], rec[i].ties, NULL, NULL, pv + i);
+            if (x && !rc) {
+                bp[i] = pv[i];
+                best[i] = tested[i];
+                if (xrec[i].status == 0) {
+                    rc = pf_rank_exact_p(xrec[i].two, xrec[i].total, bp + i);
+                    best[i] = 1;
+                }
+            }
         }
         if (!rc && bh) rc = pf_bh_adjust_p(pv, tested, n, q);
-        if (rc) { free(pv); free(q); free(tested); return rc; }
+        if (!rc && bh && x) rc = pf_bh_adjust_p(bp, best, n, bq);
+        if (rc) { free(pv); free(q); free(tested); free(bp); free(bq); free(best); return rc; }
     }
     FILE *fp = fopen(path, "w");
-    if (!fp) { free(pv); free(q); free(tested); return -1; }
+    if (!fp) { free(pv); free(q); free(tested); free(bp); free(bq); free(best); return -1; }
     fprintf(fp, "#chrom\tstart\tend\treads_h1\treads_h2\tshort_h1\tshort_h2\tallmeth_h1\tallunmeth_h1\tmixed_h1\tallmeth_h2"
-            "\tallunmeth_h2\tmixed_h2\tauc\tz\trank_p\trank_q\n");
+            "\tallunmeth_h2\tmixed_h2\tauc\tz\trank_p\trank_q%s\n", xrec ? "\texact_p\tbest_p\tbest_q" : "");
     for (uint64_t i = 0; i < n; i++) {
         const pf_rank_rec_t *r = rec + i;
         fprintf(fp, "%s\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u", r->chrom ? r->chrom : ".", r->start, r->end,
                 r->reads[0], r->reads[1], r->n_short[0], r->n_short[1], r->cls[0], r->cls[1], r->cls[2], r->cls[3], r->cls[4],
                 r->cls[5]);
-        if (!tested[i]) fprintf(fp, "\t.\t.\t.\t.\n");
+        if (!tested[i]) fprintf(fp, "\t.\t.\t.\t.");
         else {
             double auc = 0.0, z = 0.0, p = 1.0;
             (void)pf_rank_p(r->u2, r->reads[0], r->reads[1], r->ties, &auc, &z, &p);
             fprintf(fp, "\t%.4f\t%.3f\t%.6g\t", auc, z, p);
-            if (bh) fprintf(fp, "%.6g\n", q[i]); else fprintf(fp, ".\n");
+            if (bh) fprintf(fp, "%.6g", q[i]); else fprintf(fp, ".");
             if (n_tested) ++*n_tested;
         }
+        if (xrec) {
+            if (xrec[i].status == 0) {
+                fprintf(fp, "\t%.6g", bp[i]);
+                if (n_exact) ++*n_exact;
+            } else fprintf(fp, "\t.");
+            if (!best[i]) fprintf(fp, "\t.\t.");
+            else {
+                fprintf(fp, "\t%.6g\t", bp[i]);
+                if (bh) fprintf(fp, "%.6g", bq[i]); else fprintf(fp, ".");
+            }
+        }
+        fputc('\n', fp);
     }
     free(pv);
     free(q);
     free(tested);
+    free(bp);
+    free(bq);
+    free(best);
     const int bad = ferror(fp);
     if (fclose(fp) != 0 || bad) return -1;
     return PF_OK;
+}
+
+int pf_write_rank(const char *path, const pf_rank_rec_t *rec, uint64_t n, int bh, uint64_t *n_tested) {
+    return rank_file(path, rec, NULL, n, bh, n_tested, NULL);
+}
+
+int pf_write_rank_exact(const char *path, const pf_rank_rec_t *rec, const pf_rank_exact_rec_t *xrec, uint64_t n, int bh,
+                        uint64_t *n_tested, uint64_t *n_exact) {
+    if (n_tested) *n_tested = 0;
+    if (n_exact) *n_exact = 0;
+    if (n && !xrec) return PF_ERR_ARG;
+    static const pf_rank_exact_rec_t none = {0, 0, 1};
+    return rank_file(path, rec, xrec ? xrec : &none, n, bh, n_tested, n_exact);
 }
 
 /* "chrom" or "chrom:beg-end" / "chrom:beg" (1-based inclusive, commas allowed)
@@ -617,6 +671,11 @@ typedef struct {
     pf_rank_rec_t *krec;       /* the run's regions of the second pass, in the pass's order */
     size_t nk, mk;
     pf_hapmeth_rank_stats_t kst;
+    /* --dmr-rank-exact */
+    const pf_hapmeth_rank_exact_t *exact;
+    pf_rank_exact_rec_t *xrec; /* parallel to krec */
+    size_t mx;
+    pf_hapmeth_rank_exact_stats_t xst;
 } hm_t;
 
 /* the fetch of one job, the same in both passes: the records of the windows
@@ -908,6 +967,26 @@ static int hm_second(hm_t *H, const char *chrom, const pf_dmr_t *fin, pf_perm_t 
                 r->status = rk->status[j]; r->u2 = rk->u2[j]; r->ties = rk->ties[j];
             }
             if (!rc) H->kst.ms_kernels += rk->ms_kernels;
+            if (!rc && H->exact) {                     /* the same batch, the same min_calls: no further fetch */
+                pf_rank_exact_t *xr = NULL;
+                rc = pf_batch_rankexact(H->ctx, db, NULL, 0, H->rank->min_calls, H->exact->max_reads, &xr);
+                if (!rc && xr->n_windows != k) rc = PF_ERR_INTERNAL;
+                if (!rc && H->nk > H->mx) {
+                    pf_rank_exact_rec_t *p = (pf_rank_exact_rec_t *)realloc(H->xrec, H->mk * sizeof *p);
+                    if (!p) rc = PF_ERR_NOMEM;
+                    else { H->xrec = p; H->mx = H->mk; }
+                }
+                for (uint32_t j = 0; j < k && !rc; j++) {
+                    pf_rank_exact_rec_t *x = H->xrec + (H->nk - k + j);
+                    if (xr->u2[j] != rk->u2[j] || xr->n_reads[2 * j] != rk->n_reads[2 * j] ||
+                        xr->n_reads[2 * j + 1] != rk->n_reads[2 * j + 1])
+                        rc = PF_ERR_INTERNAL;          /* the two kernels count the same reads */
+                    x->two = xr->two[j]; x->total = xr->total[j]; x->status = xr->status[j];
+                    if (x->status == 2) H->xst.n_over++;
+                }
+                if (!rc) H->xst.ms_kernels += xr->ms_kernels;
+                pf_rank_exact_free(xr);
+            }
             pf_rank_free(rk);
         }
         if (!rc && H->assign) {
@@ -1133,6 +1212,19 @@ int pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
                         pf_hapmeth_hmm_stats_t *hstats, pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats,
                         pf_hapmeth_tagcheck_stats_t *tstats, pf_hapmeth_regions_stats_t *rstats,
                         pf_hapmeth_rank_stats_t *kstats) {
+    return pf_hapmeth_run_rank_exact(o, dmr, hmm, perm, assign, tagcheck, regions, rank, NULL, stats, dstats, hstats, pstats,
+                                     astats, tstats, rstats, kstats, NULL);
+}
+
+int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                              const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                              const pf_hapmeth_tagcheck_t *tagcheck, const pf_hapmeth_regions_t *regions,
+                              const pf_hapmeth_rank_t *rank, const pf_hapmeth_rank_exact_t *exact, pf_hapmeth_stats_t *stats,
+                              pf_hapmeth_dmr_stats_t *dstats, pf_hapmeth_hmm_stats_t *hstats, pf_hapmeth_perm_stats_t *pstats,
+                              pf_hapmeth_assign_stats_t *astats, pf_hapmeth_tagcheck_stats_t *tstats,
+                              pf_hapmeth_regions_stats_t *rstats, pf_hapmeth_rank_stats_t *kstats,
+                              pf_hapmeth_rank_exact_stats_t *xstats) {
+    if (xstats) memset(xstats, 0, sizeof *xstats);
     if (kstats) memset(kstats, 0, sizeof *kstats);
     if (rstats) memset(rstats, 0, sizeof *rstats);
     if (hstats) memset(hstats, 0, sizeof *hstats);
@@ -1153,9 +1245,11 @@ int pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
         return PF_ERR_ARG;
     if (regions && (!dmr || hmm || !regions->bed_path)) return PF_ERR_ARG;
     if (rank && (!dmr || rank->min_calls < 1u || rank->min_calls > 65535u)) return PF_ERR_ARG;
+    if (exact && (!rank || exact->max_reads < 2u || exact->max_reads > PF_RANK_EXACT_MAX_READS)) return PF_ERR_ARG;
     hm_t H;
     memset(&H, 0, sizeof H);
     H.rank = rank;
+    H.exact = exact;
     H.regions = regions;
     H.o = o;
     H.dmr = dmr;
@@ -1282,7 +1376,11 @@ int pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
     if (!rc && rank) {                                 /* at the end: rank_q needs every region */
         uint64_t tested = 0;
         kmade = 1;
-        rc = pf_write_rank(H.kpath, H.krec, H.nk, regions != NULL, &tested);
+        if (exact) {
+            uint64_t nx = 0;
+            rc = pf_write_rank_exact(H.kpath, H.krec, H.xrec, H.nk, regions != NULL, &tested, &nx);
+            H.xst.n_exact = nx;
+        } else rc = pf_write_rank(H.kpath, H.krec, H.nk, regions != NULL, &tested);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.kpath);
         H.kst.n_tested = tested;
         H.kst.n_untested = H.nk - tested;
@@ -1319,6 +1417,10 @@ int pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
         fprintf(stderr, "[M::pf_hapmeth_main] rank test: %llu regions tested (at least %u calls a read), %llu without a test, "
                 "%llu records fetched for it, rank kernels %.3f ms\n", (unsigned long long)H.kst.n_tested, rank->min_calls,
                 (unsigned long long)H.kst.n_untested, (unsigned long long)H.kst.n_records, H.kst.ms_kernels);
+    if (!rc && o->verbose && exact)
+        fprintf(stderr, "[M::pf_hapmeth_main] exact rank test: %llu regions with an exact p-value (at most %u reads), %llu over "
+                "the limit, exact kernels %.3f ms\n", (unsigned long long)H.xst.n_exact, exact->max_reads,
+                (unsigned long long)H.xst.n_over, H.xst.ms_kernels);
     if (!rc && o->verbose && assign)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu candidate reads scored, %llu assigned (%llu h1 / %llu h2), "
                 "%llu records fetched for it, assign kernels %.3f ms\n", (unsigned long long)H.ast.n_lines,
@@ -1343,6 +1445,7 @@ int pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
     if (hstats) *hstats = H.hst;
     if (rstats) *rstats = H.rst;
     if (kstats) *kstats = H.kst;
+    if (xstats) *xstats = H.xst;
     free(ws);
     free(we);
     free(H.path);
@@ -1356,6 +1459,7 @@ int pf_hapmeth_run_rank(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr,
     free(H.rpath);
     free(H.kpath);
     free(H.krec);
+    free(H.xrec);
     free(H.rec);
     free(H.ks);
     free(H.ke);

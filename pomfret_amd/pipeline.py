@@ -37,7 +37,7 @@ from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfH
                   AssignConfig, HAPMETH_TAGCHECK_RULE_ONLY, PfAssign, PfHapmethAssign, PfHapmethAssignStats,
                   PfHapmethTagcheck, PfHapmethTagcheckStats, PfTagcheck, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup,
                   HmmConfig, PfHapmethHmm, PfHapmethHmmStats, PfHapmethRegions, PfHapmethRegionsStats, PfRegionRec,
-                  PfHapmethRank, PfHapmethRankStats, PfRankRec,
+                  PfHapmethRank, PfHapmethRankStats, PfRankRec, PfHapmethRankExact, PfHapmethRankExactStats, PfRankExactRec,
                   REGION_ELIGIBLE, REGION_SPLIT)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
@@ -152,6 +152,16 @@ def _bind():
                                       C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
                                       C.POINTER(PfHapmethTagcheckStats), C.POINTER(PfHapmethRegionsStats),
                                       C.POINTER(PfHapmethRankStats)]
+    L.pf_hapmeth_run_rank_exact.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethHmm),
+                                            C.POINTER(PfHapmethPerm), C.POINTER(PfHapmethAssign),
+                                            C.POINTER(PfHapmethTagcheck), C.POINTER(PfHapmethRegions),
+                                            C.POINTER(PfHapmethRank), C.POINTER(PfHapmethRankExact), C.POINTER(PfHapmethStats),
+                                            C.POINTER(PfHapmethDmrStats), C.POINTER(PfHapmethHmmStats),
+                                            C.POINTER(PfHapmethPermStats), C.POINTER(PfHapmethAssignStats),
+                                            C.POINTER(PfHapmethTagcheckStats), C.POINTER(PfHapmethRegionsStats),
+                                            C.POINTER(PfHapmethRankStats), C.POINTER(PfHapmethRankExactStats)]
+    L.pf_write_rank_exact.argtypes = [C.c_char_p, C.POINTER(PfRankRec), C.POINTER(PfRankExactRec), C.c_uint64, C.c_int,
+                                      C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.pf_bh_adjust_p.argtypes = [vp, vp, C.c_uint64, vp]
     L.pf_write_rank.argtypes = [C.c_char_p, C.POINTER(PfRankRec), C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pf_regions_load.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(vp)]
@@ -529,7 +539,7 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
                   dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1,
                   assign: Optional[AssignConfig] = None, tag_check=False,
                   dmr_hmm: Optional[HmmConfig] = None, regions: Optional[str] = None, dmr_rank: bool = False,
-                  dmr_rank_min_calls: int = 3) -> Dict:
+                  dmr_rank_min_calls: int = 3, rank_exact: bool = False, rank_exact_max: int = 64) -> Dict:
     """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
@@ -594,7 +604,14 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     optimum).  rank_p is the asymptotic two-sided p-value (approximate below
     about eight reads per haplotype), rank_q its Benjamini-Hochberg q-value
     with regions, "." with found regions.  Adds rank_path, rank_tested,
-    rank_untested, rank_records and rank_ms_kernels to the dict."""
+    rank_untested, rank_records and rank_ms_kernels to the dict.
+    rank_exact: True (`--dmr-rank-exact`; needs dmr_rank) adds exact_p, best_p
+    and best_q to the rank file (pf_write_rank_exact): the exact two-sided
+    p-value of the same test for regions of at most rank_exact_max (2 .. 64)
+    counted reads, exact_p where there is one and rank_p elsewhere, and its
+    q-value with regions.  The file's first 17 columns and every other file
+    stay the same bytes.  Adds rank_exact (lines with an exact_p),
+    rank_exact_over (regions over rank_exact_max) and rank_exact_ms_kernels."""
     L = _bind()
     if regions is not None:
         if dmr_hmm is not None:
@@ -613,6 +630,10 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
         raise PomfretError("hapmeth_files: with assign, tag_check checks assign's rule: pass True")
     if dmr_rank and dmr is None:
         raise PomfretError("hapmeth_files: dmr_rank needs dmr or regions")
+    if rank_exact and not dmr_rank:
+        raise PomfretError("hapmeth_files: rank_exact needs dmr_rank")
+    if rank_exact and not 2 <= int(rank_exact_max) <= 64:
+        raise PomfretError("hapmeth_files: rank_exact_max is 2 .. 64")
     if dmr_rank and not 1 <= int(dmr_rank_min_calls) <= 65535:
         raise PomfretError("hapmeth_files: dmr_rank_min_calls is 1 .. 65535")
     lc = lcfg or LoadConfig(min_len=0)
@@ -634,12 +655,14 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
             hm = PfHapmethHmm(dmr_hmm.to_c()) if dmr_hmm is not None else None
             km, kst = PfHapmethRank(int(dmr_rank_min_calls)), PfHapmethRankStats()
             hst, ast, tst, rst = PfHapmethHmmStats(), PfHapmethAssignStats(), PfHapmethTagcheckStats(), PfHapmethRegionsStats()
-            _check(L.pf_hapmeth_run_rank(C.byref(o), C.byref(d), C.byref(hm) if hm is not None else None,
-                                         C.byref(pm) if dmr_perm else None,
-                                         C.byref(am) if assign is not None or tag_check else None,
-                                         C.byref(tm) if tag_check else None, C.byref(rg) if rg is not None else None,
-                                         C.byref(km), C.byref(st), C.byref(dst), C.byref(hst), C.byref(pst), C.byref(ast),
-                                         C.byref(tst), C.byref(rst), C.byref(kst)), "pf_hapmeth_run_rank")
+            xm, xst = PfHapmethRankExact(int(rank_exact_max)), PfHapmethRankExactStats()
+            _check(L.pf_hapmeth_run_rank_exact(C.byref(o), C.byref(d), C.byref(hm) if hm is not None else None,
+                                               C.byref(pm) if dmr_perm else None,
+                                               C.byref(am) if assign is not None or tag_check else None,
+                                               C.byref(tm) if tag_check else None, C.byref(rg) if rg is not None else None,
+                                               C.byref(km), C.byref(xm) if rank_exact else None, C.byref(st), C.byref(dst),
+                                               C.byref(hst), C.byref(pst), C.byref(ast), C.byref(tst), C.byref(rst),
+                                               C.byref(kst), C.byref(xst)), "pf_hapmeth_run_rank_exact")
         elif regions is not None:
             rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
             am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
@@ -697,6 +720,9 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
             res.update(rank_path=out_prefix + ".hapmeth.rank.tsv", rank_tested=int(kst.n_tested),
                        rank_untested=int(kst.n_untested), rank_records=int(kst.n_records),
                        rank_ms_kernels=float(kst.ms_kernels))
+        if rank_exact:
+            res.update(rank_exact=int(xst.n_exact), rank_exact_over=int(xst.n_over),
+                       rank_exact_ms_kernels=float(xst.ms_kernels))
         if assign is not None:
             res.update(assign_path=out_prefix + ".hapmeth.assign.tsv", n_assign_lines=int(ast.n_lines),
                        n_assigned=int(ast.n_h1 + ast.n_h2), n_assigned_h1=int(ast.n_h1), n_assigned_h2=int(ast.n_h2),
@@ -847,6 +873,29 @@ def write_rank(path: str, recs, bh: bool = False) -> int:
     n = C.c_uint64()
     _check(L.pf_write_rank(path.encode(), arr, len(recs), int(bool(bh)), C.byref(n)), "pf_write_rank")
     return int(n.value)
+
+
+def write_rank_exact(path: str, recs, bh: bool = False):
+    """The rank file with exact_p, best_p and best_q (pf_write_rank_exact, host
+    only).  recs: write_rank's dicts with the exact test's two, total and
+    exact_status beside them -- a window of DeviceBatch.rankexact.  Returns
+    (the records with a numeric rank_p, those with a numeric exact_p)."""
+    L = _bind()
+    arr = (PfRankRec * max(len(recs), 1))()
+    xarr = (PfRankExactRec * max(len(recs), 1))()
+    for k, r in enumerate(recs):
+        x = arr[k]
+        x.chrom, x.start, x.end = r["chrom"].encode(), int(r["start"]), int(r["end"])
+        for j in range(2):
+            x.reads[j], x.n_short[j] = int(r["n_reads"][j]), int(r["n_short"][j])
+        for j, v in enumerate(np.asarray(r["cls"]).ravel().tolist()):
+            x.cls[j] = int(v)
+        x.status, x.u2, x.ties = int(r["status"]), int(r["u2"]), int(r["ties"])
+        xarr[k].two, xarr[k].total, xarr[k].status = int(r["two"]), int(r["total"]), int(r["exact_status"])
+    n, nx = C.c_uint64(), C.c_uint64()
+    _check(L.pf_write_rank_exact(path.encode(), arr, xarr, len(recs), int(bool(bh)), C.byref(n), C.byref(nx)),
+           "pf_write_rank_exact")
+    return int(n.value), int(nx.value)
 
 
 def write_regions(path: str, recs, perm: bool = False, n_perm: int = 0) -> int:
