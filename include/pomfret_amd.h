@@ -676,6 +676,34 @@ int  pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, u
                        pf_rank_t **out);
 void pf_rank_free(pf_rank_t *r);
 
+/* The same test over position ranges inside the batch's windows (pf_rank.hip,
+ * pf_rank_ranges): range i of window w (rng_off[w] <= i <
+ * rng_off[w+1]) is tested over window w's reads by pf_batch_ranktest's
+ * definition, word for word, with ws, we := rng_start[i], rng_end[i].
+ * Participating and counted reads, order, statistic, ties, classes, sum,
+ * status 0 / 1 / 2 and the N < 2^31 limit hold per range; a read takes part
+ * in every range it has calls in.  The result's n_windows is the number of
+ * ranges, every array holds one entry per range in range order, and
+ * pf_rank_free frees it.  Ranges of one window may overlap and may be empty
+ * (start == end: status 1 and zeros); a window may have no range.  rng_off is
+ * [n_windows + 1] with rng_off[0] == 0, non-decreasing (it may be NULL for a
+ * batch without windows); rng_start / rng_end hold rng_off[n_windows] entries.
+ * PF_ERR_ARG: ws <= start <= end <= we violated for a range of window [ws,
+ * we), rng_off not as above, more than 2^31 - 1 ranges, min_calls outside [1,
+ * 65535]; PF_ERR_LIMIT: N >= 2^31 in a range, or ranges times the workgroup
+ * size above 2^32 - 1 (one workgroup per range, one launch: 16.7 M ranges at
+ * the default 256 threads, 67 M at 64).  Batches, the tag override, the
+ * refusal while a run is in flight and ownership as in pf_batch_ranktest; the
+ * batch is left as it was.  A workgroup keeps its counted reads in an LDS
+ * array of min(4,096, the reads of the largest window that has a range),
+ * rounded up to a power of two.  The result depends on neither the launch
+ * geometry, the product width nor any atomic order.  In the environment
+ * (tests): PF_RANK_THREADS and PF_RANK_WIDE as in pf_batch_ranktest;
+ * PF_RANKR_LDS_FIXED=1 takes the 4,096-read array whatever the batch (unset or
+ * 0: sized as above); any other value returns PF_ERR_ARG. */
+int  pf_batch_rankranges(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t min_calls,
+                         const uint64_t *rng_off, const uint32_t *rng_start, const uint32_t *rng_end, pf_rank_t **out);
+
 /* The rank test's two-sided p-value by the normal approximation with tie and
  * continuity correction (host only), in doubles in exactly this order:
  *   a = (double)n1 * (double)n2;  n = (double)n1 + (double)n2;
@@ -1963,6 +1991,67 @@ int  pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_
                                pf_hapmeth_assign_stats_t *ast, pf_hapmeth_tagcheck_stats_t *tst,
                                pf_hapmeth_regions_stats_t *rst, pf_hapmeth_rank_stats_t *kst,
                                pf_hapmeth_rank_exact_stats_t *xst);
+
+/* hapmeth --tile: what a tile's line holds beside its pf_rank_rec_t. */
+typedef struct pf_rank_tile_rec {
+    uint64_t sum[4];           /* pf_rank_t.sum of its range: the counted reads' m1, u1, m2, u2 */
+    uint32_t split;            /* non-zero: a phase-block break x with start < x < end (the
+                                  PF_REGION_SPLIT rule): counted, never tested             */
+} pf_rank_tile_rec_t;
+/* {prefix}.hapmeth.tiles.tsv, the whole file: pf_write_rank's line, its 17
+ * columns by the same code, and six more,
+ *   h1_meth h1_unmeth h2_meth h2_unmeth delta block
+ * the counted reads' sums, delta as in pf_write_dmr (%.4f; "." where a
+ * haplotype has no counted call) and block "ok" or "split".  A split record
+ * prints "." in auc, z, rank_p and rank_q.  rank_q is pf_bh_adjust_p over the
+ * status-0 records of rec[0, n) that are not split: the tiles are fixed in
+ * advance, so the correction holds.  No record: the header alone.  *n_tested:
+ * the records with a numeric rank_p.  n != 0 without trec: PF_ERR_ARG; -1 when
+ * the file cannot be written. */
+int  pf_write_rank_tiles(const char *path, const pf_rank_rec_t *rec, const pf_rank_tile_rec_t *trec, uint64_t n,
+                         uint64_t *n_tested);
+
+typedef struct pf_hapmeth_tiles {
+    uint32_t tile;             /* tile width T in bases, 100 .. the chunk size, which must be a
+                                  multiple of it                                           */
+    uint32_t min_calls;        /* pf_batch_rankranges', 1 .. 65535; the CLI's default is 3  */
+    const char *blocks_path;   /* NULL, or a phase-block GTF, read where the run has no dmr;
+                                  with dmr the run's one table is dmr->blocks_path        */
+} pf_hapmeth_tiles_t;
+
+typedef struct pf_hapmeth_tiles_stats {
+    uint64_t n_tiles;          /* tiles planned: ceil(span / T) over the run's spans        */
+    uint64_t n_written;        /* lines of the tile file: tiles with a participating read   */
+    uint64_t n_tested;         /* of those, with a numeric rank_p                           */
+    uint64_t n_split;          /* of those, with block "split"                              */
+    double ms_kernels;         /* summed pf_rank_t.ms_kernels of the range calls            */
+} pf_hapmeth_tiles_stats_t;
+
+/* pf_hapmeth_run_rank_exact, and with tiles != NULL {out_prefix}.hapmeth.tiles.tsv
+ * (pf_write_rank_tiles): a genome-wide scan in the first pass.  A span [s, e)
+ * -- a contig, or opts.region -- is cut into the tiles [s + j*T, min(s +
+ * (j+1)*T, e)); the chunk size is a multiple of T, so a tile lies in one fetch
+ * window, and a window the index holds no chunk for contributes none.  After
+ * each job's pileup one pf_batch_rankranges call on the same batch (its calls
+ * taken as the pileup left them, no second load stage) tests the tiles of the
+ * job's windows under the records' HP tags; a tile with a participating read on
+ * either haplotype becomes a record, kept on the host (120 bytes each) until
+ * the file is written at the run's end, because rank_q needs all of them.
+ * Neither the chunk size, the job size nor the fetch kind changes a byte.
+ * Tiles need no dmr and combine with every other option; no other file
+ * changes with tiles.  tiles == NULL: exactly pf_hapmeth_run_rank_exact (lst is
+ * zeroed).  T below 100 or above the chunk size, a chunk size that is no
+ * multiple of T, or min_calls outside [1, 65535] returns PF_ERR_ARG before
+ * any file is made.  On failure every file is unlinked.  Every stats pointer
+ * may be NULL. */
+int  pf_hapmeth_run_tiles(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                          const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                          const pf_hapmeth_tagcheck_t *tagcheck, const pf_hapmeth_regions_t *regions,
+                          const pf_hapmeth_rank_t *rank, const pf_hapmeth_rank_exact_t *exact, const pf_hapmeth_tiles_t *tiles,
+                          pf_hapmeth_stats_t *st, pf_hapmeth_dmr_stats_t *dst, pf_hapmeth_hmm_stats_t *hst,
+                          pf_hapmeth_perm_stats_t *pst, pf_hapmeth_assign_stats_t *ast, pf_hapmeth_tagcheck_stats_t *tst,
+                          pf_hapmeth_regions_stats_t *rst, pf_hapmeth_rank_stats_t *kst, pf_hapmeth_rank_exact_stats_t *xst,
+                          pf_hapmeth_tiles_stats_t *lst);
 
 /* Host helper: htslib kt_fisher_exact semantics. Returns the probability of
  * the observed table. */

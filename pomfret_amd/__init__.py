@@ -14,9 +14,10 @@ from .abi import (AlnBatch, Config, KnownVars, LoadConfig, ReadAlnBatch, WindowB
                   HAPTAG_UNPHASED)
 from ._lib import (Context, DeviceBatch, PomfretError, device_count, fisher_exact, lib,
                    methphase_windows, rank_exact_p, rank_p)
+from .pipeline import write_rank_tiles
 
 __all__ = [
     "AlnBatch", "Config", "KnownVars", "LoadConfig", "ReadAlnBatch", "WindowBatch", "WindowResult", "HAPTAG_UNPHASED",
     "Context", "DeviceBatch", "PomfretError", "device_count", "fisher_exact", "lib",
-    "methphase_windows", "rank_exact_p", "rank_p",
+    "methphase_windows", "rank_exact_p", "rank_p", "write_rank_tiles",
 ]

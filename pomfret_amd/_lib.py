@@ -110,6 +110,8 @@ def lib():
         L.pf_batch_ranktest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                         C.POINTER(C.POINTER(PfRank))]
         L.pf_rank_free.argtypes = [C.POINTER(PfRank)]
+        L.pf_batch_rankranges.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.POINTER(C.POINTER(PfRank))]
         L.pf_batch_rankexact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                          C.POINTER(C.POINTER(PfRankExact))]
         L.pf_rank_exact_free.argtypes = [C.POINTER(PfRankExact)]
@@ -774,6 +776,42 @@ class DeviceBatch:
         p = C.POINTER(PfRank)()
         _check(lib().pf_batch_ranktest(self.ctx.handle, self.handle, hp_ptr, n_hp, int(min_calls), C.byref(p)),
                "pf_batch_ranktest")
+        try:
+            r = p.contents
+            W = int(r.n_windows)
+
+            def arr(ptr, n, dt):
+                return np.ctypeslib.as_array(ptr, (n,)).copy() if W else np.zeros(0, dt)
+            return dict(n_reads=arr(r.n_reads, 2 * W, np.uint32).reshape(W, 2),
+                        n_short=arr(r.n_short, 2 * W, np.uint32).reshape(W, 2),
+                        cls=arr(r.cls, 6 * W, np.uint32).reshape(W, 2, 3), sum=arr(r.sum, 4 * W, np.uint64).reshape(W, 4),
+                        u2=arr(r.u2, W, np.uint64), ties=arr(r.ties, W, np.uint64), status=arr(r.status, W, np.uint32),
+                        min_calls=int(r.min_calls), ms=float(r.ms_kernels))
+        finally:
+            lib().pf_rank_free(p)
+
+    def rankranges(self, off, starts, ends, min_calls: int = 3, read_hp=None) -> dict:
+        """ranktest over position ranges inside the windows
+        (pf_batch_rankranges): range i of window w, off[w] <= i < off[w + 1],
+        is tested over window w's reads as a window [starts[i], ends[i]) would
+        be.  off is [W + 1], starting at 0 and non-decreasing; the ranges of a
+        window may overlap, be empty or be missing.  Returns ranktest's dict
+        with one entry per range, in range order."""
+        hp_ptr, n_hp = None, 0
+        if read_hp is not None:
+            hp = np.zeros(np.size(read_hp) + 1, np.uint8)
+            hp[:-1] = np.asarray(read_hp, np.uint8).ravel()
+            hp_ptr, n_hp = hp.ctypes.data, hp.size - 1
+        if not 0 <= int(min_calls) <= 0xFFFFFFFF:
+            raise PomfretError("pf_batch_rankranges: min_calls is 32-bit unsigned")
+        o = np.ascontiguousarray(off, np.uint64).ravel()
+        s, e = np.ascontiguousarray(starts, np.uint32).ravel(), np.ascontiguousarray(ends, np.uint32).ravel()
+        if o.size == 0 or s.size != e.size or int(o[-1]) != s.size:
+            raise PomfretError("pf_batch_rankranges: off is [n_windows + 1] and off[-1] the number of ranges")
+        s, e = np.concatenate([s, np.zeros(1, np.uint32)]), np.concatenate([e, np.zeros(1, np.uint32)])   # never empty
+        p = C.POINTER(PfRank)()
+        _check(lib().pf_batch_rankranges(self.ctx.handle, self.handle, hp_ptr, n_hp, int(min_calls), o.ctypes.data,
+                                         s.ctypes.data, e.ctypes.data, C.byref(p)), "pf_batch_rankranges")
         try:
             r = p.contents
             W = int(r.n_windows)

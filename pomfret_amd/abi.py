@@ -554,6 +554,22 @@ class PfHapmethRankExactStats(C.Structure):
     _fields_ = [("n_exact", C.c_uint64), ("n_over", C.c_uint64), ("ms_kernels", C.c_double)]
 
 
+class PfRankTileRec(C.Structure):
+    """pf_rank_tile_rec_t: a tile's counts and split flag beside a PfRankRec (pf_write_rank_tiles)."""
+    _fields_ = [("sum", C.c_uint64 * 4), ("split", C.c_uint32)]
+
+
+class PfHapmethTiles(C.Structure):
+    """pf_hapmeth_tiles_t (pf_hapmeth_run_tiles)."""
+    _fields_ = [("tile", C.c_uint32), ("min_calls", C.c_uint32), ("blocks_path", C.c_char_p)]
+
+
+class PfHapmethTilesStats(C.Structure):
+    """pf_hapmeth_tiles_stats_t."""
+    _fields_ = [("n_tiles", C.c_uint64), ("n_written", C.c_uint64), ("n_tested", C.c_uint64), ("n_split", C.c_uint64),
+                ("ms_kernels", C.c_double)]
+
+
 class PfAssignCfg(C.Structure):
     """pf_assign_cfg_t."""
     _fields_ = [("min_cov", C.c_uint32), ("min_calls", C.c_uint32), ("min_llr_q16", C.c_int64)]

@@ -1688,6 +1688,23 @@ extern "C" int pf_batch_calls_view(pf_ctx_t *ctx, pf_dbatch_t *b, pf_dev_batch *
     return PF_OK;
 }
 
+// ---- the same view without the load stage, for a consumer that follows
+// another one on the same batch with nothing in between (pf_rank.hip's
+// pf_batch_rankranges_loaded after the driver's pileup): the reads and calls
+// are taken as they stand.  A record-level batch that no load stage has sized
+// yet is refused.  Not part of the public header.
+extern "C" int pf_batch_calls_loaded(pf_ctx_t *ctx, pf_dbatch_t *b, pf_dev_batch *view) {
+    if (!ctx || !b || !view || b->ctx != ctx) return PF_ERR_ARG;
+    if (b->n_launch != b->n_finish) return PF_ERR_ARG;       // a run is in flight
+    if (b->has_aln && !b->have_map) return PF_ERR_ARG;       // run_debug has not run
+    HIPCHK(hipSetDevice(ctx->device));
+    *view = b->d;
+    view->W = b->W;
+    view->R = b->R;
+    view->N = b->N;
+    return PF_OK;
+}
+
 extern "C" int pf_methphase_run(pf_ctx_t *ctx, pf_dbatch_t *b, pf_window_out_t *out) {
     int rc = pf_methphase_launch(ctx, b);
     if (rc) return rc;

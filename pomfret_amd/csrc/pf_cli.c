@@ -13,7 +13,8 @@
  *                         [--dmr-hmm [--dmr-hmm-site-cost BITS] [--dmr-hmm-switch BITS]]
  *                         [--regions regions.bed  (instead of --dmr: the regions are given)]
  *                         [--dmr-rank [--dmr-rank-min-calls N] [--dmr-rank-exact [--dmr-rank-exact-max N]]]
- *                         [--assign] [--tag-check] [--assign-min-llr BITS] [--assign-min-calls N]] tagged.bam
+ *                         [--assign] [--tag-check] [--assign-min-llr BITS] [--assign-min-calls N]]
+ *                         [--tile T [--tile-min-calls N]  (with or without --dmr; --dmr-blocks applies)] tagged.bam
  *
  * Options and defaults follow the reference's cliopt_t (cli.c:47-75) and
  * cliopt_haptag_t (cli.c:332-343); the -c arithmetic (cov/10, cov/4), the
@@ -34,7 +35,10 @@
  * Added subcommand: hapmeth writes {prefix}.hapmeth.bed, the methylation of
  * every CpG per haplotype of a haplotagged BAM (the HP tags of methphase
  * --write-bam, varhaptag or any other haplotagger) with the allele-specific
- * methylation p-value (pf_hapmeth_main; no reference counterpart).
+ * methylation p-value (pf_hapmeth_main; no reference counterpart).  hapmeth
+ * --tile T is the genome-wide scan: {prefix}.hapmeth.tiles.tsv, every T-base
+ * tile with a read under the read-level rank-sum test, with q-values over the
+ * run (pf_hapmeth_run_tiles).
  */
 #include <getopt.h>
 #include <math.h>
@@ -100,7 +104,7 @@ enum { O_LO = 301, O_HI, O_GTF = 304, O_VCF = 306, O_MAPQ, O_TSV, O_WBAM, O_OTSV
        O_CSIZE, O_CSTRIDE, O_HELP = 400, O_DBG, O_GPUS = 500, O_JOBW, O_HFETCH, O_MBED, O_MVAR, O_REF,
        O_DMR = 600, O_DMR_COV, O_DMR_DELTA, O_DMR_GAP, O_DMR_SITES, O_DMR_MAXP, O_DMR_BLOCKS, O_DMR_PERM, O_DMR_SEED,
        O_ASSIGN, O_ASSIGN_LLR, O_ASSIGN_CALLS, O_TAGCHECK, O_DMR_HMM, O_DMR_HMM_SITE, O_DMR_HMM_SWITCH, O_REGIONS,
-       O_DMR_RANK, O_DMR_RANK_CALLS, O_DMR_RANK_EXACT, O_DMR_RANK_EXACT_MAX };
+       O_DMR_RANK, O_DMR_RANK_CALLS, O_DMR_RANK_EXACT, O_DMR_RANK_EXACT_MAX, O_TILE, O_TILE_CALLS };
 
 static const struct option longopts[] = {
     {"lo", required_argument, 0, O_LO},          {"hi", required_argument, 0, O_HI},
@@ -128,6 +132,7 @@ static const struct option longopts[] = {
     {"dmr-rank", no_argument, 0, O_DMR_RANK},    {"dmr-rank-min-calls", required_argument, 0, O_DMR_RANK_CALLS},
     {"dmr-rank-exact", no_argument, 0, O_DMR_RANK_EXACT},
     {"dmr-rank-exact-max", required_argument, 0, O_DMR_RANK_EXACT_MAX},
+    {"tile", required_argument, 0, O_TILE},      {"tile-min-calls", required_argument, 0, O_TILE_CALLS},
     {0, 0, 0, 0}};
 
 typedef struct {
@@ -351,6 +356,17 @@ static void help_hapmeth(void) {
                     "               reads than --dmr-rank-exact-max.  The first 17 columns do not change.\n");
     fprintf(stderr, "  --dmr-rank-exact-max N [opt] Needs --dmr-rank-exact.  The most counted reads of a region that is counted\n"
                     "               exactly, 2 .. 64 (the counts of 68 reads pass 64 bits). [64]\n");
+    fprintf(stderr, "  --tile T [opt] The genome-wide scan: also write {out_prefix}.hapmeth.tiles.tsv, every tile of T bases of\n"
+                    "               each contig (or of -r's range, counted from its start) that holds a tagged read's call,\n"
+                    "               under --dmr-rank's read-level rank-sum test, in the first pass: no region file and no\n"
+                    "               second fetch.  The columns are --dmr-rank's 17, then h1_meth, h1_unmeth, h2_meth, h2_unmeth\n"
+                    "               (the counted reads' calls), delta and block (split: a --dmr-blocks phase block ends inside;\n"
+                    "               such a tile is counted, not tested).  rank_q is Benjamini-Hochberg over the run's tested\n"
+                    "               tiles: the tiles are fixed in advance, so the correction holds.  T is 100 .. --chunk-size,\n"
+                    "               and --chunk-size must be a multiple of T.  Needs no --dmr and goes with every other\n"
+                    "               option; the records stay in memory until the end, about 120 bytes a tile with a read\n"
+                    "               (a human genome at T = 1000: about 3 million).\n");
+    fprintf(stderr, "  --tile-min-calls N [opt] Needs --tile.  Calls inside the tile a read needs to count, 1 .. 65535. [3]\n");
     fprintf(stderr, "  --dmr-hmm [opt] Needs --dmr.  Find the regions with a three-state hidden Markov model (none, h1>h2,\n"
                     "               h1<h2) over each contig's CpGs instead of the per-CpG threshold: every CpG adds its\n"
                     "               evidence for one direction (log2 likelihood ratio of two methylation levels against\n"
@@ -412,7 +428,8 @@ static int hapmeth(int argc, char **argv) {
     int o, csize = 100000, jobw = 0, dmr = 0, dmr_opt = 0, assign = 0, assign_opt = 0, tagcheck = 0, hmm = 0, hmm_opt = 0;
     int gap_opt = 0, rank = 0, rank_opt = 0, exact = 0, exact_opt = 0;
     long xmax = 64;
-    long rcalls = 3;
+    long rcalls = 3, tile = 0, tcalls = 3;
+    int tile_opt = 0, blocks_opt = 0;
     pf_hapmeth_regions_t rg;
     rg.bed_path = NULL;
     double hsite = 2.0, hswitch = 8.0;
@@ -442,7 +459,9 @@ static int hapmeth(int argc, char **argv) {
         case O_DMR_GAP: dmr_opt = gap_opt = 1; dgap = strtol(optarg, &end, 10); if (*end || !*optarg) dgap = -1; break;
         case O_DMR_SITES: dmr_opt = 1; dsites = strtol(optarg, &end, 10); if (*end || !*optarg) dsites = -1; break;
         case O_DMR_MAXP: dmr_opt = 1; dm.max_p = strtod(optarg, &end); if (*end || !*optarg) dm.max_p = -1.0; break;
-        case O_DMR_BLOCKS: dmr_opt = 1; dm.blocks_path = optarg; break;
+        case O_DMR_BLOCKS: blocks_opt = 1; dm.blocks_path = optarg; break;
+        case O_TILE: tile = strtol(optarg, &end, 10); if (*end || !*optarg || tile < 1) tile = -1; break;
+        case O_TILE_CALLS: tile_opt = 1; tcalls = strtol(optarg, &end, 10); if (*end || !*optarg) tcalls = -1; break;
         case O_DMR_PERM: dmr_opt = 1; dperm = strtol(optarg, &end, 10); if (*end || !*optarg) dperm = -1; break;
         case O_DMR_SEED: dmr_opt = 1; dseed = strtol(optarg, &end, 10); if (*end || !*optarg) dseed = -1; break;
         case O_ASSIGN: assign = 1; break;
@@ -476,7 +495,15 @@ static int hapmeth(int argc, char **argv) {
         return 1;
     }
     const int have = dmr || rg.bed_path != NULL;       /* a source of regions */
+    if (blocks_opt && !tile) dmr_opt = 1;              /* --dmr-blocks also goes with --tile alone */
     if (dmr_opt && !have) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --dmr-* options need --dmr or --regions\n"); return 1; }
+    if (tile_opt && !tile) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] --tile-min-calls needs --tile\n"); return 1; }
+    if (tile && (tile < 100 || tile > csize || csize % tile)) {
+        fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --tile: 100 .. --chunk-size (%d), and --chunk-size must be a multiple "
+                "of it\n", csize);
+        return 1;
+    }
+    if (tcalls < 1 || tcalls > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --tile-min-calls (1 .. 65535)\n"); return 1; }
     if (dcov < 1 || dcov > 65535) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-min-cov (1 .. 65535)\n"); return 1; }
     if (ddelta < 1 || ddelta > 100) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-delta (1 .. 100)\n"); return 1; }
     if (dgap < 1 || dgap > 0x7FFFFFFFl) { fprintf(stderr, "[E::sancheck_cliopt_hapmeth] bad --dmr-gap\n"); return 1; }
@@ -531,10 +558,13 @@ static int hapmeth(int argc, char **argv) {
     pf_hapmeth_rank_exact_t xm;
     xm.max_reads = (uint32_t)xmax;
     pf_hapmeth_rank_exact_stats_t xst;
-    const int rc = pf_hapmeth_run_rank_exact(&op, have ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
-                                       assign || tagcheck ? &am : NULL, tagcheck ? &tm : NULL, rg.bed_path ? &rg : NULL,
-                                       rank ? &km : NULL, exact ? &xm : NULL, &st, &dst, &hst, &pst, &ast, &tst, &rst, &kst,
-                                       &xst);
+    pf_hapmeth_tiles_t lm;
+    lm.tile = (uint32_t)tile; lm.min_calls = (uint32_t)tcalls; lm.blocks_path = dm.blocks_path;
+    pf_hapmeth_tiles_stats_t lst;
+    const int rc = pf_hapmeth_run_tiles(&op, have ? &dm : NULL, hmm ? &hm : NULL, pm.n_perm ? &pm : NULL,
+                                        assign || tagcheck ? &am : NULL, tagcheck ? &tm : NULL, rg.bed_path ? &rg : NULL,
+                                        rank ? &km : NULL, exact ? &xm : NULL, tile ? &lm : NULL, &st, &dst, &hst, &pst, &ast,
+                                        &tst, &rst, &kst, &xst, &lst);
     if (rc) {
         fprintf(stderr, "[E::main] hapmeth failed: %s (%d)\n", pf_strerror(rc), rc);
         return 1;
@@ -554,6 +584,9 @@ static int hapmeth(int argc, char **argv) {
     if (exact)
         fprintf(stderr, "[M::main] %llu of them with an exact p-value, %llu with more than %u counted reads\n",
                 (unsigned long long)xst.n_exact, (unsigned long long)xst.n_over, xm.max_reads);
+    if (tile)
+        fprintf(stderr, "[M::main] %llu tiles written to %s.hapmeth.tiles.tsv, %llu of them with a rank-sum p-value\n",
+                (unsigned long long)lst.n_written, op.out_prefix, (unsigned long long)lst.n_tested);
     if (assign)
         fprintf(stderr, "[M::main] %llu scored reads written to %s.hapmeth.assign.tsv, %llu of them with a tag\n",
                 (unsigned long long)ast.n_lines, op.out_prefix, (unsigned long long)(ast.n_h1 + ast.n_h2));

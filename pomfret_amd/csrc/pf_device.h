@@ -54,7 +54,8 @@
 #define PF_PERM_THREADS 256         /* the permutation test's workgroup (PF_PERM_THREADS=<64|256|1024> overrides it) */
 #define PF_PERM_THREADS_MAX 1024
 #define PF_PERM_READS 4096          /* participating reads per window held in LDS (PF_PERM_MAX_READS): 8 B each */
-#define PF_RANK_THREADS 256         /* the rank test's workgroup (PF_RANK_THREADS=<64|256|1024> overrides it) */
+#define PF_RANK_THREADS 256         /* the rank test's workgroup, pf_rank_ranges' too (PF_RANK_THREADS=<64|256|1024>
+                                      overrides it; for the ranges measured in profiles/rank_ranges/README.md) */
 #define PF_RANK_THREADS_MAX 1024
 #define PF_RANK_READS 4096          /* counted reads per window held in LDS (PF_RANK_MAX_READS): 8 B each, 32 KB */
 #define PF_RANK_NARROW_MAX 65535u   /* a window whose largest n_i is at most this compares 32-bit products */

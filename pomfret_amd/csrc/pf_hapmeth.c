@@ -55,7 +55,12 @@
  *   pf_rank_exact_p, pf_write_rank_exact, pf_hapmeth_run_rank_exact: with
  *                     --dmr-rank-exact pf_batch_rankexact follows the rank test
  *                     on the same batch and the rank file gains exact_p, best_p
- *                     and best_q.
+ *                     and best_q;
+ *   pf_write_rank_tiles, pf_hapmeth_run_tiles: with --tile the first pass also
+ *                     tests every fixed-width tile of its windows: after a
+ *                     job's pileup one pf_batch_rankranges call on the same
+ *                     batch, one record per tile with a read, and
+ *                     {prefix}.hapmeth.tiles.tsv at the run's end.
  */
 #include <math.h>
 #include <stdint.h>
@@ -499,9 +504,11 @@ int pf_rank_exact_p(uint64_t count, uint64_t total, double *p) {
     return PF_OK;
 }
 
-/* the rank file; with xrec the three columns of the exact test after pf_write_rank's line */
-static int rank_file(const char *path, const pf_rank_rec_t *rec, const pf_rank_exact_rec_t *xrec, uint64_t n, int bh,
-                     uint64_t *n_tested, uint64_t *n_exact) {
+/* the rank file; with xrec the three columns of the exact test after
+ * pf_write_rank's line, with trec the six columns of a tile (a split tile is
+ * not tested) */
+static int rank_file(const char *path, const pf_rank_rec_t *rec, const pf_rank_exact_rec_t *xrec,
+                     const pf_rank_tile_rec_t *trec, uint64_t n, int bh, uint64_t *n_tested, uint64_t *n_exact) {
     if (n_tested) *n_tested = 0;
     if (n_exact) *n_exact = 0;
     if (!path || (n && !rec)) return PF_ERR_ARG;
@@ -518,7 +525,7 @@ static int rank_file(const char *path, const pf_rank_rec_t *rec, const pf_rank_e
         int rc = pv && q && tested && (!x || (bp && bq && best)) ? PF_OK : PF_ERR_NOMEM;
         for (uint64_t i = 0; i < n && !rc; i++) {
             pv[i] = 1.0;
-            tested[i] = rec[i].status == 0;
+            tested[i] = rec[i].status == 0 && !(trec && trec[i].split);
             if (tested[i]) rc = pf_rank_p(rec[i].u2, rec[i].reads[0], rec[i].reads[1], rec[i].ties, NULL, NULL, pv + i);
             if (x && !rc) {
                 bp[i] = pv[i];
@@ -536,7 +543,8 @@ static int rank_file(const char *path, const pf_rank_rec_t *rec, const pf_rank_e
     FILE *fp = fopen(path, "w");
     if (!fp) { free(pv); free(q); free(tested); free(bp); free(bq); free(best); return -1; }
     fprintf(fp, "#chrom\tstart\tend\treads_h1\treads_h2\tshort_h1\tshort_h2\tallmeth_h1\tallunmeth_h1\tmixed_h1\tallmeth_h2"
-            "\tallunmeth_h2\tmixed_h2\tauc\tz\trank_p\trank_q%s\n", xrec ? "\texact_p\tbest_p\tbest_q" : "");
+            "\tallunmeth_h2\tmixed_h2\tauc\tz\trank_p\trank_q%s%s\n", xrec ? "\texact_p\tbest_p\tbest_q" : "",
+            trec ? "\th1_meth\th1_unmeth\th2_meth\th2_unmeth\tdelta\tblock" : "");
     for (uint64_t i = 0; i < n; i++) {
         const pf_rank_rec_t *r = rec + i;
         fprintf(fp, "%s\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u", r->chrom ? r->chrom : ".", r->start, r->end,
@@ -561,6 +569,15 @@ static int rank_file(const char *path, const pf_rank_rec_t *rec, const pf_rank_e
                 if (bh) fprintf(fp, "%.6g", bq[i]); else fprintf(fp, ".");
             }
         }
+        if (trec) {
+            const uint64_t *c = trec[i].sum;
+            fprintf(fp, "\t%llu\t%llu\t%llu\t%llu\t", (unsigned long long)c[0], (unsigned long long)c[1],
+                    (unsigned long long)c[2], (unsigned long long)c[3]);
+            if (c[0] + c[1] && c[2] + c[3])
+                fprintf(fp, "%.4f", (double)c[0] / (double)(c[0] + c[1]) - (double)c[2] / (double)(c[2] + c[3]));
+            else fputc('.', fp);
+            fprintf(fp, "\t%s", trec[i].split ? "split" : "ok");
+        }
         fputc('\n', fp);
     }
     free(pv);
@@ -575,7 +592,15 @@ static int rank_file(const char *path, const pf_rank_rec_t *rec, const pf_rank_e
 }
 
 int pf_write_rank(const char *path, const pf_rank_rec_t *rec, uint64_t n, int bh, uint64_t *n_tested) {
-    return rank_file(path, rec, NULL, n, bh, n_tested, NULL);
+    return rank_file(path, rec, NULL, NULL, n, bh, n_tested, NULL);
+}
+
+int pf_write_rank_tiles(const char *path, const pf_rank_rec_t *rec, const pf_rank_tile_rec_t *trec, uint64_t n,
+                        uint64_t *n_tested) {
+    if (n_tested) *n_tested = 0;
+    if (n && !trec) return PF_ERR_ARG;
+    static const pf_rank_tile_rec_t none = {{0, 0, 0, 0}, 0};
+    return rank_file(path, rec, NULL, trec ? trec : &none, n, 1, n_tested, NULL);
 }
 
 int pf_write_rank_exact(const char *path, const pf_rank_rec_t *rec, const pf_rank_exact_rec_t *xrec, uint64_t n, int bh,
@@ -584,7 +609,7 @@ int pf_write_rank_exact(const char *path, const pf_rank_rec_t *rec, const pf_ran
     if (n_exact) *n_exact = 0;
     if (n && !xrec) return PF_ERR_ARG;
     static const pf_rank_exact_rec_t none = {0, 0, 1};
-    return rank_file(path, rec, xrec ? xrec : &none, n, bh, n_tested, n_exact);
+    return rank_file(path, rec, xrec ? xrec : &none, NULL, n, bh, n_tested, n_exact);
 }
 
 /* "chrom" or "chrom:beg-end" / "chrom:beg" (1-based inclusive, commas allowed)
@@ -676,7 +701,18 @@ typedef struct {
     pf_rank_exact_rec_t *xrec; /* parallel to krec */
     size_t mx;
     pf_hapmeth_rank_exact_stats_t xst;
+    /* --tile */
+    const pf_hapmeth_tiles_t *tiles;
+    char *lpath;
+    pf_rank_rec_t *lrec;       /* the run's tiles with a participating read, in genome order */
+    pf_rank_tile_rec_t *ltrec; /* parallel to lrec */
+    size_t nl, ml;
+    pf_hapmeth_tiles_stats_t lst;
 } hm_t;
+
+/* pf_rank.hip: pf_batch_rankranges on a batch whose load stage has just run (not in the public header) */
+int pf_batch_rankranges_loaded(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t min_calls,
+                               const uint64_t *rng_off, const uint32_t *rng_start, const uint32_t *rng_end, pf_rank_t **out);
 
 /* the fetch of one job, the same in both passes: the records of the windows
  * ws/we[0, n) of chrom as a record-level batch, no read-back margin */
@@ -819,6 +855,65 @@ static int hm_regions_job(hm_t *H, const pf_pileup_t *pile, uint32_t n, uint32_t
     return PF_OK;
 }
 
+/* --tile: the tiles of the job's windows -- window [a, b) holds [a + j*T, min(a
+ * + (j+1)*T, b)) -- as the ranges of one pf_batch_rankranges call on the batch
+ * the pileup has just loaded; a tile with a participating read becomes a
+ * record */
+static int hm_tiles_job(hm_t *H, const char *chrom, pf_dbatch_t *db, uint32_t n, const uint32_t *ws, const uint32_t *we) {
+    const uint32_t T = H->tiles->tile;
+    uint64_t *off = (uint64_t *)malloc(8ull * ((size_t)n + 1));
+    if (!off) return PF_ERR_NOMEM;
+    off[0] = 0;
+    for (uint32_t w = 0; w < n; w++) off[w + 1] = off[w] + ((uint64_t)(we[w] - ws[w]) + T - 1) / T;
+    const uint64_t nr = off[n];
+    uint32_t *rs = (uint32_t *)malloc(4ull * (nr ? nr : 1)), *re = (uint32_t *)malloc(4ull * (nr ? nr : 1));
+    pf_rank_t *rk = NULL;
+    int rc = rs && re ? PF_OK : PF_ERR_NOMEM;
+    for (uint32_t w = 0; w < n && !rc; w++)
+        for (uint64_t i = off[w]; i < off[w + 1]; i++) {
+            const uint64_t a = (uint64_t)ws[w] + (i - off[w]) * T, b = a + T;
+            rs[i] = (uint32_t)a;
+            re[i] = b < we[w] ? (uint32_t)b : we[w];
+        }
+    if (!rc) rc = pf_batch_rankranges_loaded(H->ctx, db, NULL, 0, H->tiles->min_calls, off, rs, re, &rk);
+    if (!rc && rk->n_windows != nr) rc = PF_ERR_INTERNAL;
+    for (uint64_t i = 0; i < nr && !rc; i++) {
+        const uint32_t *c = rk->n_reads + 2 * i, *sh = rk->n_short + 2 * i;
+        if (!(c[0] + sh[0]) && !(c[1] + sh[1])) continue;      /* no participating read */
+        if (H->nl == H->ml) {
+            const size_t nm = H->ml ? H->ml * 2 : 1024;
+            pf_rank_rec_t *p = (pf_rank_rec_t *)realloc(H->lrec, nm * sizeof *p);
+            if (p) H->lrec = p;
+            pf_rank_tile_rec_t *q = p ? (pf_rank_tile_rec_t *)realloc(H->ltrec, nm * sizeof *q) : NULL;
+            if (q) H->ltrec = q;
+            if (!p || !q) { rc = PF_ERR_NOMEM; break; }
+            H->ml = nm;
+        }
+        pf_rank_rec_t *r = H->lrec + H->nl;
+        pf_rank_tile_rec_t *t = H->ltrec + H->nl;
+        H->nl++;
+        memset(r, 0, sizeof *r);
+        memset(t, 0, sizeof *t);
+        r->chrom = chrom; r->start = rs[i]; r->end = re[i];
+        for (int q = 0; q < 2; q++) { r->reads[q] = c[q]; r->n_short[q] = sh[q]; }
+        for (int q = 0; q < 6; q++) r->cls[q] = rk->cls[6 * i + q];
+        r->status = rk->status[i]; r->u2 = rk->u2[i]; r->ties = rk->ties[i];
+        for (int q = 0; q < 4; q++) t->sum[q] = rk->sum[4 * i + q];
+        uint32_t lo = 0, hi = H->n_brk;                      /* breaks <= start */
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (H->brk[mid] <= rs[i]) lo = mid + 1; else hi = mid;
+        }
+        if (lo < H->n_brk && H->brk[lo] < re[i]) { t->split = 1; H->lst.n_split++; }
+    }
+    if (!rc) H->lst.ms_kernels += rk->ms_kernels;
+    pf_rank_free(rk);
+    free(off);
+    free(rs);
+    free(re);
+    return rc;
+}
+
 /* one job: the windows ws/we[0, n) of chrom */
 static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, const uint32_t *we) {
     pf_dbatch_t *db = NULL;
@@ -830,6 +925,7 @@ static int hm_job(hm_t *H, const char *chrom, uint32_t n, const uint32_t *ws, co
         fprintf(stderr, "[E::pf_hapmeth_main] %s:%u-%u: a window exceeds a device limit (65,535 records per window); "
                 "try a smaller --chunk-size\n", chrom, ws[0] + 1, we[n - 1]);
     if (!rc) rc = pf_batch_pileup(H->ctx, db, NULL, 0, &pile);
+    if (!rc && H->tiles) rc = hm_tiles_job(H, chrom, db, n, ws, we);      /* nothing in between: the calls as they stand */
     if (!rc) rc = pf_write_hapmeth(H->path, chrom, pile, 0, n, 0);
     if (!rc) {
         H->st.n_sites += pile->n_sites;
@@ -1143,6 +1239,11 @@ static int hm_span(hm_t *H, int32_t tid, uint32_t s, uint32_t e, uint32_t chunk,
             if (!H->acc) return PF_ERR_NOMEM;
         }
     }
+    if (H->tiles) {
+        if (!H->dmr) rc = hm_breaks(H, chrom);               /* with dmr they are built above: one GTF, one array */
+        if (rc) return rc;
+        H->lst.n_tiles += ((uint64_t)(e - s) + H->tiles->tile - 1) / H->tiles->tile;   /* e >= s */
+    }
     for (uint64_t a = s; a < e && !rc; a += chunk) {
         const uint64_t b = a + chunk < e ? a + chunk : e;
         H->st.n_windows++;
@@ -1224,6 +1325,20 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
                               pf_hapmeth_assign_stats_t *astats, pf_hapmeth_tagcheck_stats_t *tstats,
                               pf_hapmeth_regions_stats_t *rstats, pf_hapmeth_rank_stats_t *kstats,
                               pf_hapmeth_rank_exact_stats_t *xstats) {
+    return pf_hapmeth_run_tiles(o, dmr, hmm, perm, assign, tagcheck, regions, rank, exact, NULL, stats, dstats, hstats, pstats,
+                                astats, tstats, rstats, kstats, xstats, NULL);
+}
+
+int pf_hapmeth_run_tiles(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t *dmr, const pf_hapmeth_hmm_t *hmm,
+                         const pf_hapmeth_perm_t *perm, const pf_hapmeth_assign_t *assign,
+                         const pf_hapmeth_tagcheck_t *tagcheck, const pf_hapmeth_regions_t *regions,
+                         const pf_hapmeth_rank_t *rank, const pf_hapmeth_rank_exact_t *exact, const pf_hapmeth_tiles_t *tiles,
+                         pf_hapmeth_stats_t *stats, pf_hapmeth_dmr_stats_t *dstats, pf_hapmeth_hmm_stats_t *hstats,
+                         pf_hapmeth_perm_stats_t *pstats, pf_hapmeth_assign_stats_t *astats,
+                         pf_hapmeth_tagcheck_stats_t *tstats, pf_hapmeth_regions_stats_t *rstats,
+                         pf_hapmeth_rank_stats_t *kstats, pf_hapmeth_rank_exact_stats_t *xstats,
+                         pf_hapmeth_tiles_stats_t *lstats) {
+    if (lstats) memset(lstats, 0, sizeof *lstats);
     if (xstats) memset(xstats, 0, sizeof *xstats);
     if (kstats) memset(kstats, 0, sizeof *kstats);
     if (rstats) memset(rstats, 0, sizeof *rstats);
@@ -1246,8 +1361,16 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
     if (regions && (!dmr || hmm || !regions->bed_path)) return PF_ERR_ARG;
     if (rank && (!dmr || rank->min_calls < 1u || rank->min_calls > 65535u)) return PF_ERR_ARG;
     if (exact && (!rank || exact->max_reads < 2u || exact->max_reads > PF_RANK_EXACT_MAX_READS)) return PF_ERR_ARG;
+    const uint32_t chunk = o->chunk_size ? o->chunk_size : 100000u;
+    if (tiles && (tiles->min_calls < 1u || tiles->min_calls > 65535u)) return PF_ERR_ARG;
+    if (tiles && (tiles->tile < 100u || tiles->tile > chunk || chunk % tiles->tile)) {
+        fprintf(stderr, "[E::pf_hapmeth_main] --tile %u: a tile is 100 bases to the chunk size, and the chunk size (%u) must "
+                "be a multiple of it, so that a tile lies in one fetch window\n", tiles->tile, chunk);
+        return PF_ERR_ARG;
+    }
     hm_t H;
     memset(&H, 0, sizeof H);
+    H.tiles = tiles;
     H.rank = rank;
     H.exact = exact;
     H.regions = regions;
@@ -1261,7 +1384,6 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
     H.lc = o->load;
     /* the batch's phasing parameters are not used by the pileup: the reference's defaults */
     H.cfg.k = 3; H.cfg.k_span = 5000; H.cfg.cov_for_selection = 6; H.cfg.n_cand = 15; H.cfg.hard_cov = 15;
-    const uint32_t chunk = o->chunk_size ? o->chunk_size : 100000u;
     const uint32_t jw = o->job_windows ? o->job_windows : 1024u;
     H.jw = jw;
     int rc = pf_bam_open(o->bam_path, NULL, &H.bam);
@@ -1303,6 +1425,10 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
         rc = pf_interval_gaps(dmr->blocks_path, PF_INTERVALS_GTF, 0, &H.blocks);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot read the phase blocks of %s\n", dmr->blocks_path);
     }
+    if (!rc && tiles && tiles->blocks_path && !dmr) {
+        rc = pf_interval_gaps(tiles->blocks_path, PF_INTERVALS_GTF, 0, &H.blocks);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot read the phase blocks of %s\n", tiles->blocks_path);
+    }
     if (!rc) {
         rc = pf_ctx_create(o->device, &H.ctx);
         if (rc) fprintf(stderr, "[E::pf_hapmeth_main] no usable GPU (device %d): %s\n", o->device, pf_strerror(rc));
@@ -1316,9 +1442,11 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
         H.trpath = (char *)malloc(l);
         H.rpath = (char *)malloc(l);
         H.kpath = (char *)malloc(l);
+        H.lpath = (char *)malloc(l);
         ws = (uint32_t *)malloc(4ull * jw);
         we = (uint32_t *)malloc(4ull * jw);
-        if (!H.path || !H.dpath || !H.apath || !H.tpath || !H.trpath || !H.rpath || !H.kpath || !ws || !we) rc = PF_ERR_NOMEM;
+        if (!H.path || !H.dpath || !H.apath || !H.tpath || !H.trpath || !H.rpath || !H.kpath || !H.lpath || !ws || !we)
+            rc = PF_ERR_NOMEM;
         else {
             snprintf(H.path, l, "%s.hapmeth.bed", o->out_prefix);
             snprintf(H.dpath, l, "%s.hapmeth.dmr.bed", o->out_prefix);
@@ -1327,6 +1455,7 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
             snprintf(H.trpath, l, "%s.hapmeth.tagcheck.regions.tsv", o->out_prefix);
             snprintf(H.rpath, l, "%s.hapmeth.regions.bed", o->out_prefix);
             snprintf(H.kpath, l, "%s.hapmeth.rank.tsv", o->out_prefix);
+            snprintf(H.lpath, l, "%s.hapmeth.tiles.tsv", o->out_prefix);
         }
     }
     if (!rc) {
@@ -1385,6 +1514,16 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
         H.kst.n_tested = tested;
         H.kst.n_untested = H.nk - tested;
     }
+    int lmade = 0;
+    if (!rc && tiles) {                                /* at the end: rank_q needs every tile */
+        uint64_t tested = 0;
+        lmade = 1;
+        rc = pf_write_rank_tiles(H.lpath, H.lrec, H.ltrec, H.nl, &tested);
+        if (rc) fprintf(stderr, "[E::pf_hapmeth_main] cannot write %s\n", H.lpath);
+        H.lst.n_written = H.nl;
+        H.lst.n_tested = tested;
+    }
+    if (rc && lmade) (void)unlink(H.lpath);
     if (rc && kmade) (void)unlink(H.kpath);
     if (rc && rmade) (void)unlink(H.rpath);
     if (rc && made) (void)unlink(H.path);              /* no truncated output behind a failure */
@@ -1421,6 +1560,11 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
         fprintf(stderr, "[M::pf_hapmeth_main] exact rank test: %llu regions with an exact p-value (at most %u reads), %llu over "
                 "the limit, exact kernels %.3f ms\n", (unsigned long long)H.xst.n_exact, exact->max_reads,
                 (unsigned long long)H.xst.n_over, H.xst.ms_kernels);
+    if (!rc && o->verbose && tiles)
+        fprintf(stderr, "[M::pf_hapmeth_main] tiles of %u bases: %llu planned, %llu with a read written, %llu tested (at least "
+                "%u calls a read), %llu split by a phase block, range kernels %.3f ms\n", tiles->tile,
+                (unsigned long long)H.lst.n_tiles, (unsigned long long)H.lst.n_written, (unsigned long long)H.lst.n_tested,
+                tiles->min_calls, (unsigned long long)H.lst.n_split, H.lst.ms_kernels);
     if (!rc && o->verbose && assign)
         fprintf(stderr, "[M::pf_hapmeth_main] %llu candidate reads scored, %llu assigned (%llu h1 / %llu h2), "
                 "%llu records fetched for it, assign kernels %.3f ms\n", (unsigned long long)H.ast.n_lines,
@@ -1446,6 +1590,7 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
     if (rstats) *rstats = H.rst;
     if (kstats) *kstats = H.kst;
     if (xstats) *xstats = H.xst;
+    if (lstats) *lstats = H.lst;
     free(ws);
     free(we);
     free(H.path);
@@ -1460,6 +1605,9 @@ int pf_hapmeth_run_rank_exact(const pf_hapmeth_opts_t *o, const pf_hapmeth_dmr_t
     free(H.kpath);
     free(H.krec);
     free(H.xrec);
+    free(H.lpath);
+    free(H.lrec);
+    free(H.ltrec);
     free(H.rec);
     free(H.ks);
     free(H.ke);

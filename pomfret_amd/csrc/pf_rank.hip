@@ -23,6 +23,18 @@
 // below 2^32.  Integer sums only: neither the workgroup size, the product
 // width nor the order of the atomics reaches the result.
 //
+// pf_rank_ranges (pf_batch_rankranges) is the same test over position ranges
+// inside the windows, one workgroup per range: the genome-wide tiles of hapmeth
+// --tile, tested in the first pass from the calls the pileup has just read.
+// The two phases are one body, rank_one, for both kernels.  The counted reads
+// lie in dynamic LDS sized to the batch's largest window: a tile counts tens of
+// reads, and a 32 KB request keeps workgroups off a CU (2.9 x at 12,800
+// ranges).  A pre-test of each read's span (first and last call position,
+// stored once a call) against the range, to spare the slice's two dependent
+// loads for the reads that lie elsewhere, was built and measured: 2 to 4 %,
+// less than the extra kernel costs, so it is not here
+// (profiles/rank_ranges/README.md).
+//
 // pf_rank_exact (pf_batch_rankexact) counts the exact null distribution of the
 // same statistic for windows of at most 64 counted reads.  A workgroup takes
 // the windows blockIdx.x, blockIdx.x + gridDim.x, ... and per window:
@@ -61,6 +73,7 @@ struct pf_dbatch;
 extern "C" int pf_ctx_device(const pf_ctx *c);
 extern "C" hipStream_t pf_ctx_stream(const pf_ctx *c);
 extern "C" int pf_batch_calls_view(pf_ctx *ctx, pf_dbatch *b, pf_dev_batch *view);       // pf_api.hip
+extern "C" int pf_batch_calls_loaded(pf_ctx *ctx, pf_dbatch *b, pf_dev_batch *view);
 
 namespace {
 
@@ -138,15 +151,17 @@ __device__ __forceinline__ void rank_rows(const uint2 *s_r, uint32_t n, uint32_t
     }
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(PF_RANK_THREADS_MAX) void pf_rank_test(rank_args a) {
-    __shared__ uint2 s_r[PF_RANK_READS];             // per counted read: m, n | tag << 31
+// One workgroup's test of the position range [*p_ws, *p_we) over the reads
+// [p_r0[0], p_r0[1]): pf_rank_test's whole body, shared with pf_rank_ranges.
+// s_r holds cap counted reads, cap at least min(PF_RANK_READS, r1 - r0).  Every
+// thread of the workgroup calls it.
+__device__ __forceinline__ void rank_one(const pf_calls_view &v, uint32_t min_calls, uint32_t force_wide, uint2 *s_r,
+                                         uint32_t cap, const uint32_t *p_ws, const uint32_t *p_we, const uint32_t *p_r0,
+                                         rank_out *out) {
     __shared__ unsigned long long s_sum[4], s_N, s_acc[3];
     __shared__ uint32_t s_nr[2], s_short[2], s_cls[6], s_max, wsum[PF_RANK_THREADS_MAX / PF_WAVE];
-    const uint32_t w = blockIdx.x, tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
     const uint32_t nt = blockDim.x, nw = nt >> 6;
-    if (w >= a.W) return;
     if (tid < 4u) s_sum[tid] = 0ull;
     if (tid < 3u) s_acc[tid] = 0ull;
     if (tid < 2u) { s_nr[tid] = 0u; s_short[tid] = 0u; }
@@ -155,22 +170,22 @@ __global__ __launch_bounds__(PF_RANK_THREADS_MAX) void pf_rank_test(rank_args a)
     __syncthreads();
 
     // ---- phase 1: the counted reads in read order
-    const uint32_t ws = a.v.win_start[w], we = a.v.win_end[w];
-    const uint32_t r0 = a.v.win_read_off[w], r1 = a.v.win_read_off[w + 1];
+    const uint32_t ws = *p_ws, we = *p_we;
+    const uint32_t r0 = p_r0[0], r1 = p_r0[1];
     uint32_t n = 0;
     for (uint32_t g = r0; g < r1; g += nt) {          // the same rounds in every thread: barriers inside
         uint32_t hp, my_m, my_u, tot;
         bool hit;
-        window_read_counts(a.v, g, r1, ws, we, tid, hp, hit, my_m, my_u);
+        window_read_counts(v, g, r1, ws, we, tid, hp, hit, my_m, my_u);
         const uint32_t my_n = my_m + my_u;
         const bool part = hit && my_n != 0u;
-        const bool counted = part && my_n >= a.min_calls;
+        const bool counted = part && my_n >= min_calls;
         const uint32_t slot = block_compact(counted, wsum, nw, lane, wave, tot);
         if (part) atomicAdd(&s_N, (unsigned long long)my_n);
         if (part && !counted) atomicAdd(&s_short[hp], 1u);
         if (counted) {
             const uint32_t idx = n + slot;
-            if (idx < PF_RANK_READS) s_r[idx] = make_uint2(my_m, (my_n & 0x7FFFFFFFu) | (hp << 31));
+            if (idx < cap) s_r[idx] = make_uint2(my_m, (my_n & 0x7FFFFFFFu) | (hp << 31));
             atomicAdd(&s_sum[2u * hp], (unsigned long long)my_m);
             atomicAdd(&s_sum[2u * hp + 1u], (unsigned long long)my_u);
             atomicAdd(&s_nr[hp], 1u);
@@ -184,7 +199,7 @@ __global__ __launch_bounds__(PF_RANK_THREADS_MAX) void pf_rank_test(rank_args a)
     const uint32_t n1 = s_nr[0], n2 = s_nr[1];
     const bool over = s_N >= 0x80000000ull;
     const uint32_t status = over ? RANK_ST_LIMIT : n > PF_RANK_READS ? 2u : (n1 == 0u || n2 == 0u) ? 1u : 0u;
-    const bool wide = a.force_wide != 0u || s_max > PF_RANK_NARROW_MAX;
+    const bool wide = force_wide != 0u || s_max > PF_RANK_NARROW_MAX;
 
     // ---- phase 2: all pairs
     if (status == 0u) {
@@ -211,8 +226,45 @@ __global__ __launch_bounds__(PF_RANK_THREADS_MAX) void pf_rank_test(rank_args a)
         for (int k = 0; k < 6; k++) o.cls[k] = s_cls[k];
         o.status = status;
         o.wide = wide ? 1u : 0u;
-        a.out[w] = o;
+        *out = o;
     }
+}
+
+struct rankr_args {
+    uint32_t W, n_rng, min_calls, force_wide, cap, pad;
+    pf_calls_view v;                                 /* read_hp: the batch's tags or the caller's */
+    const uint64_t *rng_off;                         /* [W + 1] */
+    const uint32_t *rng_start, *rng_end;             /* [n_rng] */
+    rank_out *out;                                   /* [n_rng] */
+};
+
+}  // namespace
+
+__global__ __launch_bounds__(PF_RANK_THREADS_MAX) void pf_rank_test(rank_args a) {
+    __shared__ uint2 s_r[PF_RANK_READS];             // per counted read: m, n | tag << 31
+    const uint32_t w = blockIdx.x;
+    if (w >= a.W) return;
+    rank_one(a.v, a.min_calls, a.force_wide, s_r, PF_RANK_READS, a.v.win_start + w, a.v.win_end + w, a.v.win_read_off + w,
+             a.out + w);
+}
+
+// ---- the same test over position ranges inside the windows (pf_batch_rankranges)
+//
+// One workgroup per range.  The range's window is the w with rng_off[w] <= i <
+// rng_off[w + 1], found by binary search (windows without a range are stepped
+// over: the search looks for the first offset above i).  The counted reads lie
+// in dynamic LDS, 8 B times a.cap.
+__global__ __launch_bounds__(PF_RANK_THREADS_MAX) void pf_rank_ranges(rankr_args a) {
+    extern __shared__ uint2 s_dyn[];
+    const uint32_t i = blockIdx.x;
+    if (i >= a.n_rng) return;
+    uint32_t lo = 0, hi = a.W;                        // the first w in [0, W) with rng_off[w + 1] > i
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (a.rng_off[mid + 1] > (uint64_t)i) hi = mid; else lo = mid + 1;
+    }
+    if (lo >= a.W) return;                            // not reached: rng_off[W] == n_rng > i
+    rank_one(a.v, a.min_calls, a.force_wide, s_dyn, a.cap, a.rng_start + i, a.rng_end + i, a.v.win_read_off + lo, a.out + i);
 }
 
 // ---- the exact test
@@ -392,6 +444,53 @@ static int rank_wide() {
     return -1;
 }
 
+// a result of n entries with every array allocated and zeroed; NULL: no memory
+static pf_rank_t *rank_result_new(uint32_t n, uint32_t min_calls) {
+    pf_rank_t *res = (pf_rank_t *)calloc(1, sizeof(pf_rank_t));
+    if (!res) return nullptr;
+    res->n_windows = n;
+    res->min_calls = min_calls;
+    if (n == 0) return res;
+    res->n_reads = (uint32_t *)calloc(2ull * n, 4); res->n_short = (uint32_t *)calloc(2ull * n, 4);
+    res->cls = (uint32_t *)calloc(6ull * n, 4); res->status = (uint32_t *)calloc(n, 4);
+    res->sum = (uint64_t *)calloc(4ull * n, 8); res->u2 = (uint64_t *)calloc(n, 8); res->ties = (uint64_t *)calloc(n, 8);
+    if (!res->n_reads || !res->n_short || !res->cls || !res->status || !res->sum || !res->u2 || !res->ties) {
+        pf_rank_free(res);
+        return nullptr;
+    }
+    return res;
+}
+
+// the kernels' records into the result's arrays; PF_ERR_LIMIT where one holds 2^31 or more calls
+static int rank_result_fill(pf_rank_t *res, const std::vector<rank_out> &h_out, const char *what) {
+    uint32_t *h_nr = const_cast<uint32_t *>(res->n_reads), *h_short = const_cast<uint32_t *>(res->n_short);
+    uint32_t *h_cls = const_cast<uint32_t *>(res->cls), *h_stat = const_cast<uint32_t *>(res->status);
+    uint64_t *h_sum = const_cast<uint64_t *>(res->sum), *h_u2 = const_cast<uint64_t *>(res->u2);
+    uint64_t *h_ties = const_cast<uint64_t *>(res->ties);
+    for (uint32_t w = 0; w < res->n_windows; w++) {
+        const rank_out &o = h_out[w];
+        if (o.status == RANK_ST_LIMIT) {
+            fprintf(stderr, "[E::pomfret_amd] %s holds 2^31 or more calls\n", what);
+            return PF_ERR_LIMIT;
+        }
+        for (int k = 0; k < 4; k++) h_sum[4ull * w + k] = o.sum[k];
+        for (int k = 0; k < 2; k++) { h_nr[2ull * w + k] = o.n_reads[k]; h_short[2ull * w + k] = o.n_short[k]; }
+        for (int k = 0; k < 6; k++) h_cls[6ull * w + k] = o.cls[k];
+        h_u2[w] = o.u2;
+        h_ties[w] = o.ties;
+        h_stat[w] = o.status;
+    }
+    return PF_OK;
+}
+
+// PF_RANKR_LDS_FIXED: unset or "0" 0, "1" 1 (pf_rank_ranges takes pf_rank_test's 32 KB whatever the batch), anything else -1
+static int rankr_lds_fixed() {
+    const char *e = getenv("PF_RANKR_LDS_FIXED");
+    if (!e || !strcmp(e, "0")) return 0;
+    if (!strcmp(e, "1")) return 1;
+    return -1;
+}
+
 extern "C" int pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t min_calls,
                                  pf_rank_t **out) {
     if (!ctx || !db || !out) return PF_ERR_ARG;
@@ -406,18 +505,10 @@ extern "C" int pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *
     const uint32_t W = d.W, R = d.R;
     if (read_hp && n_hp != R) return PF_ERR_ARG;
 
-    pf_rank_t *res = (pf_rank_t *)calloc(1, sizeof(pf_rank_t));
+    pf_rank_t *res = rank_result_new(W, min_calls);
     if (!res) return PF_ERR_NOMEM;
-    res->n_windows = W;
-    res->min_calls = min_calls;
     if (W == 0) { *out = res; return PF_OK; }
     std::unique_ptr<pf_rank_t, void (*)(pf_rank_t *)> own(res, pf_rank_free);      // freed on every return but the last
-    uint32_t *h_nr = (uint32_t *)calloc(2ull * W, 4), *h_short = (uint32_t *)calloc(2ull * W, 4);
-    uint32_t *h_cls = (uint32_t *)calloc(6ull * W, 4), *h_stat = (uint32_t *)calloc(W, 4);
-    uint64_t *h_sum = (uint64_t *)calloc(4ull * W, 8), *h_u2 = (uint64_t *)calloc(W, 8), *h_ties = (uint64_t *)calloc(W, 8);
-    res->n_reads = h_nr; res->n_short = h_short; res->cls = h_cls; res->sum = h_sum; res->u2 = h_u2; res->ties = h_ties;
-    res->status = h_stat;
-    if (!h_nr || !h_short || !h_cls || !h_stat || !h_sum || !h_u2 || !h_ties) return PF_ERR_NOMEM;
     std::vector<rank_out> h_out;
     try { h_out.resize(W); } catch (...) { return PF_ERR_NOMEM; }
     pf_call call(pf_ctx_stream(ctx));
@@ -436,21 +527,115 @@ extern "C" int pf_batch_ranktest(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *
         hipStreamSynchronize(call.st) != hipSuccess)
         return PF_ERR_HIP;
     res->ms_kernels = call.ms(0, 1);
-    for (uint32_t w = 0; w < W; w++) {
-        const rank_out &o = h_out[w];
-        if (o.status == RANK_ST_LIMIT) {
-            fprintf(stderr, "[E::pomfret_amd] ranktest: a window holds 2^31 or more calls\n");
-            return PF_ERR_LIMIT;
-        }
-        for (int k = 0; k < 4; k++) h_sum[4ull * w + k] = o.sum[k];
-        for (int k = 0; k < 2; k++) { h_nr[2ull * w + k] = o.n_reads[k]; h_short[2ull * w + k] = o.n_short[k]; }
-        for (int k = 0; k < 6; k++) h_cls[6ull * w + k] = o.cls[k];
-        h_u2[w] = o.u2;
-        h_ties[w] = o.ties;
-        h_stat[w] = o.status;
-    }
+    const int frc = rank_result_fill(res, h_out, "ranktest: a window");
+    if (frc) return frc;
     *out = own.release();
     return PF_OK;
+}
+
+// pf_batch_rankranges, and with loaded != 0 the entry for a caller that has
+// just run another consumer on the same batch (pf_batch_rankranges_loaded):
+// the calls are taken as they stand.
+static int rank_ranges_run(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t min_calls,
+                           const uint64_t *rng_off, const uint32_t *rng_start, const uint32_t *rng_end, pf_rank_t **out,
+                           int loaded) {
+    if (!ctx || !db || !out) return PF_ERR_ARG;
+    *out = nullptr;
+    if (min_calls < 1u || min_calls > 65535u) return PF_ERR_ARG;
+    const uint32_t nt = pf_env_threads("PF_RANK_THREADS", PF_RANK_THREADS);
+    const int fw = rank_wide(), fl = rankr_lds_fixed();
+    if (!nt || fw < 0 || fl < 0) return PF_ERR_ARG;
+    pf_dev_batch d;
+    const int vrc = loaded ? pf_batch_calls_loaded(ctx, db, &d) : pf_batch_calls_view(ctx, db, &d);
+    if (vrc) return vrc;
+    const uint32_t W = d.W, R = d.R;
+    if (read_hp && n_hp != R) return PF_ERR_ARG;
+    if (W && !rng_off) return PF_ERR_ARG;
+    uint64_t n64 = 0;
+    if (W) {
+        if (rng_off[0] != 0) return PF_ERR_ARG;
+        for (uint32_t w = 0; w < W; w++)
+            if (rng_off[w + 1] < rng_off[w]) return PF_ERR_ARG;
+        n64 = rng_off[W];
+    }
+    if (n64 > 0x7FFFFFFFull || (n64 && (!rng_start || !rng_end))) return PF_ERR_ARG;
+    const uint32_t n = (uint32_t)n64;
+    if (n64 * nt > 0xFFFFFFFFull) {                  // one workgroup per range: a launch holds fewer than 2^32 threads
+        fprintf(stderr, "[E::pomfret_amd] rankranges: %u ranges at %u threads each pass 2^32 threads in one launch\n", n, nt);
+        return PF_ERR_LIMIT;
+    }
+    hipStream_t st = pf_ctx_stream(ctx);
+
+    // every range inside its window; the LDS array after the largest window's reads
+    uint32_t max_reads = 0;
+    if (n) {
+        std::vector<uint32_t> hws, hwe, hro;
+        try { hws.resize(W); hwe.resize(W); hro.resize((size_t)W + 1); } catch (...) { return PF_ERR_NOMEM; }
+        if (hipMemcpyAsync(hws.data(), d.win_start, 4ull * W, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(hwe.data(), d.win_end, 4ull * W, hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(hro.data(), d.win_read_off, 4ull * (W + 1), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipStreamSynchronize(st) != hipSuccess)
+            return PF_ERR_HIP;
+        for (uint32_t w = 0; w < W; w++) {
+            for (uint64_t i = rng_off[w]; i < rng_off[w + 1]; i++)
+                if (rng_start[i] < hws[w] || rng_end[i] < rng_start[i] || rng_end[i] > hwe[w]) return PF_ERR_ARG;
+            if (hro[w + 1] < hro[w] || hro[w + 1] > R) return PF_ERR_INTERNAL;
+            if (rng_off[w + 1] > rng_off[w] && hro[w + 1] - hro[w] > max_reads) max_reads = hro[w + 1] - hro[w];
+        }
+    }
+
+    pf_rank_t *res = rank_result_new(n, min_calls);
+    if (!res) return PF_ERR_NOMEM;
+    if (n == 0) { *out = res; return PF_OK; }
+    std::unique_ptr<pf_rank_t, void (*)(pf_rank_t *)> own(res, pf_rank_free);      // freed on every return but the last
+    std::vector<rank_out> h_out;
+    try { h_out.resize(n); } catch (...) { return PF_ERR_NOMEM; }
+    pf_call call(st);
+    rankr_args a;
+    memset(&a, 0, sizeof a);
+    a.W = W; a.n_rng = n; a.min_calls = min_calls; a.force_wide = (uint32_t)fw;
+    // min(PF_RANK_READS, the reads of the largest window with a range), as a power of two, one wave's reads at least
+    a.cap = 64u;
+    while (a.cap < PF_RANK_READS && a.cap < max_reads) a.cap <<= 1;
+    if (fl) a.cap = PF_RANK_READS;
+    a.v = pf_calls_view_of(d);
+    const int hrc = call.upload_hp(read_hp, R, a.v);
+    if (hrc) return hrc;
+    void *p_off = call.alloc(8ull * ((size_t)W + 1)), *p_s = call.alloc(4ull * n), *p_e = call.alloc(4ull * n);
+    a.out = static_cast<rank_out *>(call.alloc(sizeof(rank_out) * (size_t)n));
+    if (!p_off || !p_s || !p_e || !a.out) return PF_ERR_NOMEM;
+    a.rng_off = static_cast<const uint64_t *>(p_off);
+    a.rng_start = static_cast<const uint32_t *>(p_s);
+    a.rng_end = static_cast<const uint32_t *>(p_e);
+    if (hipMemcpyAsync(p_off, rng_off, 8ull * ((size_t)W + 1), hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(p_s, rng_start, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(p_e, rng_end, 4ull * n, hipMemcpyHostToDevice, st) != hipSuccess || !call.mark(0))
+        return PF_ERR_HIP;
+    hipLaunchKernelGGL(pf_rank_ranges, dim3(n), dim3(nt), sizeof(uint2) * (size_t)a.cap, st, a);
+    if (hipGetLastError() != hipSuccess || !call.mark(1) ||
+        hipMemcpyAsync(h_out.data(), a.out, sizeof(rank_out) * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return PF_ERR_HIP;
+    res->ms_kernels = call.ms(0, 1);
+    const int frc = rank_result_fill(res, h_out, "rankranges: a range");
+    if (frc) return frc;
+    *out = own.release();
+    return PF_OK;
+}
+
+extern "C" int pf_batch_rankranges(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp, uint32_t min_calls,
+                                   const uint64_t *rng_off, const uint32_t *rng_start, const uint32_t *rng_end,
+                                   pf_rank_t **out) {
+    return rank_ranges_run(ctx, db, read_hp, n_hp, min_calls, rng_off, rng_start, rng_end, out, 0);
+}
+
+// ---- the same call on a batch whose load stage the caller has just run
+// (pf_hapmeth.c, right after pf_batch_pileup): a record-level batch's loader is
+// not run a second time.  Not part of the public header.
+extern "C" int pf_batch_rankranges_loaded(pf_ctx_t *ctx, pf_dbatch_t *db, const uint8_t *read_hp, uint32_t n_hp,
+                                          uint32_t min_calls, const uint64_t *rng_off, const uint32_t *rng_start,
+                                          const uint32_t *rng_end, pf_rank_t **out) {
+    return rank_ranges_run(ctx, db, read_hp, n_hp, min_calls, rng_off, rng_start, rng_end, out, 1);
 }
 
 extern "C" void pf_rank_exact_free(pf_rank_exact_t *p) {

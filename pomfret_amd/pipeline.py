@@ -38,7 +38,7 @@ from .abi import (Config, DmrConfig, LoadConfig, PfCfg, PfDmr, PfHapmethDmr, PfH
                   PfHapmethTagcheck, PfHapmethTagcheckStats, PfTagcheck, PfHapmethPerm, PfHapmethPermStats, PfHapmethStats, PfLoadCfg, PfPerm, PfPileup,
                   HmmConfig, PfHapmethHmm, PfHapmethHmmStats, PfHapmethRegions, PfHapmethRegionsStats, PfRegionRec,
                   PfHapmethRank, PfHapmethRankStats, PfRankRec, PfHapmethRankExact, PfHapmethRankExactStats, PfRankExactRec,
-                  REGION_ELIGIBLE, REGION_SPLIT)
+                  PfHapmethTiles, PfHapmethTilesStats, PfRankTileRec, REGION_ELIGIBLE, REGION_SPLIT)
 
 MODE_METHPHASE, MODE_REPORT = 0, 1
 JOB_WINDOWS, JOB_HAPTAG = 0, 1
@@ -162,6 +162,16 @@ def _bind():
                                             C.POINTER(PfHapmethRankStats), C.POINTER(PfHapmethRankExactStats)]
     L.pf_write_rank_exact.argtypes = [C.c_char_p, C.POINTER(PfRankRec), C.POINTER(PfRankExactRec), C.c_uint64, C.c_int,
                                       C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    L.pf_hapmeth_run_tiles.argtypes = [C.POINTER(PfHapmethOpts), C.POINTER(PfHapmethDmr), C.POINTER(PfHapmethHmm),
+                                       C.POINTER(PfHapmethPerm), C.POINTER(PfHapmethAssign), C.POINTER(PfHapmethTagcheck),
+                                       C.POINTER(PfHapmethRegions), C.POINTER(PfHapmethRank), C.POINTER(PfHapmethRankExact),
+                                       C.POINTER(PfHapmethTiles), C.POINTER(PfHapmethStats), C.POINTER(PfHapmethDmrStats),
+                                       C.POINTER(PfHapmethHmmStats), C.POINTER(PfHapmethPermStats),
+                                       C.POINTER(PfHapmethAssignStats), C.POINTER(PfHapmethTagcheckStats),
+                                       C.POINTER(PfHapmethRegionsStats), C.POINTER(PfHapmethRankStats),
+                                       C.POINTER(PfHapmethRankExactStats), C.POINTER(PfHapmethTilesStats)]
+    L.pf_write_rank_tiles.argtypes = [C.c_char_p, C.POINTER(PfRankRec), C.POINTER(PfRankTileRec), C.c_uint64,
+                                      C.POINTER(C.c_uint64)]
     L.pf_bh_adjust_p.argtypes = [vp, vp, C.c_uint64, vp]
     L.pf_write_rank.argtypes = [C.c_char_p, C.POINTER(PfRankRec), C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
     L.pf_regions_load.argtypes = [C.c_char_p, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(vp)]
@@ -539,8 +549,9 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
                   dmr_blocks: Optional[str] = None, dmr_perm: int = 0, dmr_seed: int = 1,
                   assign: Optional[AssignConfig] = None, tag_check=False,
                   dmr_hmm: Optional[HmmConfig] = None, regions: Optional[str] = None, dmr_rank: bool = False,
-                  dmr_rank_min_calls: int = 3, rank_exact: bool = False, rank_exact_max: int = 64) -> Dict:
-    """`pomfret-amd hapmeth` (pf_hapmeth_run): the per-haplotype CpG
+                  dmr_rank_min_calls: int = 3, rank_exact: bool = False, rank_exact_max: int = 64, tile: int = 0,
+                  tile_min_calls: int = 3) -> Dict:
+    """`pomfret-amd hapmeth` (pf_hapmeth_run_tiles): the per-haplotype CpG
     methylation of a haplotagged BAM, written to out_prefix + .hapmeth.bed
     (chrom, start, end, meth / unmeth calls of haplotype 1, haplotype 2 and
     the other reads, the two-sided Fisher p of haplotype 1 against 2).
@@ -611,8 +622,25 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     counted reads, exact_p where there is one and rank_p elsewhere, and its
     q-value with regions.  The file's first 17 columns and every other file
     stay the same bytes.  Adds rank_exact (lines with an exact_p),
-    rank_exact_over (regions over rank_exact_max) and rank_exact_ms_kernels."""
+    rank_exact_over (regions over rank_exact_max) and rank_exact_ms_kernels.
+    tile: a tile width in bases (`--tile`; 0: off) also writes out_prefix +
+    .hapmeth.tiles.tsv, the genome-wide scan (pf_hapmeth_run_tiles,
+    pf_write_rank_tiles): every tile of each contig, or of `region` counted
+    from its start, that holds a tagged read's call, under dmr_rank's test in
+    the first pass, with the counted reads' calls, delta, block (split by a
+    dmr_blocks phase block: counted, not tested) and rank_q over the run's
+    tested tiles.  tile is 100 .. chunk_size and chunk_size a multiple of it;
+    a read counts with at least tile_min_calls calls in the tile.  Needs no
+    dmr, goes with every other option and changes no other file.  Adds
+    tiles_path, n_tiles (planned), tiles_written, tiles_tested, tiles_split and
+    tiles_ms_kernels to the dict."""
     L = _bind()
+    if tile:
+        cs = int(chunk_size) if chunk_size else 100_000
+        if not 100 <= int(tile) <= cs or cs % int(tile):
+            raise PomfretError("hapmeth_files: tile is 100 .. chunk_size, and chunk_size must be a multiple of tile")
+        if not 1 <= int(tile_min_calls) <= 65535:
+            raise PomfretError("hapmeth_files: tile_min_calls is 1 .. 65535")
     if regions is not None:
         if dmr_hmm is not None:
             raise PomfretError("hapmeth_files: regions gives the regions: it excludes dmr_hmm")
@@ -640,68 +668,31 @@ def hapmeth_files(bam: str, out_prefix: str, region: Optional[str] = None, chunk
     o = PfHapmethOpts(bam.encode(), out_prefix.encode(), region.encode() if region else None, int(chunk_size),
                       int(job_windows), lc.to_c(), int(threads), int(bool(host_fetch)), int(device), 0)
     st = PfHapmethStats()
-    if dmr is None:
-        _check(L.pf_hapmeth_main(C.byref(o), C.byref(st)), "pf_hapmeth_main")
-    else:
-        d = PfHapmethDmr(dmr.to_c(), float(dmr_max_p), dmr_blocks.encode() if dmr_blocks else None)
-        dst = PfHapmethDmrStats()
-        pm = PfHapmethPerm(int(dmr_perm), int(dmr_seed))
-        pst = PfHapmethPermStats()
-        if dmr_rank:
-            rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
-            am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
-            tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
-            rg = PfHapmethRegions(regions.encode()) if regions is not None else None
-            hm = PfHapmethHmm(dmr_hmm.to_c()) if dmr_hmm is not None else None
-            km, kst = PfHapmethRank(int(dmr_rank_min_calls)), PfHapmethRankStats()
-            hst, ast, tst, rst = PfHapmethHmmStats(), PfHapmethAssignStats(), PfHapmethTagcheckStats(), PfHapmethRegionsStats()
-            xm, xst = PfHapmethRankExact(int(rank_exact_max)), PfHapmethRankExactStats()
-            _check(L.pf_hapmeth_run_rank_exact(C.byref(o), C.byref(d), C.byref(hm) if hm is not None else None,
-                                               C.byref(pm) if dmr_perm else None,
-                                               C.byref(am) if assign is not None or tag_check else None,
-                                               C.byref(tm) if tag_check else None, C.byref(rg) if rg is not None else None,
-                                               C.byref(km), C.byref(xm) if rank_exact else None, C.byref(st), C.byref(dst),
-                                               C.byref(hst), C.byref(pst), C.byref(ast), C.byref(tst), C.byref(rst),
-                                               C.byref(kst), C.byref(xst)), "pf_hapmeth_run_rank_exact")
-        elif regions is not None:
-            rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
-            am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
-            tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
-            rg = PfHapmethRegions(regions.encode())
-            hst, ast, tst, rst = PfHapmethHmmStats(), PfHapmethAssignStats(), PfHapmethTagcheckStats(), PfHapmethRegionsStats()
-            _check(L.pf_hapmeth_run_regions(C.byref(o), C.byref(d), None, C.byref(pm) if dmr_perm else None,
-                                            C.byref(am) if assign is not None or tag_check else None,
-                                            C.byref(tm) if tag_check else None, C.byref(rg), C.byref(st), C.byref(dst),
-                                            C.byref(hst), C.byref(pst), C.byref(ast), C.byref(tst), C.byref(rst)),
-                   "pf_hapmeth_run_regions")
-        elif dmr_hmm is not None:
-            rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
-            am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
-            tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
-            hm = PfHapmethHmm(dmr_hmm.to_c())
-            hst, ast, tst = PfHapmethHmmStats(), PfHapmethAssignStats(), PfHapmethTagcheckStats()
-            _check(L.pf_hapmeth_run_hmm(C.byref(o), C.byref(d), C.byref(hm), C.byref(pm) if dmr_perm else None,
-                                        C.byref(am) if assign is not None or tag_check else None,
-                                        C.byref(tm) if tag_check else None, C.byref(st), C.byref(dst), C.byref(hst),
-                                        C.byref(pst), C.byref(ast), C.byref(tst)), "pf_hapmeth_run_hmm")
-        elif tag_check:
-            rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
-            am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
-            tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
-            ast, tst = PfHapmethAssignStats(), PfHapmethTagcheckStats()
-            _check(L.pf_hapmeth_run_tagcheck(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(am),
-                                             C.byref(tm), C.byref(st), C.byref(dst), C.byref(pst), C.byref(ast),
-                                             C.byref(tst)), "pf_hapmeth_run_tagcheck")
-        elif assign is None:
-            _check(L.pf_hapmeth_run_perm(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(st),
-                                         C.byref(dst), C.byref(pst)), "pf_hapmeth_run_perm")
-        else:
-            am = PfHapmethAssign(assign.min_llr_q16, int(assign.min_calls), 0)
-            ast = PfHapmethAssignStats()
-            _check(L.pf_hapmeth_run_assign(C.byref(o), C.byref(d), C.byref(pm) if dmr_perm else None, C.byref(am),
-                                           C.byref(st), C.byref(dst), C.byref(pst), C.byref(ast)), "pf_hapmeth_run_assign")
+    # every combination is one call: the earlier entry points are this one with NULLs
+    d = PfHapmethDmr(dmr.to_c(), float(dmr_max_p), dmr_blocks.encode() if dmr_blocks else None) if dmr is not None else None
+    pm = PfHapmethPerm(int(dmr_perm), int(dmr_seed))
+    rule = assign if assign is not None else tag_check if isinstance(tag_check, AssignConfig) else AssignConfig()
+    am = PfHapmethAssign(rule.min_llr_q16, int(rule.min_calls), 0)
+    tm = PfHapmethTagcheck(0 if assign is not None else HAPMETH_TAGCHECK_RULE_ONLY, 0)
+    rg = PfHapmethRegions(regions.encode()) if regions is not None else None
+    hm = PfHapmethHmm(dmr_hmm.to_c()) if dmr_hmm is not None else None
+    km, xm = PfHapmethRank(int(dmr_rank_min_calls)), PfHapmethRankExact(int(rank_exact_max))
+    lm = PfHapmethTiles(int(tile), int(tile_min_calls), dmr_blocks.encode() if dmr_blocks else None)
+    dst, pst, hst, ast = PfHapmethDmrStats(), PfHapmethPermStats(), PfHapmethHmmStats(), PfHapmethAssignStats()
+    tst, rst, kst, xst = PfHapmethTagcheckStats(), PfHapmethRegionsStats(), PfHapmethRankStats(), PfHapmethRankExactStats()
+    lst = PfHapmethTilesStats()
+
+    def ref(x, on=True):
+        return C.byref(x) if on and x is not None else None
+    _check(L.pf_hapmeth_run_tiles(C.byref(o), ref(d), ref(hm), ref(pm, dmr_perm), ref(am, assign is not None or tag_check),
+                                  ref(tm, tag_check), ref(rg), ref(km, dmr_rank), ref(xm, rank_exact), ref(lm, tile),
+                                  C.byref(st), C.byref(dst), C.byref(hst), C.byref(pst), C.byref(ast), C.byref(tst),
+                                  C.byref(rst), C.byref(kst), C.byref(xst), C.byref(lst)), "pf_hapmeth_run_tiles")
     res = dict(path=out_prefix + ".hapmeth.bed", n_windows=int(st.n_windows), n_skipped=int(st.n_skipped),
                n_records=int(st.n_records), n_sites=int(st.n_sites), ms_kernels=float(st.ms_kernels))
+    if tile:
+        res.update(tiles_path=out_prefix + ".hapmeth.tiles.tsv", n_tiles=int(lst.n_tiles), tiles_written=int(lst.n_written),
+                   tiles_tested=int(lst.n_tested), tiles_split=int(lst.n_split), tiles_ms_kernels=float(lst.ms_kernels))
     if dmr is not None:
         if regions is not None:
             res.update(regions_path=out_prefix + ".hapmeth.regions.bed", n_regions=int(rst.n_regions),
@@ -872,6 +863,32 @@ def write_rank(path: str, recs, bh: bool = False) -> int:
         x.status, x.u2, x.ties = int(r["status"]), int(r["u2"]), int(r["ties"])
     n = C.c_uint64()
     _check(L.pf_write_rank(path.encode(), arr, len(recs), int(bool(bh)), C.byref(n)), "pf_write_rank")
+    return int(n.value)
+
+
+def write_rank_tiles(path: str, recs) -> int:
+    """{prefix}.hapmeth.tiles.tsv from records (pf_write_rank_tiles, host only).
+    recs: write_rank's dicts with sum [4] (the counted reads' m1, u1, m2, u2)
+    and optionally split (bool) beside them -- a range of
+    DeviceBatch.rankranges and its tile.  rank_q by Benjamini-Hochberg over the
+    status-0 records that are not split.  Returns the records with a numeric
+    rank_p."""
+    L = _bind()
+    arr = (PfRankRec * max(len(recs), 1))()
+    tarr = (PfRankTileRec * max(len(recs), 1))()
+    for k, r in enumerate(recs):
+        x = arr[k]
+        x.chrom, x.start, x.end = r["chrom"].encode(), int(r["start"]), int(r["end"])
+        for j in range(2):
+            x.reads[j], x.n_short[j] = int(r["n_reads"][j]), int(r["n_short"][j])
+        for j, v in enumerate(np.asarray(r["cls"]).ravel().tolist()):
+            x.cls[j] = int(v)
+        x.status, x.u2, x.ties = int(r["status"]), int(r["u2"]), int(r["ties"])
+        for j in range(4):
+            tarr[k].sum[j] = int(r["sum"][j])
+        tarr[k].split = int(bool(r.get("split", False)))
+    n = C.c_uint64()
+    _check(L.pf_write_rank_tiles(path.encode(), arr, tarr, len(recs), C.byref(n)), "pf_write_rank_tiles")
     return int(n.value)
 
 
